@@ -26,12 +26,22 @@ independent: ranks share nothing on the hot path (weak scaling); for N > 1 the l
 carries ``record_gather``: the RCCL all_gather of every rank's game records (C4's only
 collective), timed after the measured region.
 
-Extra objects on the JSON line: ``roofline`` for the dominant kernel (the fused trunk,
-MFMA-bound), ``roofline_tree`` for the hand-written HIP search kernels (HBM-bound),
-``cpu_baseline`` for the reference-shaped CPU port (oracle/, config C1) timed on this box's
-host cores on rank 0 at N=1.  ``traffic`` figures come from the tracked PMC table
-profiles/pmc_traffic.json (rocprofv3 passes of exactly the named kernel and shape); they are
-null when no pass exists for the kernel that ran.
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps,
+the outputs (``--dump-outputs DIR``) and the line.  It times the arithmetic ``--precision``
+resolves to (``auto``: the product's own probe).  Everything else moves behind ``--full``:
+the parity gate against the fp32 oracle (and the re-timed window in f16x3 when the timed mode
+misses the 1e-3 bar), the timed move boundary, the stamped in-graph phase leg, the eager phase
+profile, the other precision modes' legs, the games/hour leg, the record gather (N > 1) and the
+extra objects on the line: ``roofline`` for the dominant kernel (the fused trunk, MFMA-bound),
+``roofline_tree`` for the hand-written HIP search kernels (HBM-bound), ``cpu_baseline`` for the
+reference-shaped CPU port (oracle/, config C1) timed on this box's host cores on rank 0 at N=1.
+``traffic`` figures come from the tracked PMC table profiles/pmc_traffic.json (rocprofv3 passes
+of exactly the named kernel and shape); they are null when no pass exists for the kernel that ran.
+
+``--dump-outputs DIR``: what the K timed steps leave for a caller of the lockstep search (rank
+0's games, read right behind the window; see ``last_step_outputs``), one ``DIR/<name>.npy`` per
+array.  The inputs (weights, games, noise) are seeded, so two builds run with the same arguments
+can be compared output for output.
 """
 import argparse
 import contextlib
@@ -114,6 +124,13 @@ def parse():
                         "the batch mixes; 0 = skip")
     p.add_argument("--numpy-promotion", default="auto", choices=["auto", "nep50", "legacy"],
                    help="arithmetic of the PUCT term 10 * prior (mctree.py:79-87); auto = the installed numpy's")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: parity gate (and re-timing), move boundary, phase and kernel profiles, "
+                        "rooflines, the other precision modes, games/hour, record gather, CPU baseline.  The options "
+                        "that size those legs (--strict-steps, --parity-positions, --graph-phase-steps, --gph-seconds, "
+                        "--no-cpu-baseline, --cpu-seconds) act only with --full")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (rank 0's games) as DIR/<name>.npy, float32 / float64")
     return p.parse_args()
 
 
@@ -603,7 +620,39 @@ def play_opening(run, moves, sims):
         run.end_move()                                     # (a shortened move draws its noise at the boundary)
 
 
-def timed_window(run, a, barrier, model=None, sync=None, stamped=0):
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+
+
+def last_step_outputs(run):
+    """What the timed steps leave for a caller of the lockstep search, read right behind the window: every game's
+    root children (move ids, visit counts, value sums, priors) -- what the move choice at the boundary is made from --
+    and the value the tower gave the last step's S2 leaves.  float32 (float64 for the value sums, as the tree holds
+    them).  Games beyond DUMP_BYTES are sampled: a fixed, seeded choice of rows, listed in ``games``."""
+    import numpy as np
+    eng = run.engine
+    torch.cuda.synchronize()
+    rc = eng.root_children()
+    out = {"root_child_moves": rc["moves"].astype(np.float32), "root_child_visits": rc["visits"].astype(np.float32),
+           "root_child_value_sums": rc["values"].astype(np.float64), "root_child_priors": rc["priors"].astype(np.float32),
+           "root_children": rc["nchild"].astype(np.float32), "root_visits": rc["root_visits"].astype(np.float32),
+           "leaf_value_s2": eng.val_s2.float().cpu().numpy()}
+    G = out["root_visits"].shape[0]
+    per_game = sum(v.nbytes for v in out.values()) // G + 4
+    if G * per_game > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(G, DUMP_BYTES // per_game, replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+        out["games"] = rows.astype(np.float32)
+    return out
+
+
+def write_outputs(path, outputs):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def timed_window(run, a, barrier, model=None, sync=None, stamped=0, outputs=False):
     """W un-timed warm-up steps, then EXACTLY K timed steps between barrier + synchronize pairs.  A window
     shorter than a move is centred on the middle of a move (trees pre-grown un-timed); a few shortened, noisy
     opening moves first (un-timed, ``play_opening``) put every game on a line of its own and load every
@@ -613,16 +662,17 @@ def timed_window(run, a, barrier, model=None, sync=None, stamped=0):
     ``model``: its counter of S1 boards evaluated twice (hybrid) is read INSIDE the window, next to the simulation
     counters -- behind the un-timed steps (round 5 read it in front of them and divided ~21 windows' worth of
     fall-back boards by one window's simulations).  The runner's precision guard is switched off for the window: a
-    mode change (and a graph re-capture) in mid-window would time two arithmetics under one name."""
+    mode change (and a graph re-capture) in mid-window would time two arithmetics under one name.
+    ``outputs``: ``last_step_outputs`` read behind the window (before any stamped step) into ``w["outputs"]``."""
     sync = sync or torch.cuda.synchronize
     guard_every, run.GUARD_EVERY = getattr(run, "GUARD_EVERY", 0), 0
     try:
-        return _timed_window(run, a, barrier, model, sync, stamped)
+        return _timed_window(run, a, barrier, model, sync, stamped, outputs)
     finally:
         run.GUARD_EVERY = guard_every
 
 
-def _timed_window(run, a, barrier, model, sync, stamped):
+def _timed_window(run, a, barrier, model, sync, stamped, outputs):
     if run._sims_in_move:                         # a second window (another precision mode): finish the move
         run.end_move()
     # un-timed opening: the games leave their common line; it also loads every move-boundary kernel and host path
@@ -635,7 +685,7 @@ def _timed_window(run, a, barrier, model, sync, stamped):
         second_half = a.sims // 2 + 8
         start = second_half if a.steps <= a.sims - second_half - 1 else (a.sims - a.steps) // 2
         pre = max(0, start - a.warmup)
-    run.steps(pre + a.warmup)
+    run.steps(pre)
     distinct = None
     get_positions = getattr(run.engine.ctx, "get_positions", None)
     if get_positions is not None:
@@ -645,6 +695,7 @@ def _timed_window(run, a, barrier, model, sync, stamped):
         distinct = int(len(np.unique(get_positions(), axis=0)))
     gp = graph_phases_begin(run, stamped) if stamped else None      # (may move on into the next move: room for its leg)
     run.engine.prepare_graphs(a.steps)        # (nothing is captured inside the timed region)
+    run.steps(a.warmup)                       # the W warm-up steps run right in front of the window
     fallback = getattr(model, "fallback_boards", None) if getattr(model, "fused", False) else None
     w = {"pre": pre, "window_start": run._sims_in_move or 0, "moves0": run.moves_played, "distinct_roots": distinct,
          "c0": run.engine.ctx.counters(), "fb0": fallback() if fallback else 0}
@@ -661,6 +712,8 @@ def _timed_window(run, a, barrier, model, sync, stamped):
     w["sims"] = w["c1"]["sims"] - w["c0"]["sims"]          # simulations completed (backed up) in the timed region
     # fraction of the window's simulations whose S1 board went through the f16x3 fall-back (this rank's games)
     w["twice"] = (w["fb1"] - w["fb0"]) / max(1, w["sims"])
+    if outputs:
+        w["outputs"] = last_step_outputs(run)
     if gp is not None:
         # the stamped leg, right behind the window: same trees, same clocks, no capture in between
         try:
@@ -880,6 +933,60 @@ def measure_games_per_hour(seconds, seed, device, steps_per_graph=None):
     return out
 
 
+def headline(a, world, total_sims, max_dt):
+    """The fields every line carries, plain or --full."""
+    return {"metric": "MCTS simulations/sec at 800 sims/move", "value": total_sims / max_dt,
+            "unit": "simulations/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": max_dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": a.dtype, "data": "synthetic"}
+
+
+def line_config(a, model, eng, probe_at_load, retime):
+    G, F, B = a.games, a.filters, a.blocks
+    cfg_name = {(512, 100, 6, 64): "C2", (4096, 800, 10, 128): "C3 (= C4 per-GPU shard)",
+                (4096, 800, 20, 256): "C5 per-GPU shard"}.get((G, a.sims, B, F), "custom")
+    kern = (trunk_kernel_name(F, G, int(eng.bitplanes) | (2 if model._trunk_mode() == "f16x3" else 0))
+            if model.fused else None)
+    return {"workload": "%s: %d self-play games in lockstep per GPU, %d sims/move, "
+                        "%d-block/%d-filter %s tower, standard start position, "
+                        "Dirichlet noise on" % (cfg_name if a.weights is None else "custom (trained weights)", G, a.sims, B, F,
+                                                "random-init" if a.weights is None else
+                                                "TRAINED (%s)" % os.path.basename(a.weights)),
+            "games_per_gpu": G, "sims_per_move": a.sims, "tower": "%dx%d" % (B, F),
+            "hipgraph": not a.no_graph, "steps_per_hipgraph_launch": eng.STEPS_PER_GRAPH if not a.no_graph else None,
+            "fused_trunk_kernel": bool(model.fused),
+            "policy_format": "legal priors [G,256]" if eng.legal_priors else "full [G,1968]",
+            "tower_precision": getattr(model, "precision", a.dtype),
+            "tower_precision_requested": a.precision, "tower_precision_probe": probe_at_load,
+            "tower_precision_why": ("the mode first timed missed the 1e-3 bar against the fp32 oracle on these "
+                                    "weights (tower_error_vs_fp32.first_timed_mode): timed again in " + model.precision if retime
+                                    else ("asked for by --precision" if a.precision != "auto" else
+                                          "ChessModel(precision='auto'): f16 kept only if within %g of f16x3 on "
+                                          "%d probe positions, else %s" % (model.PROBE_TOL, model.PROBE_POSITIONS,
+                                                                          model.AUTO_STRICT))),
+            "tower_precision_guard": getattr(model, "guard", None),
+            "trunk_kernel": kern,
+            "numpy_promotion": eng.numpy_promotion,
+            "parallelism": "games sharded, no collective on the hot path"}
+
+
+def line_window(a, win):
+    return {"untimed_steps_before": win["pre"] + a.warmup, "first_sim_of_move": win["window_start"],
+            "opening": "%d shortened moves of %d simulations, Dirichlet noise on, un-timed (play_opening)"
+                       % (a.opening_moves, a.opening_sims),
+            "distinct_root_positions": win.get("distinct_roots"), "games": a.games,
+            "move_boundaries_inside": (win["moves1"] - win["moves0"]) // max(1, a.games),
+            "note": "a window shorter than one move is centred mid-move"}
+
+
+def finish(run, dist):
+    if dist is not None:
+        dist.barrier()            # rank 0 is still profiling its phases: nobody tears RCCL down early
+    run.close()
+    if dist is not None:
+        dist.destroy_process_group()
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -928,9 +1035,20 @@ def main():
         per = every_rank(dist, [w["sims"], w["dt"]], rdev)
         return sum(p[0] for p in per), max(p[1] for p in per), [p[1] / a.steps * 1e3 for p in per]
 
-    n_stamped = a.graph_phase_steps if (rank == 0 and model.fused) else 0
-    win = timed_window(run, a, barrier, model, stamped=n_stamped)
+    n_stamped = a.graph_phase_steps if (a.full and rank == 0 and model.fused) else 0
+    dump = a.dump_outputs is not None and rank == 0
+    win = timed_window(run, a, barrier, model, stamped=n_stamped, outputs=dump)
     total_sims, max_dt, rank_ms = reduce_window(win)
+    if not a.full:
+        if rank == 0:
+            if dump:
+                write_outputs(a.dump_outputs, win["outputs"])
+            out = headline(a, world, total_sims, max_dt)
+            out.update(config=line_config(a, model, run.engine, probe_at_load, False), window=line_window(a, win),
+                       per_rank={"ms_per_step": spread(rank_ms)}, full=False)
+            print(json.dumps(out), flush=True)
+        finish(run, dist)
+        return
     timed = {model.precision if model.fused else a.dtype: hybrid_entry({"simulations_per_s": total_sims / max_dt,
                                                                         "ms_per_step": max_dt / a.steps * 1e3}, model, win, run)}
 
@@ -949,7 +1067,7 @@ def main():
         # the timed mode misses the bar on these weights: the headline is the rate of the mode the product
         # falls back to (every output under the bar evaluated in f16x3)
         model.set_precision(model.AUTO_STRICT)
-        win = timed_window(run, a, barrier, model, stamped=n_stamped)
+        win = timed_window(run, a, barrier, model, stamped=n_stamped, outputs=dump)
         total_sims, max_dt, rank_ms = reduce_window(win)
         timed[model.precision] = hybrid_entry({"simulations_per_s": total_sims / max_dt,
                                                "ms_per_step": max_dt / a.steps * 1e3}, model, win, run)
@@ -959,7 +1077,7 @@ def main():
             parity["first_timed_mode"] = {k: failed[k] for k in ("mode", "dpolicy_max", "dvalue_max", "dvalue_p999",
                                                                   "positions_beyond_bar", "within_bar")}
     c0, c1, dt = win["c0"], win["c1"], win["dt"]
-    pre, window_start, moves0, moves1 = win["pre"], win["window_start"], win["moves0"], win["moves1"]
+    moves0, moves1 = win["moves0"], win["moves1"]
     gather = time_record_gather(run, dist, max_plies) if dist is not None else None
     # every rank's trunk launch time (clock / straggler visibility when the scaling curve is run)
     eng = run.engine
@@ -1132,8 +1250,6 @@ def main():
             if model.precision != keep:
                 model.set_precision(keep)
             modes["f16_vs_f16x3_on_probe"] = probe_dist
-        cfg_name = {(512, 100, 6, 64): "C2", (4096, 800, 10, 128): "C3 (= C4 per-GPU shard)",
-                    (4096, 800, 20, 256): "C5 per-GPU shard"}.get((G, a.sims, B, F), "custom")
         timed_mode = getattr(model, "precision", a.dtype)
         whole = tracked_whole_run((G, a.sims, "%dx%d" % (B, F)), timed_mode) if a.weights is None else None
         same_cfg = whole is not None
@@ -1141,38 +1257,9 @@ def main():
         gph = None
         if world == 1 and a.gph_seconds > 0 and model.fused:
             gph = measure_games_per_hour(a.gph_seconds, a.seed, local, a.steps_per_graph)
-        out = {
-            "metric": "MCTS simulations/sec at 800 sims/move", "value": total_sims / max_dt,
-            "unit": "simulations/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": max_dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": "%s: %d self-play games in lockstep per GPU, %d sims/move, "
-                                   "%d-block/%d-filter %s tower, standard start position, "
-                                   "Dirichlet noise on" % (cfg_name if a.weights is None else "custom (trained weights)", G, a.sims, B, F,
-                                                           "random-init" if a.weights is None else
-                                                           "TRAINED (%s)" % os.path.basename(a.weights)),
-                       "games_per_gpu": G, "sims_per_move": a.sims, "tower": "%dx%d" % (B, F),
-                       "hipgraph": not a.no_graph, "steps_per_hipgraph_launch": eng.STEPS_PER_GRAPH if not a.no_graph else None,
-                       "fused_trunk_kernel": bool(model.fused),
-                       "policy_format": "legal priors [G,256]" if eng.legal_priors else "full [G,1968]",
-                       "tower_precision": getattr(model, "precision", a.dtype),
-                       "tower_precision_requested": a.precision, "tower_precision_probe": probe_at_load,
-                       "tower_precision_why": ("the mode first timed missed the 1e-3 bar against the fp32 oracle on these "
-                                               "weights (tower_error_vs_fp32.first_timed_mode): timed again in " + model.precision if retime
-                                               else ("asked for by --precision" if a.precision != "auto" else
-                                                     "ChessModel(precision='auto'): f16 kept only if within %g of f16x3 on "
-                                                     "%d probe positions, else %s" % (model.PROBE_TOL, model.PROBE_POSITIONS,
-                                                                                     model.AUTO_STRICT))),
-                       "tower_precision_guard": getattr(model, "guard", None),
-                       "trunk_kernel": kern if model.fused else None,
-                       "numpy_promotion": eng.numpy_promotion,
-                       "parallelism": "games sharded, no collective on the hot path"},
-            "window": {"untimed_steps_before": pre + a.warmup, "first_sim_of_move": window_start,
-                       "opening": "%d shortened moves of %d simulations, Dirichlet noise on, un-timed (play_opening)"
-                                  % (a.opening_moves, a.opening_sims),
-                       "distinct_root_positions": win.get("distinct_roots"), "games": G,
-                       "move_boundaries_inside": inside,
-                       "note": "a window shorter than one move is centred mid-move"},
+        out = headline(a, world, total_sims, max_dt)
+        out.update({
+            "config": line_config(a, model, eng, probe_at_load, retime), "window": line_window(a, win),
             "per_rank": {"ms_per_step": spread(rank_ms), "trunk_launch_ms": spread(rank_k_ms)},
             "move_boundary": boundary, "value_incl_boundaries": incl,
             "moves_per_sec": rate / a.sims,
@@ -1191,17 +1278,15 @@ def main():
             "gflop_per_sim": 2 * 2 * model.macs_per_eval() / 1e9,
             "roofline": roof, "roofline_tree": tree, "roofline_compliant": compliant, "precision_modes": modes,
             "tower_error_vs_fp32": parity,
-        }
+        })
         if gather is not None:
             out["record_gather"] = gather
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.cpu_seconds)
+        if dump:
+            write_outputs(a.dump_outputs, win["outputs"])
         print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()            # rank 0 is still profiling its phases: nobody tears RCCL down early
-    run.close()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish(run, dist)
 
 
 if __name__ == "__main__":

@@ -25,6 +25,9 @@ Run in the authoring container only (needs /root/reference):
 
 * mcts_noise_cases.json -- ``search_move(noise=True)`` after ``np.random.seed(s)``: the noisy
                       policy bit for bit and the move it selects.
+* mcts_live_cases.json -- one 70-simulation ``search_move`` from a five-ply opening in both promotion
+                      modes and its ``compute_policy(noise=True)`` after ``np.random.seed(3)``
+                      (``python -m oracle.make_golden --only live``).
 * selfplay_games.json -- whole games by the reference's own ``selfplay.play_game`` ->
                       ``AgentDistributed.best_move / predict_policy / predict_outcome`` ->
                       ``SelfPlayTree`` -> ``get_game_state`` (functions taken out of the parsed files by
@@ -389,8 +392,38 @@ def run_case(mct, case, mode):
     }
 
 
+LIVE_PREFIX = ["d2d4", "g8f6", "c2c4", "e7e6", "b1c3"]
+
+
+def write_live(mct):
+    """mcts_live_cases.json: 70 simulations of the reference's own search from a five-ply opening
+    (FakeNet seed 17, prior_shift 30; the oracle agent with and without float64-widened priors) and
+    its noisy compute_policy after np.random.seed(3)."""
+    cases = []
+    for mode in ("nep50", "legacy"):
+        g = OracleGame()
+        for u in LIVE_PREFIX:
+            assert g.move(u)
+        agent = mcts_oracle.OracleAgent(FakeNet(seed=17, prior_shift=30), widen_priors=(mode == "legacy"))
+        tree = mct.SelfPlayTree(g, threads=1)
+        bm, am = tree.search_move(agent, max_iters=70, noise=False, ai_move=True)
+        np.random.seed(3)
+        pol = tree.compute_policy(tree.root, noise=True)
+        cases.append({"mode": mode, "prefix_moves": LIVE_PREFIX, "net_seed": 17, "prior_shift": 30, "sims": 70,
+                      "noise_seed": 3, "visits": [int(c.visits) for c in tree.root.children],
+                      "values": [f64hex(c.value) for c in tree.root.children], "bm": bm, "am": am,
+                      "policy": [f64hex(x) for x in pol]})
+    with open(os.path.join(OUT, "mcts_live_cases.json"), "w") as f:
+        json.dump({"source": "mctree.SelfPlayTree.search_move and compute_policy(noise=True) (mctree.py:159-198, "
+                             "305-322) of the reference, imported with a stub game module; numpy %s" % np.__version__,
+                   "cases": cases}, f)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["--only", "live"]:       # just the fixture of test_oracle_matches_reference_mctree_live
+        write_live(ref_loader.load_mctree())
+        return
     if sys.argv[1:] == ["--only", "r5"]:         # just the round-5 fixture (the others take ~4.5 minutes)
         write_r5(ref_loader.load_mctree())
         return

@@ -192,3 +192,31 @@ def test_multiprocess_env_is_set_by_the_entry_points_not_at_import(monkeypatch):
     assert os.environ["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", "1")
     assert chessrl_amd.multiprocess_env() == "1"
+
+
+def test_dumped_outputs_are_float_arrays_within_the_cap_and_a_fixed_sample(bench, monkeypatch, tmp_path):
+    """--dump-outputs: last_step_outputs hands over float32 / float64 arrays only; a batch beyond DUMP_BYTES is cut to
+    a fixed, seeded sample of games (the same rows every run, listed in ``games``) that fits the cap."""
+    import numpy as np
+    import torch
+    G = 96
+    rng = np.random.default_rng(1)
+    rc = {"nchild": rng.integers(0, 40, G).astype(np.int32), "visits": rng.integers(0, 800, (G, 256)).astype(np.int32),
+          "values": rng.standard_normal((G, 256)), "priors": rng.random((G, 256)).astype(np.float32),
+          "moves": rng.integers(0, 4096, (G, 256)).astype(np.uint16), "replies": np.zeros((G, 256), np.uint16),
+          "root_visits": rng.integers(1, 800, G).astype(np.int32)}
+    eng = types.SimpleNamespace(root_children=lambda: rc, val_s2=torch.linspace(-1, 1, G))
+    run = types.SimpleNamespace(engine=eng)
+    monkeypatch.setattr(bench.torch.cuda, "synchronize", lambda: None)
+    whole = bench.last_step_outputs(run)
+    assert "games" not in whole and all(v.dtype in (np.float32, np.float64) for v in whole.values())
+    assert np.array_equal(whole["root_child_visits"], rc["visits"]) and np.array_equal(whole["root_child_value_sums"], rc["values"])
+    assert np.array_equal(whole["root_child_moves"], rc["moves"]) and whole["leaf_value_s2"].shape == (G,)
+    cap = sum(v.nbytes for v in whole.values()) // 3
+    monkeypatch.setattr(bench, "DUMP_BYTES", cap)
+    a, b = bench.last_step_outputs(run), bench.last_step_outputs(run)
+    assert sum(v.nbytes for v in a.values()) <= cap and 0 < len(a["games"]) < G
+    rows = a["games"].astype(np.int64)
+    assert np.array_equal(rows, b["games"]) and np.array_equal(a["root_child_visits"], rc["visits"][rows])
+    bench.write_outputs(str(tmp_path / "out"), a)
+    assert sorted(os.listdir(str(tmp_path / "out"))) == sorted(k + ".npy" for k in a)

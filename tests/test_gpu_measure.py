@@ -175,3 +175,39 @@ def test_the_reply_rule_of_hybrid_is_watched_on_the_runs_own_positions_and_heals
             break
     assert seen > 0 and model.guard["reply_rule"]["differ_but_not_listed"] == seen
     run.close()
+
+
+def test_a_plain_bench_run_times_k_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """bench.py without --full prints the headline only: ``steps`` = K, ``ms_per_step`` the time of one of them (one
+    simulation per game each).  --dump-outputs writes what the last timed step computed, float32 / float64 within
+    64 MB, and two runs with the same arguments write the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    G, K = 64, 6
+    args = ["--gpus", "1", "--steps", str(K), "--warmup", "2", "--games", str(G), "--sims", "16", "--blocks", "2",
+            "--filters", "64"]
+    dumps = []
+    for i in range(2):
+        d = str(tmp_path / ("run%d" % i))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--dump-outputs", d],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == K and line["warmup"] == 2 and line["higher_is_better"] is True
+        assert line["unit"] == "simulations/s" and line["dtype"] == "f16" and line["metric"].startswith("MCTS")
+        assert line["value"] * line["ms_per_step"] * 1e-3 == pytest.approx(G, rel=0.1)
+        assert not {"roofline", "cpu_baseline", "tower_error_vs_fp32", "precision_modes", "move_boundary",
+                    "self_play_games_per_hour_measured"} & set(line)
+        arrs = {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert {"root_child_moves", "root_child_visits", "root_child_value_sums", "leaf_value_s2"} <= set(arrs)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["root_child_visits"].shape == (G, 256) and arrs["root_child_visits"].sum() > 0
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

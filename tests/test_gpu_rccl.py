@@ -72,7 +72,8 @@ def test_bench_one_rank_under_a_launcher_environment_takes_the_rccl_branch():
                MASTER_PORT="29654", CRL_BENCH_FORCE_GROUP="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6",
                           "--warmup", "2", "--games", "64", "--sims", "16", "--blocks", "2", "--filters", "64",
-                          "--no-cpu-baseline", "--gph-seconds", "3"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--gph-seconds", "3"], env=env, capture_output=True, text=True,
+                         timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["value"] > 0

@@ -1,5 +1,5 @@
 """CPU: the MCTS oracle against the committed golden vectors (outputs of the reference's own
-mctree.py, oracle/make_golden.py) and, where /root/reference exists, against mctree.py live."""
+mctree.py, oracle/make_golden.py)."""
 import json
 import os
 import struct
@@ -7,7 +7,7 @@ import struct
 import numpy as np
 import pytest
 
-from oracle import mcts_oracle, ref_loader
+from oracle import mcts_oracle
 from oracle.chess_oracle import OracleGame, board_from_fen
 from oracle.fakenet import FakeNet
 
@@ -136,25 +136,20 @@ def test_round5_goldens_hold_the_fivefold_of_a_cleaned_fen_root(golden_dir):
     assert len(cs["unclean_rights_king_off_e1"]["visits"]) == 24      # no white castling among the root's moves
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="/root/reference not present on this box")
 @pytest.mark.parametrize("mode", ["nep50", "legacy"])
-def test_oracle_matches_reference_mctree_live(mode):
-    mct = ref_loader.load_mctree()
-    g = OracleGame()
-    for u in ["d2d4", "g8f6", "c2c4", "e7e6", "b1c3"]:
-        g.move(u)
-    net = FakeNet(seed=17, prior_shift=30)
-    agent = mcts_oracle.OracleAgent(net, widen_priors=(mode == "legacy"))
-    tree = mct.SelfPlayTree(g, threads=1)
-    mv = tree.search_move(agent, max_iters=70, noise=False, ai_move=True)
-    r = mcts_oracle.search(g, mcts_oracle.OracleAgent(net), 70, noise=False, mode=mode)
-    assert [c.visits for c in tree.root.children] == r.visits and mv == r.moves
-    assert [float(c.value) for c in tree.root.children] == r.values
-    np.random.seed(3)
-    p_ref = tree.compute_policy(tree.root, noise=True)
-    np.random.seed(3)
+def test_oracle_matches_reference_mctree_live(golden_dir, mode):
+    """mcts_live_cases.json: a 70-simulation search that the reference's own mctree.py ran from a five-ply opening
+    (oracle/make_golden.py --only live) -- visit counts, value sums, the chosen moves -- and its noisy
+    compute_policy after np.random.seed(3), bit for bit."""
+    c = [c for c in load_cases(golden_dir, "mcts_live_cases.json") if c["mode"] == mode][0]
+    g = case_game(c)
+    net = FakeNet(seed=c["net_seed"], prior_shift=c["prior_shift"])
+    r = mcts_oracle.search(g, mcts_oracle.OracleAgent(net), c["sims"], noise=False, mode=mode)
+    assert r.visits == c["visits"] and tuple(r.moves) == (c["bm"], c["am"])
+    assert [struct.pack(">d", v).hex() for v in r.values] == c["values"]
+    np.random.seed(c["noise_seed"])
     p_mine = mcts_oracle.compute_policy(r.visits, r.root_visits, len(g), noise=True)
-    assert np.array_equal(p_ref, p_mine)
+    assert [struct.pack(">d", p).hex() for p in p_mine] == c["policy"]
 
 
 def test_tau_schedule_and_denominator():

@@ -52,7 +52,7 @@ for cfg in "c3 --steps 800 --warmup 200" "c5g --blocks 20 --filters 256 --steps 
   set -- $cfg; name=$1; shift
   rm -rf /tmp/st_$name
   lim=900; [ "$name" = c5g ] && lim=400        # (a tracer that aborts the queue leaves the process hanging)
-  timeout $lim rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st_$name -- python3 $R/bench.py --no-cpu-baseline --parity-positions 0 --gph-seconds 0 "$@" > $O/bench_${name}_profiled.json 2> $O/bench_${name}.err
+  timeout $lim rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st_$name -- python3 $R/bench.py --full --no-cpu-baseline --parity-positions 0 --gph-seconds 0 "$@" > $O/bench_${name}_profiled.json 2> $O/bench_${name}.err
   find /tmp/st_$name -name "*kernel_stats.csv" -exec cp {} $O/bench_${name}_kernel_stats.csv \;
   find /tmp/st_$name -name "*domain_stats.csv" -exec cp {} $O/bench_${name}_domain_stats.csv \;
 done

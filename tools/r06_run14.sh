@@ -5,8 +5,8 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06; mkdir -p $O
 python tools/make_sharp_weights.py $O/sharp_10x128.npz 10 128 7 > $O/make_sharp.log 2>&1
 python tools/make_sharp_weights.py $O/sharp_20x256.npz 20 256 7 >> $O/make_sharp.log 2>&1
-timeout 900 python bench.py --weights $O/sharp_10x128.npz --steps 400 --warmup 100 --gph-seconds 0 --no-cpu-baseline > $O/bench_c3_sharp.json 2> $O/bench_c3_sharp.err; echo "c3 sharp rc $?"
-timeout 900 python bench.py --weights $O/sharp_20x256.npz --steps 40 --warmup 10 --gph-seconds 0 --no-cpu-baseline > $O/bench_c5_sharp.json 2> $O/bench_c5_sharp.err; echo "c5 sharp rc $?"
+timeout 900 python bench.py --full --weights $O/sharp_10x128.npz --steps 400 --warmup 100 --gph-seconds 0 --no-cpu-baseline > $O/bench_c3_sharp.json 2> $O/bench_c3_sharp.err; echo "c3 sharp rc $?"
+timeout 900 python bench.py --full --weights $O/sharp_20x256.npz --steps 40 --warmup 10 --gph-seconds 0 --no-cpu-baseline > $O/bench_c5_sharp.json 2> $O/bench_c5_sharp.err; echo "c5 sharp rc $?"
 rm -f $O/sharp_10x128.npz $O/sharp_20x256.npz
 python - <<'PY'
 import json

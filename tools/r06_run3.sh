@@ -12,7 +12,7 @@ Q="--steps 16 --warmup 8 --no-cpu-baseline --parity-positions 0 --strict-steps 0
 tr() {  # name args...
   local name=$1; shift
   rm -rf /tmp/tr_$name
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_$name -- python3 $R/bench.py $Q "$@" > $R/$O/trace_$name.json 2> $R/$O/trace_$name.err
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_$name -- python3 $R/bench.py --full $Q "$@" > $R/$O/trace_$name.json 2> $R/$O/trace_$name.err
   echo "trace $name rc $?"
   find /tmp/tr_$name -name "*kernel_stats.csv" -exec cp {} $R/$O/trace_${name}_kernel_stats.csv \;
 }
