@@ -18,7 +18,8 @@
 //     weights per 768 MFMAs of the workgroup = 43 B per MFMA;
 //   * a wave owns one board x 128 output channels: 4 x 8 accumulator blocks of 16 positions x 16 channels = 128 registers
 //     (no skip stream in registers: it is the block's input, re-read from the activation image by the second convolution's
-//     epilogue as hi + lo -- exact in fp32); per (chunk, tap) 4 + 4 activation and 8 + 8 weight fragment reads feed 96 MFMAs:
+//     epilogue as hi + lo -- a sum exact in fp32, but of the 22 bits the pair holds: within 2^-22 of the fp32 value the
+//     previous epilogue rounded, not equal to it as k_trunk_x16's register skip is); per (chunk, tap) 4 + 4 activation and 8 + 8 weight fragment reads feed 96 MFMAs:
 //     0.25 ds_read_b128 per MFMA (k_trunk_x16: 0.5);
 //   * ONE barrier per (chunk, tap) = per 96 MFMAs of a wave: it sits where both weight planes of the tap are consumed into
 //     registers, publishes the next tap's two planes (requested one tap earlier) and frees the two slots for the tap after;
@@ -541,7 +542,8 @@ __global__ __launch_bounds__(512, 2) void k_layer_conv(const unsigned char *__re
             unsigned char *dst = outp + ((size_t)((obase >> 5) + g) * G::ROWS + board * 64 + 16 * pt + r) * G::GROW + q * 16;
             f32x4v o[2] = {acc[pt][2 * g], acc[pt][2 * g + 1]};
             if constexpr (KIND >= 2) {
-                // the skip connection: the block's input as it stands in the image, hi + lo (exact in fp32)
+                // the skip connection: the block's input as it stands in the image, hi + lo (the sum is exact in fp32; the pair
+                // holds 22 bits: |hi + lo - x| <= 2^-22 |x| of the fp32 x stored, and 2^-25 absolute once lo is an fp16 subnormal)
                 const half8 xh = *reinterpret_cast<const half8 *>(dst), xl = *reinterpret_cast<const half8 *>(dst + 64);
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
