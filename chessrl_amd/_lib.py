@@ -57,6 +57,7 @@ SYMBOLS = [
     "crl_heads_forward_legal", "crl_heads_forward_legal_raw", "crl_heads_raw_supported", "crl_heads_set_sliced_max",
     "crl_set_policy_stats", "crl_abi_version", "crl_source_hash", "crl_reply_margin", "crl_trunk_forward_indexed", "crl_trunk_workspace_bytes",
     "crl_end_move_fetch", "crl_advance_fetch",
+    "crl_reroot", "crl_reroot_fetch", "crl_search_begin_kept", "crl_copy_game_tree", "crl_fetch_tree",
     "crl_im2col3x3_f32", "crl_col2im3x3_f32", "crl_stamp", "crl_stamp_clock_khz",
 ]
 
@@ -65,7 +66,7 @@ class HipLibraryError(RuntimeError):
     pass
 
 
-ABI_VERSION = 8          # include/chessrl_hip.h: CRL_ABI_VERSION (checked against the loaded library)
+ABI_VERSION = 9          # include/chessrl_hip.h: CRL_ABI_VERSION (checked against the loaded library)
 _HASH_MARK = b"CRL_SRC_HASH="
 
 
@@ -200,6 +201,11 @@ def lib():
     L.crl_counters.argtypes = [vp, vp]
     L.crl_end_move_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.crl_advance_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.crl_reroot.argtypes = [vp, vp, i32, vp, vp]
+    L.crl_reroot_fetch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.crl_search_begin_kept.argtypes = [vp, vp]
+    L.crl_copy_game_tree.argtypes = [vp, i32, i32]
+    L.crl_fetch_tree.argtypes = [vp, i32, vp, i32, vp, i32, vp]
     L.crl_trunk_forward.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.crl_trunk_forward_bitplanes.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.crl_trunk_forward_x.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, ctypes.c_size_t]
@@ -308,6 +314,10 @@ class Context(object):
         """Slot ``dst`` becomes a deep copy of slot ``src`` of another context on the same GPU."""
         self._ck(self._L.crl_copy_game_from(self._h, dst, src_ctx._h, src), "crl_copy_game_from")
 
+    def copy_game_tree(self, dst, src):
+        """``copy_game`` that carries the slot's live search tree along."""
+        self._ck(self._L.crl_copy_game_tree(self._h, dst, src), "crl_copy_game_tree")
+
     def sync(self):
         self._ck(self._L.crl_sync(self._h), "crl_sync")
 
@@ -383,6 +393,10 @@ class Context(object):
     def search_begin(self, dev_planes):
         self._ck(self._L.crl_search_begin(self._h, ctypes.c_void_p(dev_planes)), "crl_search_begin")
 
+    def search_begin_kept(self, dev_planes):
+        """``search_begin`` that leaves the roots ``reroot`` kept as they are."""
+        self._ck(self._L.crl_search_begin_kept(self._h, ctypes.c_void_p(dev_planes)), "crl_search_begin_kept")
+
     def search_root_priors(self, dev_policy):
         self._ck(self._L.crl_search_root_priors(self._h, ctypes.c_void_p(dev_policy)),
                  "crl_search_root_priors")
@@ -442,6 +456,46 @@ class Context(object):
         counts = np.zeros(self.G, np.int32)
         self._ck(self._L.crl_advance_fetch(self._h, _ptr(c), None, None, _ptr(res), _ptr(counts)), "crl_advance_fetch")
         return res, counts
+
+    def reroot(self, chosen, next_sims):
+        """``advance`` that keeps the chosen child's subtree where it fits ``next_sims`` more simulations."""
+        c = np.ascontiguousarray(chosen, dtype=np.int32)
+        assert c.shape == (self.G,)
+        bm = np.zeros(self.G, np.uint16)
+        am = np.zeros(self.G, np.uint16)
+        self._ck(self._L.crl_reroot(self._h, _ptr(c), int(next_sims), _ptr(bm), _ptr(am)), "crl_reroot")
+        return bm, am
+
+    def reroot_fetch(self, chosen, next_sims):
+        """reroot + results + legal-move counts of the next roots + kept nodes / kept children per slot
+        in one synchronising call; returns a dict."""
+        c = np.ascontiguousarray(chosen, dtype=np.int32)
+        assert c.shape == (self.G,)
+        out = {"bm": np.zeros(self.G, np.uint16), "am": np.zeros(self.G, np.uint16),
+               "results": np.zeros(self.G, np.int8), "legal_counts": np.zeros(self.G, np.int32),
+               "kept_nodes": np.zeros(self.G, np.int32), "kept_children": np.zeros(self.G, np.int32)}
+        self._ck(self._L.crl_reroot_fetch(self._h, _ptr(c), int(next_sims), _ptr(out["bm"]), _ptr(out["am"]),
+                                          _ptr(out["results"]), _ptr(out["legal_counts"]), _ptr(out["kept_nodes"]),
+                                          _ptr(out["kept_children"])), "crl_reroot_fetch")
+        return out
+
+    NODE_DTYPE = np.dtype([("edge0", "<i4"), ("nmoves", "<u2"), ("nexp", "<u2"), ("result", "i1"), ("has_s2", "u1"),
+                           ("parent", "<u2"), ("parent_edge", "<i4"), ("rest", "V160")])
+    EDGE_DTYPE = np.dtype([("value", "<f8"), ("visits", "<i4"), ("prior", "<f4"), ("move", "<u2"), ("child", "<u2"),
+                           ("hint", "<u4")])
+
+    def fetch_tree(self, slot):
+        """Debug read-back of one slot's tree (csrc/state.hpp records): (nodes, edges, info) with
+        info = {n_nodes, edge_top, root_visits, kept}; empty arrays when the slot has no live tree."""
+        cap_n = self.max_sims + 1
+        nodes = np.zeros(cap_n, self.NODE_DTYPE)
+        edges = np.zeros(cap_n * 218, self.EDGE_DTYPE)
+        info = np.zeros(4, np.int32)
+        self._ck(self._L.crl_fetch_tree(self._h, int(slot), _ptr(nodes), cap_n, _ptr(edges), len(edges), _ptr(info)),
+                 "crl_fetch_tree")
+        self.sync()
+        return (nodes[:info[0]], edges[:info[1]],
+                {"n_nodes": int(info[0]), "edge_top": int(info[1]), "root_visits": int(info[2]), "kept": int(info[3])})
 
     def counters(self):
         c = np.zeros(6, dtype=np.uint64)

@@ -21,7 +21,7 @@ class Agent(Player):
     """``model``: a ``ChessModel`` (or any callable planes -> (policy, value) on the GPU)."""
 
     def __init__(self, color, weights=None, endpoint=None, num_threads=6, model=None,
-                 blocks=10, filters=256, numpy_promotion="auto"):
+                 blocks=10, filters=256, numpy_promotion="auto", tree_nodes=None):
         super().__init__(color)
         if model is None:
             from .model import ChessModel
@@ -32,6 +32,10 @@ class Agent(Player):
         self.address = endpoint
         self.num_threads = num_threads
         self.numpy_promotion = numpy_promotion
+        # node budget of the search engines (default: max_iters + 1, a fresh tree per move); a tree continued
+        # from one of its root children (``SelfPlayTree(tree.root.children[k])``) needs room for the kept
+        # subtree + max_iters more nodes
+        self.tree_nodes = tree_nodes
         self._engines = {}
 
     # ---- tower requests (agentdistributed.py:70-99) --------------------------------------
@@ -71,11 +75,13 @@ class Agent(Player):
         return best_move
 
     def engine_for(self, max_iters):
-        """One single-game LockstepEngine per simulation budget, reused across moves."""
+        """One single-game LockstepEngine per simulation budget, reused across moves; its node pool holds
+        max(max_iters + 1, tree_nodes) nodes."""
         from .engine import LockstepEngine
         if max_iters not in self._engines:
+            nodes = max(max_iters + 1, self.tree_nodes or 0)
             self._engines[max_iters] = LockstepEngine(
-                self.model, n_games=1, max_sims=max_iters, numpy_promotion=self.numpy_promotion)
+                self.model, n_games=1, max_sims=nodes - 1, max_nodes=nodes, numpy_promotion=self.numpy_promotion)
         return self._engines[max_iters]
 
     def get_copy(self):

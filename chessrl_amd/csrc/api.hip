@@ -45,6 +45,8 @@ struct crl_ctx {
     int32_t *t_i32a = nullptr;    // [G][256]
     int32_t *t_i32b = nullptr;    // [G]
     int32_t *t_i32c = nullptr;    // [G]
+    int32_t *t_i32d = nullptr;    // [G]
+    int32_t *t_i32e = nullptr;    // [G]
     double *t_f64 = nullptr;      // [G][256]
     float *t_f32 = nullptr;       // [G][256]
     uint8_t *t_u8 = nullptr;      // [G]
@@ -189,7 +191,7 @@ int crl_create(crl_ctx **out, int device, int max_games, int max_sims, int max_p
     A(d.lab_s1, G * MAX_MOVES); A(d.lab_s2, G * MAX_MOVES); A(d.lab_n1, G); A(d.lab_n2, G);
     A(d.counters, G * CNT_N); A(d.err, 1);
     A(ctx->t_moves, G * MAX_MOVES); A(ctx->t_moves2, G * MAX_MOVES); A(ctx->t_i32a, G * MAX_MOVES);
-    A(ctx->t_i32b, G); A(ctx->t_i32c, G); A(ctx->t_f64, G * MAX_MOVES); A(ctx->t_f32, G * MAX_MOVES);
+    A(ctx->t_i32b, G); A(ctx->t_i32c, G); A(ctx->t_i32d, G); A(ctx->t_i32e, G); A(ctx->t_f64, G * MAX_MOVES); A(ctx->t_f32, G * MAX_MOVES);
     A(ctx->t_u8, G); A(ctx->t_u16a, G); A(ctx->t_u16b, G); A(ctx->t_boards, G);
     u16 *lut = nullptr;
     A(lut, 5 * 4096);
@@ -466,7 +468,15 @@ int crl_search_begin(crl_ctx *ctx, void *dev_planes_f16)
 {
     if (!ctx || !dev_planes_f16) return fail(ctx, CRL_ERR_ARG, "crl_search_begin: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    LAUNCH(ctx, k_search_begin, ctx->d, dev_planes_f16);
+    LAUNCH(ctx, k_search_begin, ctx->d, dev_planes_f16, 0);
+    return CRL_OK;
+}
+
+int crl_search_begin_kept(crl_ctx *ctx, void *dev_planes_f16)
+{
+    if (!ctx || !dev_planes_f16) return fail(ctx, CRL_ERR_ARG, "crl_search_begin_kept: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LAUNCH(ctx, k_search_begin, ctx->d, dev_planes_f16, 1);
     return CRL_OK;
 }
 
@@ -571,6 +581,88 @@ int crl_advance_fetch(crl_ctx *ctx, const int32_t *chosen, uint16_t *bm, uint16_
     HIP_TRY(ctx, hipMemcpyAsync(results, ctx->t_u8, G, hipMemcpyDeviceToHost, s));
     LAUNCH(ctx, k_legal_moves, ctx->d, ctx->t_moves, ctx->t_i32b);
     HIP_TRY(ctx, hipMemcpyAsync(legal_counts, ctx->t_i32b, G * 4, hipMemcpyDeviceToHost, s));
+    return check_dev_error(ctx);
+}
+
+// ---- Tree(Node): the chosen child keeps its subtree across the move boundary ---------------------------------
+static int reroot_launch(crl_ctx *ctx, const int32_t *chosen, int next_sims, uint16_t *bm, uint16_t *am,
+                         int32_t *kept_nodes, int32_t *kept_children)
+{
+    const size_t G = ctx->W;
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->t_i32b, chosen, G * 4, hipMemcpyHostToDevice, s));
+    LAUNCH(ctx, k_reroot, ctx->d, (const int32_t *)ctx->t_i32b, next_sims, ctx->t_u16a, ctx->t_u16b, ctx->t_i32d,
+           ctx->t_i32e);
+    if (bm) HIP_TRY(ctx, hipMemcpyAsync(bm, ctx->t_u16a, G * 2, hipMemcpyDeviceToHost, s));
+    if (am) HIP_TRY(ctx, hipMemcpyAsync(am, ctx->t_u16b, G * 2, hipMemcpyDeviceToHost, s));
+    if (kept_nodes) HIP_TRY(ctx, hipMemcpyAsync(kept_nodes, ctx->t_i32d, G * 4, hipMemcpyDeviceToHost, s));
+    if (kept_children) HIP_TRY(ctx, hipMemcpyAsync(kept_children, ctx->t_i32e, G * 4, hipMemcpyDeviceToHost, s));
+    return CRL_OK;
+}
+
+int crl_reroot(crl_ctx *ctx, const int32_t *chosen, int next_sims, uint16_t *bm, uint16_t *am)
+{
+    if (!ctx || !chosen || next_sims < 0) return fail(ctx, CRL_ERR_ARG, "crl_reroot: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = reroot_launch(ctx, chosen, next_sims, bm, am, nullptr, nullptr);
+    return rc != CRL_OK ? rc : check_dev_error(ctx);
+}
+
+int crl_reroot_fetch(crl_ctx *ctx, const int32_t *chosen, int next_sims, uint16_t *bm, uint16_t *am, int8_t *results,
+                     int32_t *legal_counts, int32_t *kept_nodes, int32_t *kept_children)
+{
+    if (!ctx || !chosen || next_sims < 0 || !results || !legal_counts || !kept_nodes || !kept_children)
+        return fail(ctx, CRL_ERR_ARG, "crl_reroot_fetch: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t G = ctx->W;
+    hipStream_t s = ctx->stream;
+    int rc = reroot_launch(ctx, chosen, next_sims, bm, am, kept_nodes, kept_children);
+    if (rc != CRL_OK) return rc;
+    LAUNCH(ctx, k_game_scalars, ctx->d, ctx->t_i32c, (int8_t *)ctx->t_u8);
+    HIP_TRY(ctx, hipMemcpyAsync(results, ctx->t_u8, G, hipMemcpyDeviceToHost, s));
+    LAUNCH(ctx, k_legal_moves, ctx->d, ctx->t_moves, ctx->t_i32b);
+    HIP_TRY(ctx, hipMemcpyAsync(legal_counts, ctx->t_i32b, G * 4, hipMemcpyDeviceToHost, s));
+    return check_dev_error(ctx);
+}
+
+int crl_copy_game_tree(crl_ctx *ctx, int dst, int src)
+{
+    if (!ctx || dst < 0 || src < 0 || dst >= ctx->d.G || src >= ctx->d.G)
+        return fail(ctx, CRL_ERR_ARG, "crl_copy_game_tree: bad slot");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (dst != src) {
+        hipLaunchKernelGGL(k_copy_game, dim3(1), dim3(64), 0, ctx->stream, ctx->d, dst, src);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_copy_tree, dim3(64), dim3(64), 0, ctx->stream, ctx->d, dst, src);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return CRL_OK;
+}
+
+int crl_fetch_tree(crl_ctx *ctx, int slot, void *nodes, int node_cap, void *edges, int edge_cap, int32_t *info)
+{
+    if (!ctx || slot < 0 || slot >= ctx->d.G || !info || node_cap < 0 || edge_cap < 0)
+        return fail(ctx, CRL_ERR_ARG, "crl_fetch_tree: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    GameRow row;
+    HIP_TRY(ctx, hipMemcpyAsync(&row, ctx->d.game + slot, sizeof row, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const bool live = !row.root_dead;
+    info[0] = live ? row.n_nodes : 0;
+    info[1] = live ? row.edge_top : 0;
+    info[2] = live ? row.root_visits : 0;
+    info[3] = row.root_kept;
+    if (info[0] > ctx->d.N || info[1] > ctx->d.ECAP) return fail(ctx, CRL_ERR_STATE, "crl_fetch_tree: tree counters out of range");
+    if (nodes && info[0] > 0) {
+        if (info[0] > node_cap) return fail(ctx, CRL_ERR_CAPACITY, "crl_fetch_tree: node buffer too small");
+        HIP_TRY(ctx, hipMemcpyAsync(nodes, ctx->d.node + (size_t)slot * ctx->d.N, (size_t)info[0] * sizeof(NodeRow),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (edges && info[1] > 0) {
+        if (info[1] > edge_cap) return fail(ctx, CRL_ERR_CAPACITY, "crl_fetch_tree: edge buffer too small");
+        HIP_TRY(ctx, hipMemcpyAsync(edges, ctx->d.edge + (size_t)slot * ctx->d.ECAP, (size_t)info[1] * sizeof(Edge),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    }
     return check_dev_error(ctx);
 }
 

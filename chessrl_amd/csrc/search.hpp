@@ -457,18 +457,25 @@ __global__ __launch_bounds__(64) void k_copy_game_across(Dev d, int dst, Dev sd,
 }
 
 // ---- SelfPlayTree seam kernels -------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_search_begin(Dev d, void *planes)
+// keep != 0 (crl_search_begin_kept): a root that k_reroot kept (GameRow.pad) is left as it is -- Tree(Node),
+// mctree.py:98-111 -- and only the pending-simulation fields are reset; every other slot gets a fresh tree
+__global__ __launch_bounds__(64) void k_search_begin(Dev d, void *planes, int keep)
 {
     __shared__ WaveLds s;
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
     const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
+    const bool kept = keep && uni(d.game[g].root_kept) && !uni(d.game[g].root_dead);
     if (lane == 0) { d.game[g].leaf_kind = LEAF_NONE; d.game[g].path_len = 0; }
     if (d.game[g].game_result != RESULT_NONE) {
-        if (lane == 0) { d.game[g].root_dead = 1; d.game[g].n_nodes = 0; d.game[g].root_visits = 0; }
+        if (lane == 0) { d.game[g].root_dead = 1; d.game[g].n_nodes = 0; d.game[g].root_visits = 0; d.game[g].root_kept = 0; }
         return;
     }
     Board b = d.cur[g];
     const int p = d.game[g].ply;
+    if (kept) {                                   // the tower evaluates every row: give it this root's planes
+        encode_position(d, g, b, 0, p, p, lane, s, planes, r);
+        return;
+    }
     MoveGenInfo mi = wave_movegen(b, lane, s.mv);
     __syncthreads();
     init_edges(d, eb, 0, mi.n, s.mv, lane);
@@ -483,6 +490,7 @@ __global__ __launch_bounds__(64) void k_search_begin(Dev d, void *planes)
         d.game[g].edge_top = mi.n;
         d.game[g].root_visits = 1;                // Tree.__init__: root.visits = 1
         d.game[g].root_dead = 0;
+        d.game[g].root_kept = 0;
         d.path_node[nb] = 0;
     }
     __syncthreads();
@@ -493,6 +501,10 @@ __global__ __launch_bounds__(64) void k_root_priors(Dev d, const float *pol)
 {
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
     if (d.game[g].root_dead) return;
+    if (uni(d.game[g].root_kept)) {                     // a kept root: its edges hold the priors gathered when the node was
+        if (lane == 0) d.game[g].root_kept = 0;         // created; no root evaluation is counted
+        return;
+    }
     NodeMeta m = d.node[(size_t)g * d.N].meta;
     gather_priors(d, r, (size_t)g * d.ECAP, m.edge0, m.nmoves, pol, lane, FMT_FULL);   // the root's policy is always full
     if (lane == 0) d.counters[(size_t)g * CNT_N + CNT_EVALS] += 1;
@@ -765,6 +777,193 @@ __global__ __launch_bounds__(64) void k_advance(Dev d, const int32_t *chosen, u1
     d.game[g].ply = np;
     d.game[g].game_result = cm.result;
     d.game[g].root_dead = 1;                       // the tree is consumed: fresh tree per move
+}
+
+// ---- Tree(Node) (mctree.py:98-111): the chosen child becomes the root and keeps its subtree --------------------
+// k_advance's work, then -- instead of killing the tree -- the subtree below the chosen child is compacted in
+// place so that the child is node 0.  Kept iff the child's state is S2 and running and kept nodes + next_sims
+// fit the node pool (one simulation creates at most one node); otherwise exactly k_advance's outcome.
+//   pass 1  membership + new ids + new edge offsets.  Ids are handed out in creation order (parent < child),
+//           so one ascending pass decides keep[i] = keep[parent[i]]; edge runs were allocated in the same order,
+//           so the new offset of a run is the exclusive prefix sum of the owned edge counts of the kept nodes.
+//           The id map lives in path_node, the new edge0 in path_edge (both dead at a move boundary).
+//   pass 2  parent_edge of every kept node (in place, while every record still sits at its old id), then the
+//           edge runs move down, ascending, 64 records read before they are written; child ids and descent
+//           hints are rewritten on the way.
+//   pass 3  node records move to their new ids (ascending, 64 read before written).
+// No arithmetic on values: sums, visits and priors move as bit patterns.
+constexpr u16 ID_DROPPED = 0xFFFF;
+
+__global__ __launch_bounds__(64) void k_reroot(Dev d, const int32_t *chosen, int next_sims, u16 *bm, u16 *am,
+                                               int32_t *kept_nodes, int32_t *kept_children)
+{
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    if (lane == 0) { bm[r] = NO_MOVE; am[r] = NO_MOVE; kept_nodes[r] = 0; kept_children[r] = 0; }
+    const int k = chosen[r];
+    if (k < 0 || d.game[g].root_dead) return;
+    const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
+    const NodeMeta m = d.node[nb].meta;
+    if (k >= m.nexp || d.game[g].leaf_kind != LEAF_NONE) { if (lane == 0) dev_error(d, DERR_STATE); return; }
+    const Edge ed = d.edge[eb + m.edge0 + (m.nmoves - 1 - k)];
+    const int c = uni(ed.child & CHILD_NONE);
+    const NodeMeta cm = d.node[nb + c].meta;
+    const int p = uni(d.game[g].ply);
+    const int np = p + (cm.has_s2 ? 2 : 1);
+    if (np > d.MAXPLY) { if (lane == 0) dev_error(d, DERR_PLY_POOL); return; }
+    const int n = uni(d.game[g].n_nodes);
+    if (lane == 0) {                                                   // gam.move(bm); gam.move(am) as in k_advance
+        size_t hi = (size_t)g * HIST_RING + ((p + 1) & (HIST_RING - 1));
+        d.hist[hi] = d.node[nb + c].s1;
+        d.hist_hash[hi] = d.node[nb + c].h1;
+        d.rec_moves[(size_t)g * d.MAXPLY + p] = ed.move;
+        bm[r] = ed.move;
+        if (cm.has_s2) {
+            hi = (size_t)g * HIST_RING + ((p + 2) & (HIST_RING - 1));
+            d.hist[hi] = d.node[nb + c].s2;
+            d.hist_hash[hi] = d.node[nb + c].h2;
+            d.rec_moves[(size_t)g * d.MAXPLY + p + 1] = d.node[nb + c].reply;
+            am[r] = d.node[nb + c].reply;
+        }
+        d.cur[g] = d.node[nb + c].s2;
+        d.game[g].ply = np;
+        d.game[g].game_result = cm.result;
+        d.game[g].root_dead = 1;
+        d.game[g].root_kept = 0;
+    }
+    if (!cm.has_s2 || cm.result != RESULT_NONE) return;
+    __syncthreads();                                                   // node c was read before any record moves
+
+    u16 *map = d.path_node + nb;
+    int32_t *ne0 = d.path_edge + nb;
+    // ---- pass 1
+    int K = 0, E = 0;
+    for (int base = c; base < n; base += 64) {
+        const int i = base + lane;
+        const bool in = i < n;
+        int par = 0, owned = 0;
+        if (in) {
+            const NodeMeta mi = d.node[nb + i].meta;
+            par = mi.parent;
+            owned = mi.has_s2 ? mi.nmoves : 0;                         // a node whose game ended on our move owns no run
+        }
+        bool known = !in || i == c || par < base, keep = false;
+        if (in) {
+            if (i == c) keep = true;
+            else if (par < base) keep = par >= c && map[par] != ID_DROPPED;
+        }
+        for (;;) {                                                     // parents inside this chunk
+            const u64 km = __ballot(known), kp = __ballot(keep);
+            if (km == ~0ull) break;
+            if (!known) {
+                const int pl = par - base;
+                if ((km >> pl) & 1) { keep = ((kp >> pl) & 1) != 0; known = true; }
+            }
+        }
+        const u64 kp = __ballot(keep);
+        const int nid = K + popc(kp & ((1ull << lane) - 1));
+        const int x = keep ? owned : 0;
+        int incl = x;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(incl, o);
+            if (lane >= o) incl += y;
+        }
+        if (in) {
+            map[i] = keep ? (u16)nid : ID_DROPPED;
+            if (keep) ne0[i] = E + incl - x;
+        }
+        K += popc(kp);
+        E += __shfl(incl, 63);
+        __threadfence_block();
+        __syncthreads();                                               // the next chunk reads this chunk's map entries
+    }
+    if (K + next_sims > d.N) return;                                   // no room: fresh tree at the next begin
+
+    // ---- pass 2
+    for (int base = c; base < n; base += 64) {
+        const int i = base + lane;
+        bool has_run = false;
+        int oe0 = 0, nm = 0, n0 = 0;
+        if (i < n && map[i] != ID_DROPPED) {
+            const NodeMeta mi = d.node[nb + i].meta;
+            if (i != c)
+                d.node[nb + i].meta.parent_edge = mi.parent_edge - d.node[nb + mi.parent].meta.edge0 + ne0[mi.parent];
+            if (mi.has_s2 && mi.nmoves > 0) { has_run = true; oe0 = mi.edge0; nm = mi.nmoves; n0 = ne0[i]; }
+        }
+        u64 todo = __ballot(has_run);
+        while (todo) {
+            const int l = __ffsll((unsigned long long)todo) - 1;
+            todo &= todo - 1;
+            const int so = __shfl(oe0, l), dn = __shfl(n0, l), cnt = __shfl(nm, l);
+            for (int t = 0; t < cnt; t += 64) {
+                const int j = t + lane;
+                Edge e;
+                e.value = 0.0; e.visits = 0; e.prior = 0.f; e.move = 0; e.child = CHILD_NONE; e.pad = 0;
+                if (j < cnt) {
+                    e = d.edge[eb + so + j];
+                    if (e.child != CHILD_NONE) {
+                        const int cid = e.child & CHILD_NONE;
+                        e.child = (u16)(map[cid] | (e.child & CHILD_TERMINAL));
+                        if (e.pad & HINT_FULL) e.pad = hint_pack(ne0[cid], (int)((e.pad >> HINT_EDGE_BITS) & 0xFFu));
+                    }
+                }
+                __syncthreads();                                       // 64 records read before they are written
+                if (j < cnt) d.edge[eb + dn + j] = e;
+            }
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // ---- pass 3
+    for (int base = c; base < n; base += 64) {
+        const int i = base + lane;
+        const int nid = i < n ? map[i] : ID_DROPPED;
+        const bool kp = nid != ID_DROPPED;
+        NodeRow row;
+        if (kp) {
+            row = d.node[nb + i];
+            row.meta.edge0 = row.meta.has_s2 ? ne0[i] : 0;
+            if (i == c) { row.meta.parent = 0; row.meta.parent_edge = -1; }
+            else row.meta.parent = map[row.meta.parent];
+        }
+        __syncthreads();
+        if (kp) d.node[nb + nid] = row;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (lane == 0) {
+        d.game[g].n_nodes = K;
+        d.game[g].edge_top = E;
+        d.game[g].root_visits = 1;                                     // mctree.py:111
+        d.game[g].root_dead = 0;
+        d.game[g].path_len = 0;
+        d.game[g].root_kept = 1;                                             // root was kept
+        d.path_node[nb] = 0;
+        kept_nodes[r] = K;
+        kept_children[r] = cm.nexp;
+    }
+}
+
+// crl_copy_game_tree: after k_copy_game, the live tree of slot src goes with the game (grid of workgroups)
+__global__ __launch_bounds__(64) void k_copy_tree(Dev d, int dst, int src)
+{
+    if (d.game[src].root_dead) return;
+    const int tid = blockIdx.x * 64 + threadIdx.x, stride = gridDim.x * 64;
+    const size_t nbs = (size_t)src * d.N, nbd = (size_t)dst * d.N;
+    const size_t ebs = (size_t)src * d.ECAP, ebd = (size_t)dst * d.ECAP;
+    const int n = d.game[src].n_nodes, et = d.game[src].edge_top;
+    for (int i = tid; i < n; i += stride) d.node[nbd + i] = d.node[nbs + i];
+    for (int i = tid; i < et; i += stride) d.edge[ebd + i] = d.edge[ebs + i];
+    if (tid == 0) {
+        d.game[dst].n_nodes = n;
+        d.game[dst].edge_top = et;
+        d.game[dst].root_visits = d.game[src].root_visits;
+        d.game[dst].path_len = 0;
+        d.game[dst].root_kept = d.game[src].root_kept;
+        d.game[dst].root_dead = 0;
+        d.path_node[nbd] = 0;
+    }
 }
 
 }  // namespace crl

@@ -3,7 +3,9 @@
 // Everything is structure-of-arrays, game-major, sized at crl_create and never
 // reallocated.  G games advance in lockstep; each owns a fresh search tree per
 // move (agentdistributed.py:61-63) of at most N = max_sims + 1 nodes, because
-// one simulation creates at most one node (mctree.py:231-257).
+// one simulation creates at most one node (mctree.py:231-257) -- or, with
+// crl_reroot, the subtree of the move that was played (mctree.py:98-111) for as
+// long as kept nodes + the next move's simulations fit the same N.
 //
 //   games   game[G]               32-byte row of per-game scalars (ply, result, tree counters,
 //                                 pending-simulation state)
@@ -73,7 +75,8 @@ struct __attribute__((aligned(16))) GameRow {
     int8_t game_result;     // Game.get_result(); RESULT_NONE = running
     uint8_t root_dead;      // no live tree (finished game, or the tree was consumed by crl_advance)
     uint8_t leaf_kind;      // LeafKind of the pending simulation
-    uint8_t pad;
+    uint8_t root_kept;      // the root is a child that crl_reroot kept with its subtree (Tree(Node), mctree.py:98-111);
+                            // cleared by the next search begin
 };
 static_assert(sizeof(GameRow) == 32, "GameRow must be 32 bytes");
 

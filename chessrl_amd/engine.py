@@ -216,15 +216,22 @@ class LockstepEngine(object):
 
     def __init__(self, evaluator, n_games, max_sims, device=0, max_plies=4096,
                  numpy_promotion="auto", use_graph=True, bitplanes=None, legal_priors=None, raw_priors=None,
-                 steps_per_graph=None):
+                 steps_per_graph=None, max_nodes=None):
         numpy_promotion = resolve_numpy_promotion(numpy_promotion)
+        # node budget of every tree (default max_sims + 1: a fresh tree per move never needs more); a larger
+        # one leaves room for the subtree ``reroot`` keeps across a move boundary
+        if max_nodes is None:
+            max_nodes = max_sims + 1
+        if not max_sims + 1 <= max_nodes <= 32000:
+            raise ValueError("max_nodes must lie in [max_sims + 1, 32000]")
+        self.max_nodes = max_nodes
         if not torch.cuda.is_available():
             raise _lib.HipLibraryError("LockstepEngine needs an MI355X: no CPU fallback exists")
         self.numpy_promotion = numpy_promotion
         self.G, self.max_sims = n_games, max_sims
         self.dev = torch.device("cuda", device)
         torch.cuda.set_device(self.dev)
-        self.ctx = _lib.Context(n_games, max_sims, max_plies=max_plies, device=device,
+        self.ctx = _lib.Context(n_games, max_nodes - 1, max_plies=max_plies, device=device,
                                 numpy_legacy=(numpy_promotion == "legacy"))
         self.evaluator = evaluator
         G = n_games
@@ -458,18 +465,23 @@ class LockstepEngine(object):
         self.run_steps(1)
 
     # ---- SelfPlayTree surface -------------------------------------------------------------
-    def search_begin(self):
-        """Tree.__init__ for every slot + the root's policy (priors of its children)."""
+    def search_begin(self, keep_root=False):
+        """Tree.__init__ for every slot + the root's policy (priors of its children).  ``keep_root``: slots whose
+        root ``reroot`` kept go on with that tree (Tree(Node), mctree.py:98-111); the others start a fresh one."""
         self._bind_stream()
-        self.ctx.search_begin(self.planes_s2.data_ptr())
+        if keep_root:
+            self.ctx.search_begin_kept(self.planes_s2.data_ptr())
+        else:
+            self.ctx.search_begin(self.planes_s2.data_ptr())
         self._eval_into(self.planes_s2, self.pol_s2, self.val_s2)
         self.ctx.search_root_priors(self.pol_s2.data_ptr())
 
-    def search(self, n_sims):
-        """search_begin + n_sims lockstep simulations + the last backprop."""
+    def search(self, n_sims, keep_root=False):
+        """search_begin + n_sims lockstep simulations + the last backprop.  A kept tree that would not fit n_sims
+        more nodes was already turned into a fresh one by ``reroot(chosen, n_sims)``."""
         if n_sims > self.max_sims:
             raise ValueError("n_sims exceeds the max_sims this engine was created with")
-        self.search_begin()
+        self.search_begin(keep_root=keep_root)
         self.run_steps(n_sims)
         self.ctx.sim_backup(self.pri_s2.data_ptr(), self.val_s2.data_ptr())
 
@@ -478,6 +490,14 @@ class LockstepEngine(object):
 
     def advance(self, chosen):
         return self.ctx.advance(chosen)
+
+    def reroot(self, chosen, next_sims):
+        """``advance`` that keeps the chosen child's subtree in every slot where kept nodes + ``next_sims`` fit
+        ``max_nodes``; ``search(next_sims, keep_root=True)`` then continues on it."""
+        if next_sims > self.max_sims:
+            raise ValueError("next_sims exceeds the max_sims this engine was created with")
+        self._bind_stream()
+        return self.ctx.reroot(chosen, next_sims)
 
     # ---- Game surface (batched) --------------------------------------------------------------
     def reset(self, mask=None):

@@ -81,11 +81,19 @@ class SelfPlayRunner(object):
 
     def __init__(self, evaluator, n_parallel, sims, seed=0, noise=True, rank=0, world=1, device=0,
                  max_plies=4096, numpy_promotion="auto", use_graph=True, total_games=None,
-                 compact=True, round_size=None, steps_per_graph=None):
+                 compact=True, round_size=None, steps_per_graph=None, reuse_tree=False, tree_nodes=None):
         _warm_numpy()
+        # reuse_tree: the subtree below the move that was played is kept for the next search (Tree(Node),
+        # mctree.py:98-111) wherever kept nodes + sims fit tree_nodes; every move still runs `sims` NEW
+        # simulations for every game.  Off (the default): a fresh tree per move, today's calls exactly.
+        if tree_nodes is not None and not reuse_tree:
+            raise ValueError("tree_nodes is the node budget of reuse_tree=True")
+        if reuse_tree and tree_nodes is None:
+            tree_nodes = 2 * sims + 1
+        self.reuse_tree, self.tree_nodes = bool(reuse_tree), tree_nodes
         self.engine = LockstepEngine(evaluator, n_parallel, sims, device=device, max_plies=max_plies,
                                      numpy_promotion=numpy_promotion, use_graph=use_graph,
-                                     steps_per_graph=steps_per_graph)
+                                     steps_per_graph=steps_per_graph, max_nodes=tree_nodes)
         self.G, self.sims, self.seed, self.noise = n_parallel, sims, seed, noise
         self.rank, self.world = rank, world
         self.total_games = total_games           # global cap on started games (None = endless)
@@ -104,6 +112,10 @@ class SelfPlayRunner(object):
         self.sims_run = 0
         self.truncated_games = 0                 # records handed over at max_plies (result None)
         self.boundaries = 0                      # move boundaries crossed
+        self.reuse_kept = 0                      # reuse_tree: moves after which the tree was kept,
+        self.reuse_fell_back = 0                 # ... moves that went on with a fresh tree for lack of room,
+        self.reuse_kept_nodes = 0                # ... and the kept nodes summed
+        self._kept_children = np.zeros(n_parallel, dtype=np.int32)   # children the kept roots already have
         self._sims_in_move = None
         self._noise_rows = None                  # this move's Dirichlet draws, made while the GPU searches
         self._noise_states = {}                  # ... and every drawn stream's state before its draw
@@ -140,7 +152,7 @@ class SelfPlayRunner(object):
         """Fresh tree per slot (agentdistributed.py:61-63) + the root's priors."""
         if self.noise and self._root_legal is None:
             self._root_legal = self.engine.ctx.legal_counts()
-        self.engine.search_begin()
+        self.engine.search_begin(keep_root=self.reuse_tree)
         self._sims_in_move = 0
         self._noise_rows = None
 
@@ -183,7 +195,9 @@ class SelfPlayRunner(object):
         order and with the same arguments as at the boundary: the values are identical."""
         if not self.noise or self._noise_rows is not None or self._root_legal is None:
             return
-        n_final = np.where(self.game_id >= 0, np.minimum(self._root_legal[:self.G], self.sims), 0)
+        # (a kept root goes on from the children it has: kept_children + sims, 0 + sims for a fresh tree)
+        n_final = np.where(self.game_id >= 0,
+                           np.minimum(self._root_legal[:self.G], self._kept_children[:self.G] + self.sims), 0)
         mat = np.zeros((self.G, max(1, int(n_final.max()))), dtype=np.float64)
         # a move that is cut short after this point (end_move before `sims` simulations) ends with fewer
         # root children and must draw again FROM THE SAME STREAM POSITION: the states are kept until then
@@ -218,7 +232,16 @@ class SelfPlayRunner(object):
         full = self.active() & (chosen >= 0) & (np.asarray(plies) + 2 > self.max_plies)
         chosen[full] = -1
         live = int((chosen >= 0).sum())
-        res, next_legal = eng.ctx.advance_fetch(chosen)
+        if self.reuse_tree:
+            out = eng.ctx.reroot_fetch(chosen, self.sims)
+            res, next_legal = out["results"], out["legal_counts"]
+            kept = out["kept_nodes"] > 0
+            self._kept_children = np.where(kept, out["kept_children"], 0).astype(np.int32)
+            self.reuse_kept += int(kept.sum())
+            self.reuse_fell_back += int(((chosen >= 0) & (res == _lib.RESULT_NONE) & ~full & ~kept).sum())
+            self.reuse_kept_nodes += int(out["kept_nodes"].sum())
+        else:
+            res, next_legal = eng.ctx.advance_fetch(chosen)
         self.moves_played += live
         self.sims_run += live * self._sims_in_move
         self._sims_in_move = None
@@ -236,6 +259,7 @@ class SelfPlayRunner(object):
                 if self.round_size:
                     r = int(self.game_id[g]) // self.round_size
                     self._round_done[r] = self._round_done.get(r, 0) + 1
+            self._kept_children[done] = 0
             self._start(done)
             self._maybe_compact()
             next_legal = None                               # slots were reset / moved: count again
@@ -294,13 +318,25 @@ class SelfPlayRunner(object):
         free = [s for s in range(n_new) if self.game_id[s] < 0]
         for src in act[act >= n_new]:
             dst = free.pop()
-            self.engine.ctx.copy_game(int(dst), int(src))
+            if self.reuse_tree:                                  # the kept tree moves with its game
+                self.engine.ctx.copy_game_tree(int(dst), int(src))
+                self._kept_children[dst] = self._kept_children[src]
+            else:
+                self.engine.ctx.copy_game(int(dst), int(src))
             self.game_id[dst], self.color[dst], self.rngs[dst] = self.game_id[src], self.color[src], self.rngs[src]
             self.game_id[src] = -1
         self.engine.shrink(n_new)
         self.G = n_new
         self.game_id, self.color, self.rngs = self.game_id[:n_new], self.color[:n_new], self.rngs[:n_new]
+        self._kept_children = self._kept_children[:n_new]
         log.debug("compacted the lockstep batch to %d slots (%d games running)", n_new, len(act))
+
+    def log_reuse(self, who):
+        """What the node budget did (reuse_tree): moves that kept their tree, moves that fell back, kept nodes."""
+        if self.reuse_tree:
+            log.info("%s: tree reuse with %d nodes per tree: %d moves kept their tree (%.1f nodes on average), %d fell "
+                     "back to a fresh tree for lack of room", who, self.tree_nodes, self.reuse_kept,
+                     self.reuse_kept_nodes / max(self.reuse_kept, 1), self.reuse_fell_back)
 
     def play_move(self):
         """search_move + the two pushes for every running game (``sims`` lockstep steps)."""
@@ -676,6 +712,13 @@ def main(argv=None):
                              "of small dependent kernels get almost nothing of the GPU beside a full lockstep batch: "
                              "305 s for a round that takes 15 s alone).  C3 on one GPU needs ~0.2 to keep pace; 0 = "
                              "self-play first, the trainer takes what is left")
+    parser.add_argument("--reuse-tree", action="store_true",
+                        help="keep the subtree below the move that was played for the next search (the reference's "
+                             "Tree(Node), mctree.py:98-111) wherever it fits the node budget; every move still runs "
+                             "--sims new simulations.  Default: a fresh tree per move")
+    parser.add_argument("--tree-nodes", type=int, default=None,
+                        help="--reuse-tree: nodes per tree (default 2 * sims + 1; a tree is kept only if its kept "
+                             "nodes + sims fit, else that game searches a fresh tree for this move)")
     parser.add_argument("--max-plies", type=int, default=4096,
                         help="longest game record; a game still running there is handed over unfinished "
                              "(result None) and its slot refilled")
@@ -765,6 +808,7 @@ def main(argv=None):
     def after_round_rolling(rnd, recs):
         """Rolling rounds: gather, store, hand the round to rank 0's background trainer and play on."""
         newrecs = store(rnd, recs)
+        runner.log_reuse("up to round %d, rank %d" % (rnd, rank))
         if background is not None:
             background.submit(rnd, recs if dp else newrecs)        # dp: every rank trains on its own share
 
@@ -787,7 +831,8 @@ def main(argv=None):
         runner = SelfPlayRunner(model, parallel, args.sims, seed=args.seed, noise=not args.no_noise,
                                 rank=rank, world=world, device=local, max_plies=max_plies,
                                 total_games=args.games * args.rounds, round_size=args.games,
-                                numpy_promotion=args.numpy_promotion)
+                                numpy_promotion=args.numpy_promotion, reuse_tree=args.reuse_tree,
+                                tree_nodes=args.tree_nodes)
         t0 = time.perf_counter()
         poll = (lambda: background.ready() if background is not None else 0) if not args.no_train else None
         share = min(max(args.trainer_share, 0.0), 0.9)
@@ -803,6 +848,7 @@ def main(argv=None):
         dt = time.perf_counter() - t0
         log.info("rank %d: %d rolling rounds of %d games, %d sims in %.1fs (%.0f sims/s)", rank, args.rounds,
                  args.games, runner.sims_run, dt, runner.sims_run / max(dt, 1e-9))
+        runner.log_reuse("rank %d" % rank)
         if not args.no_train:
             if background is not None:
                 try:
@@ -818,12 +864,14 @@ def main(argv=None):
             runner = SelfPlayRunner(model, parallel, args.sims, seed=args.seed + rnd * args.games,
                                     noise=not args.no_noise, rank=rank, world=world, device=local,
                                     max_plies=max_plies, total_games=args.games,
-                                    numpy_promotion=args.numpy_promotion)
+                                    numpy_promotion=args.numpy_promotion, reuse_tree=args.reuse_tree,
+                                    tree_nodes=args.tree_nodes)
             t0 = time.perf_counter()
             recs = runner.run()
             dt = time.perf_counter() - t0
             log.info("round %d rank %d: %d games, %d sims in %.1fs (%.0f sims/s)", rnd, rank, len(recs),
                      runner.sims_run, dt, runner.sims_run / max(dt, 1e-9))
+            runner.log_reuse("round %d rank %d" % (rnd, rank))
             runner.close()
             after_round(rnd, recs)
     import hashlib

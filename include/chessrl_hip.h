@@ -70,7 +70,7 @@ typedef struct crl_ctx crl_ctx;
  * signature hands the GPU garbage pointers).  crl_source_hash(): sha256 over the sources (csrc/ + this
  * header + compiler flags) the library was built from, as chessrl_amd/_lib.py computes it; the string
  * is also findable in the file itself behind the marker "CRL_SRC_HASH=".  No reference counterpart. */
-#define CRL_ABI_VERSION 8
+#define CRL_ABI_VERSION 9
 int  crl_abi_version(void);
 const char *crl_source_hash(void);
 
@@ -205,6 +205,31 @@ int  crl_end_move_fetch(crl_ctx *ctx, const void *dev_policy_s2_f32, const void 
                         int32_t *plies /*G*/);
 int  crl_advance_fetch(crl_ctx *ctx, const int32_t *chosen /*G*/, uint16_t *bm, uint16_t *am,
                        int8_t *results /*G*/, int32_t *legal_counts /*G*/);
+/* Tree(Node) (mctree.py:98-111: "You can pass a Node object with a Game as state or directly the game"):
+ * crl_advance's two pushes, and the chosen child KEEPS its subtree and becomes the root of the next search
+ * (visits 1, mctree.py:111).  Decided per slot on the device: kept iff the child's state is S2 and the game
+ * goes on and kept nodes + next_sims <= max_sims + 1 (the node pool of crl_create; one simulation creates at
+ * most one node, so the pool cannot overflow during the next move).  Every other slot ends exactly as after
+ * crl_advance: no live tree, fresh tree at the next begin.  The kept tree is compacted in place (ids dense
+ * from 0, edge runs contiguous); value sums, visits and priors move as bit patterns.
+ * crl_search_begin_kept is crl_search_begin that leaves kept roots alone (only the pending-simulation
+ * state is reset; the following crl_search_root_priors skips them and counts no evaluation for them), so a
+ * batch mixes kept and fresh roots; plain crl_search_begin starts a fresh tree in every slot.
+ * crl_reroot_fetch is the fused boundary form, crl_advance_fetch + kept_nodes (0 = fresh tree next) and
+ * kept_children (children the kept root already has: the next search ends with
+ * min(legal moves, kept_children + simulations) of them). */
+int  crl_reroot(crl_ctx *ctx, const int32_t *chosen /*G*/, int next_sims, uint16_t *bm, uint16_t *am);
+int  crl_reroot_fetch(crl_ctx *ctx, const int32_t *chosen /*G*/, int next_sims, uint16_t *bm, uint16_t *am,
+                      int8_t *results /*G*/, int32_t *legal_counts /*G*/, int32_t *kept_nodes /*G*/,
+                      int32_t *kept_children /*G*/);
+int  crl_search_begin_kept(crl_ctx *ctx, void *dev_planes_f16);
+/* crl_copy_game that carries a live tree along (nodes, edges, root visits, the kept mark): the lockstep
+ * runner moves games between slots at a move boundary.  crl_copy_game itself leaves no tree in dst. */
+int  crl_copy_game_tree(crl_ctx *ctx, int dst, int src);
+/* Debug read-back of one slot's tree: 176-byte node records and 24-byte edge records as the kernels keep
+ * them (csrc/state.hpp), info = {nodes, edges, root visits, kept mark}; nodes / edges may be NULL. */
+int  crl_fetch_tree(crl_ctx *ctx, int slot, void *nodes, int node_cap, void *edges, int edge_cap,
+                    int32_t *info /*4*/);
 /* Device-side counters since crl_create: [0] simulations run, [1] nodes created,
  * [2] sum of selection depth (edges), [3] sum of legal moves over created nodes,
  * [4] tower evaluations consumed, [5] terminal leaves hit. */
