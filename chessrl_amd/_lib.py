@@ -38,6 +38,7 @@ N_LABELS = 1968
 PLANES = 128
 NO_MOVE = 0xFFFF
 RESULT_NONE = 2
+ROLLOUT_GAMES, ROLLOUT_LEAVES, ROLLOUT_SKIPPED = 0, 1, 0xFFFF
 FLAG_NUMPY_LEGACY = 1
 POLICY_FULL, POLICY_LEGAL, POLICY_LEGAL_RAW = 0, 1, 2
 TRUNK_BITPLANES = 1
@@ -59,6 +60,7 @@ SYMBOLS = [
     "crl_end_move_fetch", "crl_advance_fetch",
     "crl_reroot", "crl_reroot_fetch", "crl_search_begin_kept", "crl_copy_game_tree", "crl_fetch_tree",
     "crl_im2col3x3_f32", "crl_col2im3x3_f32", "crl_stamp", "crl_stamp_clock_khz",
+    "crl_rollout_games", "crl_rollout",
 ]
 
 
@@ -227,6 +229,8 @@ def lib():
     L.crl_im2col3x3_f32.argtypes = [vp, vp, vp, i32, i32]
     L.crl_col2im3x3_f32.argtypes = [vp, vp, vp, i32, i32]
     L.crl_stamp.argtypes = [vp, vp, u32, u32]
+    L.crl_rollout_games.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.crl_rollout.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     for name in SYMBOLS:
         if name not in ("crl_destroy", "crl_last_error", "crl_source_hash"):
@@ -496,6 +500,31 @@ class Context(object):
         self.sync()
         return (nodes[:info[0]], edges[:info[1]],
                 {"n_nodes": int(info[0]), "edge_top": int(info[1]), "root_visits": int(info[2]), "kept": int(info[3])})
+
+    # ---- random playouts (simulation.py:19-34, mctree.py:272-274) ------------------------------
+    def rollout_games(self, words, counts, chunks, max_moves, played=None):
+        """The in-slot form: every slot of the window plays its own game on with the 32-bit words of its row;
+        returns (played, used, chunk_results) -- plies of the run so far, words consumed by this call, and
+        Game.get_result() after every chunk of ``max_moves`` plies.  ``played``: what an earlier call of the
+        same run returned (a slot that ran out of words is resumed with the following words)."""
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        c = np.ascontiguousarray(counts, dtype=np.int32)
+        assert w.ndim == 2 and w.shape[0] == self.G and w.shape[1] >= 1 and c.shape == (self.G,)
+        played = np.zeros(self.G, np.int32) if played is None else np.array(played, dtype=np.int32)
+        assert played.shape == (self.G,)
+        used = np.zeros(self.G, np.int32)
+        res = np.zeros((self.G, max(int(chunks), 1)), np.int8)
+        self._ck(self._L.crl_rollout_games(self._h, _ptr(w), _ptr(c), w.shape[1], int(chunks), int(max_moves),
+                                           _ptr(played), _ptr(used), _ptr(res)), "crl_rollout_games")
+        return played, used, res
+
+    def rollout(self, root_source, repetitions, max_moves, dev_keys, dev_value, dev_results=None, dev_plies=None):
+        """The private form (enqueue only): ``repetitions`` independent playouts from every root; all arguments
+        but the three integers are device addresses (keys uint64 [G], value f32 [G], results int8 / plies
+        uint16 [G][repetitions], optional)."""
+        vp = ctypes.c_void_p
+        self._ck(self._L.crl_rollout(self._h, int(root_source), int(repetitions), int(max_moves), vp(dev_keys),
+                                     vp(dev_value), vp(dev_results), vp(dev_plies)), "crl_rollout")
 
     def counters(self):
         c = np.zeros(6, dtype=np.uint64)

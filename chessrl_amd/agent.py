@@ -74,15 +74,18 @@ class Agent(Player):
             best_move = tree.search_move(self, max_iters=max_iters, verbose=verbose, ai_move=ai_move)
         return best_move
 
-    def engine_for(self, max_iters):
-        """One single-game LockstepEngine per simulation budget, reused across moves; its node pool holds
+    def engine_for(self, max_iters, simulate=None):
+        """One single-game LockstepEngine per simulation budget (and leaf evaluator: ``simulate``, a
+        ``simulation.Rollouts`` or None for the value head), reused across moves; its node pool holds
         max(max_iters + 1, tree_nodes) nodes."""
         from .engine import LockstepEngine
-        if max_iters not in self._engines:
+        key = max_iters if simulate is None else (max_iters, simulate)
+        if key not in self._engines:
             nodes = max(max_iters + 1, self.tree_nodes or 0)
-            self._engines[max_iters] = LockstepEngine(
-                self.model, n_games=1, max_sims=nodes - 1, max_nodes=nodes, numpy_promotion=self.numpy_promotion)
-        return self._engines[max_iters]
+            self._engines[key] = LockstepEngine(
+                self.model, n_games=1, max_sims=nodes - 1, max_nodes=nodes, numpy_promotion=self.numpy_promotion,
+                simulate=simulate)
+        return self._engines[key]
 
     def get_copy(self):
         return self

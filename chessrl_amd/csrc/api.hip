@@ -2,6 +2,7 @@
 // C-ABI declared in include/chessrl_hip.h.  gfx950 only; no torch types cross this boundary.
 #include "../../include/chessrl_hip.h"
 #include "search.hpp"
+#include "rollout.hpp"
 #include "tower_x16.hpp"
 #include "tower_layer.hpp"
 #include "heads.hpp"
@@ -53,6 +54,11 @@ struct crl_ctx {
     u16 *t_u16a = nullptr;        // [G]
     u16 *t_u16b = nullptr;        // [G]
     Board *t_boards = nullptr;    // [G]
+    // random playouts (crl_rollout): results / plies of every playout where the caller keeps none
+    bool search_begun = false;
+    int8_t *roll_results = nullptr;
+    u16 *roll_plies = nullptr;
+    size_t roll_cap = 0;
 };
 
 // ---- netencoder.get_uci_labels (netencoder.py:94-134) as move ids ------------------------------
@@ -469,6 +475,7 @@ int crl_search_begin(crl_ctx *ctx, void *dev_planes_f16)
     if (!ctx || !dev_planes_f16) return fail(ctx, CRL_ERR_ARG, "crl_search_begin: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LAUNCH(ctx, k_search_begin, ctx->d, dev_planes_f16, 0);
+    ctx->search_begun = true;
     return CRL_OK;
 }
 
@@ -477,6 +484,7 @@ int crl_search_begin_kept(crl_ctx *ctx, void *dev_planes_f16)
     if (!ctx || !dev_planes_f16) return fail(ctx, CRL_ERR_ARG, "crl_search_begin_kept: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LAUNCH(ctx, k_search_begin, ctx->d, dev_planes_f16, 1);
+    ctx->search_begun = true;
     return CRL_OK;
 }
 
@@ -676,6 +684,68 @@ int crl_counters(crl_ctx *ctx, uint64_t *out6)
     for (int k = 0; k < CNT_N; k++) out6[k] = 0;
     for (int g = 0; g < ctx->d.G; g++)
         for (int k = 0; k < CNT_N; k++) out6[k] += h[(size_t)g * CNT_N + k];
+    return CRL_OK;
+}
+
+// ---- random playouts (csrc/rollout.hpp): RandomSimulation.run, simulation.py:19-34; mctree.py:272-274 ----------
+int crl_rollout_games(crl_ctx *ctx, const uint32_t *words, const int32_t *counts, int stride, int chunks,
+                      int max_moves, int32_t *played, int32_t *used, int8_t *chunk_results)
+{
+    if (!ctx || !words || !counts || !played || !used || !chunk_results || stride < 1 || chunks < 1 || max_moves < 0 ||
+        (long long)chunks * max_moves > 0x7FFFFFFFll)
+        return fail(ctx, CRL_ERR_ARG, "crl_rollout_games: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t G = ctx->W;
+    const size_t wb = G * (size_t)stride * sizeof(u32), cb = G * (size_t)chunks;
+    unsigned char *buf = nullptr;                 // setup-time call: a scratch buffer per call is fine
+    HIP_TRY(ctx, hipMalloc((void **)&buf, wb + cb));
+    u32 *dwords = (u32 *)buf;
+    int8_t *dres = (int8_t *)(buf + wb);
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemcpyAsync(dwords, words, wb, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->t_i32b, counts, G * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->t_i32c, played, G * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_rollout_games, dim3((unsigned)G), dim3(64), 0, s, ctx->d, (const u32 *)dwords,
+                           (const int32_t *)ctx->t_i32b, stride, chunks, max_moves, ctx->t_i32c, ctx->t_i32d, dres);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(played, ctx->t_i32c, G * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(used, ctx->t_i32d, G * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(chunk_results, dres, cb, hipMemcpyDeviceToHost, s);
+    hipError_t es = hipStreamSynchronize(s);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(ctx, CRL_ERR_HIP, hipGetErrorString(e));
+    if (es != hipSuccess) return fail(ctx, CRL_ERR_HIP, hipGetErrorString(es));
+    return check_dev_error(ctx);
+}
+
+int crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, const uint64_t *dev_keys,
+                void *dev_value_f32, int8_t *dev_results_i8, uint16_t *dev_plies_u16)
+{
+    if (!ctx || (root_source != CRL_ROLLOUT_GAMES && root_source != CRL_ROLLOUT_LEAVES) || repetitions < 1 ||
+        max_moves < 0 || max_moves > 65534 || !dev_keys || !dev_value_f32 ||
+        (long long)ctx->W * repetitions > 0x7FFFFFFFll)
+        return fail(ctx, CRL_ERR_ARG, "crl_rollout: bad argument");
+    if (root_source == CRL_ROLLOUT_LEAVES && !ctx->search_begun)
+        return fail(ctx, CRL_ERR_STATE, "crl_rollout: CRL_ROLLOUT_LEAVES needs a search (crl_search_begin first)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)ctx->W * repetitions;
+    if ((!dev_results_i8 || !dev_plies_u16) && n > ctx->roll_cap) {
+        int8_t *r = nullptr;
+        u16 *p = nullptr;
+        if (dalloc(ctx, &r, n, false) != hipSuccess || dalloc(ctx, &p, n, false) != hipSuccess)
+            return fail(ctx, CRL_ERR_HIP, "crl_rollout: hipMalloc of the result buffer failed");
+        ctx->roll_results = r; ctx->roll_plies = p; ctx->roll_cap = n;     // (the smaller ones go with the context)
+    }
+    int8_t *res = dev_results_i8 ? dev_results_i8 : ctx->roll_results;
+    u16 *pl = dev_plies_u16 ? dev_plies_u16 : ctx->roll_plies;
+    hipLaunchKernelGGL(k_rollout, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d, root_source, repetitions,
+                       max_moves, (const u64 *)dev_keys, res, pl);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_rollout_mean, dim3((unsigned)ctx->W), dim3(64), 0, ctx->stream, (const int8_t *)res,
+                       repetitions, (float *)dev_value_f32);
+    HIP_TRY(ctx, hipGetLastError());
     return CRL_OK;
 }
 

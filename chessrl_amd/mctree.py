@@ -115,9 +115,12 @@ class Tree(object):
 
 class SelfPlayTree(Tree):
 
-    def __init__(self, root, threads=6):
+    def __init__(self, root, threads=6, simulate=None):
+        """``simulate``: None -- leaves are valued by ``agent.predict_outcome`` (the value head) -- or a
+        ``chessrl_amd.simulation.Rollouts``: by random playouts, the alternative mctree.py:272-274 names."""
         super().__init__(root)
         self.num_threads = threads
+        self.simulate = simulate
 
     def search_move(self, agent, max_iters=200, verbose=False, noise=True, ai_move=False):
         # the tree searches its own snapshot of the caller's game (taken at construction, as the
@@ -127,7 +130,7 @@ class SelfPlayTree(Tree):
             eng = self._continue_on_device(max_iters)
             eng.search(max_iters, keep_root=True)
         else:
-            eng = agent.engine_for(max_iters)
+            eng = agent.engine_for(max_iters, self.simulate) if self.simulate is not None else agent.engine_for(max_iters)
             eng._tree_owner = None
             eng.ctx.copy_game_from(0, arena().ctx, game._slot)
             eng.search(max_iters)

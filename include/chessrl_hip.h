@@ -235,6 +235,39 @@ int  crl_fetch_tree(crl_ctx *ctx, int slot, void *nodes, int node_cap, void *edg
  * [4] tower evaluations consumed, [5] terminal leaves hit. */
 int  crl_counters(crl_ctx *ctx, uint64_t *out6);
 
+/* ---- random playouts: RandomSimulation.run (simulation.py:19-34), the leaf evaluator SelfPlayTree.simulate
+ * names beside predict_outcome (mctree.py:272-274).  csrc/rollout.hpp states the ply, the choice rule
+ * (CPython's random.choice, word for word) and the counter generator of the private form. ------------------- */
+#define CRL_ROLLOUT_GAMES  0   /* roots = the current position of every slot of the window                 */
+#define CRL_ROLLOUT_LEAVES 1   /* roots = S2 of the pending leaf of every slot of a running search           */
+#define CRL_ROLLOUT_SKIPPED 0xFFFFu   /* dev_plies_u16 of a slot that had no playout to run                */
+/* The in-slot form (simulation.py:19-34 as written; mctree.py:272-274 calls it on the leaf's own game): every
+ * slot of the window plays ITS game on by random moves -- history, move record, ply count and result change as
+ * by crl_push_moves -- taking 32-bit words from words[g*stride .. g*stride+counts[g]) (host; random.choice
+ * consumes one MT19937 output per word).  A slot stops when its game has a result, when chunks * max_moves plies
+ * have been played since the run began, or when its words run out: played[g] (host, in/out; 0 at the start of a
+ * run) counts the plies of the run, and a caller whose slot stopped for want of words calls again with the
+ * following words and the played[] it got back.  used[g] = words this call consumed; chunk_results[g*chunks + c] =
+ * Game.get_result() after chunk c of max_moves plies (CRL_RESULT_NONE where the game went on), final once the
+ * slot's run is over.  CRL_ERR_ARG: chunks < 1, max_moves < 0, stride < 1, a NULL array. */
+int  crl_rollout_games(crl_ctx *ctx, const uint32_t *words /*G x stride*/, const int32_t *counts /*G*/, int stride,
+                       int chunks, int max_moves, int32_t *played /*G*/, int32_t *used /*G*/,
+                       int8_t *chunk_results /*G x chunks*/);
+/* The private form (simulation.py:19-34 with independent repetitions, mctree.py:272-274): `repetitions` playouts
+ * of at most max_moves plies from every root, nothing of the game state written; a playout still running after
+ * max_moves plies counts 0.  Everything is device memory and the call only enqueues (it captures into a hipGraph):
+ * dev_keys uint64 [G] = the stream key of every slot (read at run time), dev_value_f32 [G] =
+ * (float)((double)sum of results / repetitions), dev_results_i8 / dev_plies_u16 [G][repetitions] = result and
+ * plies of every playout (either may be NULL: the library then keeps them in a buffer of its own, grown by a
+ * device allocation when a call needs more than any before -- pass both inside a graph capture).
+ * root_source CRL_ROLLOUT_LEAVES: a slot with no pending simulation, a terminal leaf or a leaf that ended on our
+ * move gets value 0 and CRL_ROLLOUT_SKIPPED plies (the backup does not read the value there); the simulation
+ * index of the generator is the number of simulations the current search has backed up.
+ * CRL_ERR_ARG: repetitions < 1, max_moves < 0 or > 65534, a NULL key or value array, an unknown root source;
+ * CRL_ERR_STATE: CRL_ROLLOUT_LEAVES on a context where no search was ever begun.  No state changes on an error. */
+int  crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, const uint64_t *dev_keys,
+                 void *dev_value_f32, int8_t *dev_results_i8, uint16_t *dev_plies_u16);
+
 /* ---- tower seam (model.py) -------------------------------------------------------------- */
 /* Residual trunk of ChessModel (model.py:33-37,111-122: stem conv + n_blocks residual blocks,
  * BatchNorm folded) for `filters` in {64, 128, 256} (BASELINE configs C2, C3/C4, C5; 256 is the
