@@ -40,6 +40,7 @@ NO_MOVE = 0xFFFF
 RESULT_NONE = 2
 ROLLOUT_GAMES, ROLLOUT_LEAVES, ROLLOUT_SKIPPED = 0, 1, 0xFFFF
 FLAG_NUMPY_LEGACY = 1
+WAVE_MAX_THREADS = 64     # include/chessrl_hip.h: CRL_WAVE_MAX_THREADS
 POLICY_FULL, POLICY_LEGAL, POLICY_LEGAL_RAW = 0, 1, 2
 TRUNK_BITPLANES = 1
 TRUNK_SPLIT = 2
@@ -61,6 +62,8 @@ SYMBOLS = [
     "crl_reroot", "crl_reroot_fetch", "crl_search_begin_kept", "crl_copy_game_tree", "crl_fetch_tree",
     "crl_im2col3x3_f32", "crl_col2im3x3_f32", "crl_stamp", "crl_stamp_clock_khz",
     "crl_rollout_games", "crl_rollout",
+    "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
+    "crl_wave_stats",
 ]
 
 
@@ -232,6 +235,13 @@ def lib():
     L.crl_rollout_games.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.crl_rollout.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
+    L.crl_wave_config.argtypes = [vp, i32]
+    L.crl_wave_begin.argtypes = [vp, i32]
+    L.crl_wave_select.argtypes = [vp, vp, vp, vp]
+    L.crl_wave_reply.argtypes = [vp, vp, vp]
+    L.crl_wave_backup.argtypes = [vp, vp, vp]
+    L.crl_wave_remaining.argtypes = [vp, vp]
+    L.crl_wave_stats.argtypes = [vp, vp, vp, vp]
     for name in SYMBOLS:
         if name not in ("crl_destroy", "crl_last_error", "crl_source_hash"):
             getattr(L, name).restype = ctypes.c_int
@@ -525,6 +535,37 @@ class Context(object):
         vp = ctypes.c_void_p
         self._ck(self._L.crl_rollout(self._h, int(root_source), int(repetitions), int(max_moves), vp(dev_keys),
                                      vp(dev_value), vp(dev_results), vp(dev_plies)), "crl_rollout")
+
+    # ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------
+    def wave_config(self, threads):
+        """Allocate the wave arrays for ``threads`` leaves per game and wave (1..64)."""
+        self._ck(self._L.crl_wave_config(self._h, int(threads)), "crl_wave_config")
+
+    def wave_begin(self, n_sims):
+        """After search_begin + search_root_priors: every live slot gets a budget of ``n_sims`` simulations."""
+        self._ck(self._L.crl_wave_begin(self._h, int(n_sims)), "crl_wave_begin")
+
+    def wave_select(self, dev_policy_s2, dev_value_s2, dev_planes_s1):
+        vp = ctypes.c_void_p
+        self._ck(self._L.crl_wave_select(self._h, vp(dev_policy_s2), vp(dev_value_s2), vp(dev_planes_s1)), "crl_wave_select")
+
+    def wave_reply(self, dev_policy_s1, dev_planes_s2):
+        self._ck(self._L.crl_wave_reply(self._h, ctypes.c_void_p(dev_policy_s1), ctypes.c_void_p(dev_planes_s2)), "crl_wave_reply")
+
+    def wave_backup(self, dev_policy_s2, dev_value_s2):
+        self._ck(self._L.crl_wave_backup(self._h, ctypes.c_void_p(dev_policy_s2), ctypes.c_void_p(dev_value_s2)), "crl_wave_backup")
+
+    def wave_remaining(self):
+        """The largest budget not yet selected over the window (synchronises); 0: only wave_backup is left."""
+        n = np.zeros(1, np.int32)
+        self._ck(self._L.crl_wave_remaining(self._h, _ptr(n)), "crl_wave_remaining")
+        return int(n[0])
+
+    def wave_stats(self):
+        """Per window slot since wave_begin: {waves, short_waves, leaves} (synchronises)."""
+        out = {k: np.zeros(self.G, np.int32) for k in ("waves", "short_waves", "leaves")}
+        self._ck(self._L.crl_wave_stats(self._h, _ptr(out["waves"]), _ptr(out["short_waves"]), _ptr(out["leaves"])), "crl_wave_stats")
+        return out
 
     def counters(self):
         c = np.zeros(6, dtype=np.uint64)

@@ -21,7 +21,7 @@ class Agent(Player):
     """``model``: a ``ChessModel`` (or any callable planes -> (policy, value) on the GPU)."""
 
     def __init__(self, color, weights=None, endpoint=None, num_threads=6, model=None,
-                 blocks=10, filters=256, numpy_promotion="auto", tree_nodes=None):
+                 blocks=10, filters=256, numpy_promotion="auto", tree_nodes=None, virtual_loss=False):
         super().__init__(color)
         if model is None:
             from .model import ChessModel
@@ -36,6 +36,9 @@ class Agent(Player):
         # from one of its root children (``SelfPlayTree(tree.root.children[k])``) needs room for the kept
         # subtree + max_iters more nodes
         self.tree_nodes = tree_nodes
+        # virtual_loss=True: ``best_move`` searches with ``num_threads`` workers per tree in the wave schedule
+        # (mctree.SelfPlayTree(virtual_loss=True)); off, ``num_threads`` is accepted and one worker searches
+        self.virtual_loss = bool(virtual_loss)
         self._engines = {}
 
     # ---- tower requests (agentdistributed.py:70-99) --------------------------------------
@@ -70,21 +73,26 @@ class Agent(Player):
             best_move = game.get_legal_moves()[int(np.argmax(policy))]
         elif game.get_result() is None:
             from . import mctree
-            tree = mctree.SelfPlayTree(game, threads=self.num_threads)
+            tree = mctree.SelfPlayTree(game, threads=self.num_threads, virtual_loss=self.virtual_loss)
             best_move = tree.search_move(self, max_iters=max_iters, verbose=verbose, ai_move=ai_move)
         return best_move
 
-    def engine_for(self, max_iters, simulate=None):
-        """One single-game LockstepEngine per simulation budget (and leaf evaluator: ``simulate``, a
+    def engine_for(self, max_iters, simulate=None, threads=1):
+        """One single-game LockstepEngine per (simulation budget, threads) (and leaf evaluator: ``simulate``, a
         ``simulation.Rollouts`` or None for the value head), reused across moves; its node pool holds
-        max(max_iters + 1, tree_nodes) nodes."""
+        max(max_iters + 1, tree_nodes) nodes -- max_iters + 1 with ``threads`` > 1, where every search starts from
+        a fresh tree."""
         from .engine import LockstepEngine
-        key = max_iters if simulate is None else (max_iters, simulate)
+        key = (max_iters, threads) if simulate is None else (max_iters, threads, simulate)
         if key not in self._engines:
-            nodes = max(max_iters + 1, self.tree_nodes or 0)
-            self._engines[key] = LockstepEngine(
-                self.model, n_games=1, max_sims=nodes - 1, max_nodes=nodes, numpy_promotion=self.numpy_promotion,
-                simulate=simulate)
+            if threads > 1:
+                self._engines[key] = LockstepEngine(self.model, n_games=1, max_sims=max_iters, simulate=simulate,
+                                                    numpy_promotion=self.numpy_promotion, threads=threads)
+            else:
+                nodes = max(max_iters + 1, self.tree_nodes or 0)
+                self._engines[key] = LockstepEngine(
+                    self.model, n_games=1, max_sims=nodes - 1, max_nodes=nodes, numpy_promotion=self.numpy_promotion,
+                    simulate=simulate)
         return self._engines[key]
 
     def get_copy(self):

@@ -3,6 +3,7 @@
 #include "../../include/chessrl_hip.h"
 #include "search.hpp"
 #include "rollout.hpp"
+#include "search_wave.hpp"
 #include "tower_x16.hpp"
 #include "tower_layer.hpp"
 #include "heads.hpp"
@@ -59,6 +60,9 @@ struct crl_ctx {
     int8_t *roll_results = nullptr;
     u16 *roll_plies = nullptr;
     size_t roll_cap = 0;
+    // waves (crl_wave_config): the arrays and their device descriptor
+    std::vector<void *> wave_allocs;
+    int wave_threads = 0;
 };
 
 // ---- netencoder.get_uci_labels (netencoder.py:94-134) as move ids ------------------------------
@@ -115,20 +119,26 @@ static int fail(crl_ctx *ctx, int code, const std::string &msg)
     } while (0)
 
 template <typename T>
-static hipError_t dalloc(crl_ctx *ctx, T **p, size_t count, bool zero = true)
+static hipError_t dalloc_into(std::vector<void *> &owner, T **p, size_t count, bool zero = true)
 {
     void *q = nullptr;
     size_t bytes = count * sizeof(T);
     if (bytes == 0) bytes = 16;
     hipError_t e = hipMalloc(&q, bytes);
     if (e != hipSuccess) return e;
-    ctx->allocs.push_back(q);
+    owner.push_back(q);
     if (zero) {
         e = hipMemset(q, 0, bytes);
         if (e != hipSuccess) return e;
     }
     *p = (T *)q;
     return hipSuccess;
+}
+
+template <typename T>
+static hipError_t dalloc(crl_ctx *ctx, T **p, size_t count, bool zero = true)
+{
+    return dalloc_into(ctx->allocs, p, count, zero);
 }
 
 static const char *dev_err_name(int c)
@@ -237,6 +247,7 @@ void crl_destroy(crl_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     for (void *p : ctx->allocs) (void)hipFree(p);
+    for (void *p : ctx->wave_allocs) (void)hipFree(p);
     delete ctx;
 }
 
@@ -747,6 +758,135 @@ int crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, c
                        repetitions, (float *)dev_value_f32);
     HIP_TRY(ctx, hipGetLastError());
     return CRL_OK;
+}
+
+// ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------------------------
+int crl_wave_config(crl_ctx *ctx, int threads)
+{
+    if (!ctx || threads < 1 || threads > CRL_WAVE_MAX_THREADS) return fail(ctx, CRL_ERR_ARG, "crl_wave_config: threads must lie in [1, 64]");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    {   // pending simulations are read from the DEVICE (entry points captured into a hipGraph run on the host only once)
+        std::vector<GameRow> rows(ctx->d.G);
+        HIP_TRY(ctx, hipMemcpy(rows.data(), ctx->d.game, rows.size() * sizeof(GameRow), hipMemcpyDeviceToHost));
+        bool pending = false;
+        for (const GameRow &g : rows) pending = pending || g.leaf_kind != LEAF_NONE;
+        if (ctx->d.wave && !pending) {
+            WaveArrs w{};
+            std::vector<int32_t> nl(ctx->d.G);
+            HIP_TRY(ctx, hipMemcpy(&w, ctx->d.wave, sizeof w, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(nl.data(), w.n_leaves, nl.size() * 4, hipMemcpyDeviceToHost));
+            for (int32_t x : nl) pending = pending || x > 0;
+        }
+        if (pending) return fail(ctx, CRL_ERR_STATE, "crl_wave_config: a simulation is pending (back it up first)");
+    }
+    for (void *p : ctx->wave_allocs) (void)hipFree(p);
+    ctx->wave_allocs.clear();
+    ctx->d.wave = nullptr;
+    ctx->wave_threads = 0;
+    const Dev &d = ctx->d;
+    const size_t G = d.G, T = threads, GT = G * T, plane = T * G * d.N;
+    WaveArrs w{};
+    w.T = threads;
+    bool ok = true;
+#define A(ptr, count) ok = ok && (dalloc_into(ctx->wave_allocs, &(ptr), (count)) == hipSuccess)
+    A(w.kind, GT); A(w.leaf, GT); A(w.plen, GT); A(w.path_edge, plane); A(w.path_node, plane);
+    A(w.s1_moves, GT * MAX_MOVES); A(w.s1_n, GT); A(w.budget, G); A(w.n_leaves, G); A(w.stats, G * WST_N);
+    WaveArrs *dw = nullptr;
+    A(dw, 1);
+#undef A
+    if (ok) ok = hipMemcpy(dw, &w, sizeof w, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        for (void *p : ctx->wave_allocs) (void)hipFree(p);
+        ctx->wave_allocs.clear();
+        return fail(ctx, CRL_ERR_HIP, "crl_wave_config: hipMalloc failed (the path planes need about " +
+                                          std::to_string((plane * 6) >> 20) + " MiB)");
+    }
+    ctx->d.wave = dw;
+    ctx->wave_threads = threads;
+    return CRL_OK;
+}
+
+static int wave_ready(crl_ctx *ctx, const char *what)
+{
+    if (!ctx) return CRL_ERR_ARG;
+    if (!ctx->d.wave) return fail(ctx, CRL_ERR_STATE, std::string(what) + ": crl_wave_config first");
+    if (ctx->d.policy_fmt != CRL_POLICY_FULL)
+        return fail(ctx, CRL_ERR_STATE, std::string(what) + ": waves read full policy vectors (CRL_POLICY_FULL) only");
+    return CRL_OK;
+}
+
+int crl_wave_begin(crl_ctx *ctx, int n_sims)
+{
+    int rc = wave_ready(ctx, "crl_wave_begin");
+    if (rc != CRL_OK) return rc;
+    if (n_sims < 1 || n_sims > ctx->d.N - 1) return fail(ctx, CRL_ERR_ARG, "crl_wave_begin: n_sims must lie in [1, max_sims]");
+    if (!ctx->search_begun) return fail(ctx, CRL_ERR_STATE, "crl_wave_begin: needs crl_search_begin first");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LAUNCH(ctx, k_wave_begin, ctx->d, n_sims);
+    return CRL_OK;
+}
+
+int crl_wave_select(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32, void *dev_planes_s1)
+{
+    int rc = wave_ready(ctx, "crl_wave_select");
+    if (rc != CRL_OK) return rc;
+    if (!dev_policy_s2_f32 || !dev_value_s2_f32 || !dev_planes_s1) return fail(ctx, CRL_ERR_ARG, "crl_wave_select: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LAUNCH(ctx, k_wave_select, ctx->d, (const float *)dev_policy_s2_f32, (const float *)dev_value_s2_f32, dev_planes_s1);
+    return CRL_OK;
+}
+
+int crl_wave_reply(crl_ctx *ctx, const void *dev_policy_s1_f32, void *dev_planes_s2)
+{
+    int rc = wave_ready(ctx, "crl_wave_reply");
+    if (rc != CRL_OK) return rc;
+    if (!dev_policy_s1_f32 || !dev_planes_s2) return fail(ctx, CRL_ERR_ARG, "crl_wave_reply: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LAUNCH(ctx, k_wave_reply, ctx->d, (const float *)dev_policy_s1_f32, dev_planes_s2);
+    return CRL_OK;
+}
+
+int crl_wave_backup(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32)
+{
+    int rc = wave_ready(ctx, "crl_wave_backup");
+    if (rc != CRL_OK) return rc;
+    if (!dev_policy_s2_f32 || !dev_value_s2_f32) return fail(ctx, CRL_ERR_ARG, "crl_wave_backup: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    LAUNCH(ctx, k_wave_backup, ctx->d, (const float *)dev_policy_s2_f32, (const float *)dev_value_s2_f32);
+    return CRL_OK;
+}
+
+int crl_wave_remaining(crl_ctx *ctx, int32_t *max_remaining)
+{
+    int rc = wave_ready(ctx, "crl_wave_remaining");
+    if (rc != CRL_OK) return rc;
+    if (!max_remaining) return fail(ctx, CRL_ERR_ARG, "crl_wave_remaining: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_wave_remaining, dim3(1), dim3(64), 0, ctx->stream, ctx->d, ctx->W, ctx->t_i32b);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(max_remaining, ctx->t_i32b, 4, hipMemcpyDeviceToHost, ctx->stream));
+    return check_dev_error(ctx);
+}
+
+int crl_wave_stats(crl_ctx *ctx, int32_t *waves, int32_t *short_waves, int32_t *leaves)
+{
+    int rc = wave_ready(ctx, "crl_wave_stats");
+    if (rc != CRL_OK) return rc;
+    if (!waves || !short_waves || !leaves) return fail(ctx, CRL_ERR_ARG, "crl_wave_stats: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int G = ctx->W;
+    hipLaunchKernelGGL(k_wave_stats, dim3(1), dim3(64), 0, ctx->stream, ctx->d, G, ctx->t_i32a);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<int32_t> h((size_t)G * WST_N);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->t_i32a, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    rc = check_dev_error(ctx);
+    for (int g = 0; g < G; g++) {
+        waves[g] = h[(size_t)g * WST_N + WST_WAVES];
+        short_waves[g] = h[(size_t)g * WST_N + WST_SHORT];
+        leaves[g] = h[(size_t)g * WST_N + WST_LEAVES];
+    }
+    return rc;
 }
 
 // ---- tower seam (model.py) -------------------------------------------------------------------

@@ -27,6 +27,8 @@
 //                                 backup's visits/value update touches one sector per level,
 //                                 and the winner's child id comes out of the same record.
 //   step    path_*[G][N]          the selection path of the pending simulation
+//   waves   WaveArrs              only after crl_wave_config (threads > 1, csrc/search_wave.hpp): per (game, thread)
+//                                 the pending leaf, its path plane [T][G][N] and S1 move list; per game the budget
 #pragma once
 #include "board.hpp"
 
@@ -95,6 +97,21 @@ static_assert(sizeof(Edge) == 24, "Edge must be 24 bytes");
 
 enum Counter { CNT_SIMS = 0, CNT_NODES, CNT_DEPTH, CNT_BRANCH, CNT_EVALS, CNT_TERMINAL, CNT_N };
 
+// The arrays of the wave mode (csrc/search_wave.hpp), allocated by crl_wave_config.  Index gt = g * T + t.
+struct WaveArrs {
+    int T;                             // threads: leaves per game and wave at most
+    uint8_t *kind;                     // [G*T] LeafKind of leaf t of the pending wave
+    u16 *leaf;                         // [G*T] its node
+    int32_t *plen;                     // [G*T] its path length
+    int32_t *path_edge;                // [T][G][N] thread t's plane is laid out like Dev::path_edge
+    u16 *path_node;                    // [T][G][N]
+    u16 *s1_moves;                     // [G*T][MAX_MOVES] legal moves of S1 of a leaf that waits for the reply
+    int32_t *s1_n;                     // [G*T]
+    int32_t *budget;                   // [G] simulations of the current search not yet selected
+    int32_t *n_leaves;                 // [G] leaves of the pending wave
+    int32_t *stats;                    // [G][3] waves, short waves, leaves since crl_wave_begin
+};
+
 struct Dev {
     int G, N, ECAP, MAXPLY;
     int g0;                            // first slot of the active window (I/O rows are window-relative)
@@ -126,6 +143,7 @@ struct Dev {
     const u16 *lut;                    // [5][4096] move -> label index (0xFFFF = none)
     unsigned long long *counters;      // [G][CNT_N]
     int32_t *err;                      // sticky device error code
+    const WaveArrs *wave;              // device copy of the wave arrays; null until crl_wave_config
 };
 
 enum DevErr { DERR_NONE = 0, DERR_NODE_POOL = 1, DERR_EDGE_POOL = 2, DERR_PLY_POOL = 3,

@@ -18,8 +18,16 @@ expands them on chip, or fp16 NHWC planes for any other evaluator -- and the
 search kernels read the tower's fp32 outputs in place
 (``torch.Tensor.data_ptr()`` across the C-ABI).
 
-Sequential ``threads=1`` semantics of the reference (the only deterministic
-mode): per game, simulations are strictly ordered.
+Sequential ``threads=1`` semantics of the reference by default: per game,
+simulations are strictly ordered.
+
+``LockstepEngine(..., threads=T)`` with T > 1 runs the reference's ``threads``
+workers per tree in the WAVE schedule (csrc/search_wave.hpp) -- the deterministic
+one among the legal schedules of its virtual-loss thread pool (mctree.py:12,
+173-176,226-227,289-293): a step selects up to T leaves per game, the two tower
+calls evaluate G*T rows (row = game * T + thread), and the leaves are backed up
+in thread order.  Waves may end short, so the number of steps of a search is
+data-dependent, between ceil(n/T) and n; a game whose budget is spent idles.
 """
 import numpy as np
 import torch
@@ -218,10 +226,29 @@ class LockstepEngine(object):
 
     def __init__(self, evaluator, n_games, max_sims, device=0, max_plies=4096,
                  numpy_promotion="auto", use_graph=True, bitplanes=None, legal_priors=None, raw_priors=None,
-                 steps_per_graph=None, max_nodes=None, simulate=None):
+                 steps_per_graph=None, max_nodes=None, simulate=None, threads=1):
         numpy_promotion = resolve_numpy_promotion(numpy_promotion)
         if simulate is not None and not isinstance(simulate, Rollouts):
             raise TypeError("simulate must be None or a chessrl_amd.simulation.Rollouts")
+        # threads > 1: virtual-loss waves.  What the wave kernels do not cover is refused by name, never ignored.
+        threads = int(threads)
+        if not 1 <= threads <= _lib.WAVE_MAX_THREADS:
+            raise ValueError("threads must lie in [1, %d]" % _lib.WAVE_MAX_THREADS)
+        if threads > 1:
+            if simulate is not None:
+                raise ValueError("threads > 1 cannot be combined with rollouts (simulate=Rollouts): the playout kernel "
+                                 "values one pending leaf per game")
+            if legal_priors:
+                raise ValueError("threads > 1 cannot be combined with legal_priors=True: the wave kernels read full "
+                                 "policy vectors")
+            if raw_priors:
+                raise ValueError("threads > 1 cannot be combined with raw_priors=True: the wave kernels read full "
+                                 "policy vectors")
+            if max_nodes is not None and max_nodes != max_sims + 1:
+                raise ValueError("threads > 1 cannot be combined with max_nodes (tree reuse): a wave search starts from "
+                                 "a fresh tree")
+            legal_priors, raw_priors = False, False
+        self.threads = threads
         # node budget of every tree (default max_sims + 1: a fresh tree per move never needs more); a larger
         # one leaves room for the subtree ``reroot`` keeps across a move boundary
         if max_nodes is None:
@@ -238,7 +265,9 @@ class LockstepEngine(object):
         self.ctx = _lib.Context(n_games, max_nodes - 1, max_plies=max_plies, device=device,
                                 numpy_legacy=(numpy_promotion == "legacy"))
         self.evaluator = evaluator
-        G = n_games
+        if threads > 1:
+            self.ctx.wave_config(threads)
+        G = n_games * threads                    # evaluator rows: one per game, or game-major one per (game, thread)
         # An evaluator that runs the fused HIP trunk takes the encoder's compact form -- 128 plane
         # bitboards (1 KiB) per position -- and expands it on chip: the 16-KiB fp16 planes are then
         # never written to HBM.  Any other evaluator gets the fp16 NHWC planes.
@@ -321,12 +350,12 @@ class LockstepEngine(object):
         """Keep only slots [0, n) in the lockstep batch (finite runs: the batch thins out as games
         end; the caller compacts the running games into the first slots with ``ctx.copy_game``).
         Every later launch, tower batch and the re-captured hipGraph cover n games."""
-        if not 0 < n <= self._full[0].shape[0] or n % 4:
+        if not 0 < n <= self._full[0].shape[0] // self.threads or n % 4:
             raise ValueError("shrink: n must be a multiple of 4 within the engine's capacity")
         self.ctx.set_window(0, n)
         self.G = n
         (self.planes_s1, self.planes_s2, self.pol_s1, self.pol_s2, self.val_s2,
-         self.pri_s1, self.pri_s2) = (t[:n] for t in self._full)
+         self.pri_s1, self.pri_s2) = (t[:n * self.threads] for t in self._full)
         if self.legal_priors:
             self._pick_policy_format()
         self._graph = None
@@ -369,6 +398,13 @@ class LockstepEngine(object):
         self.ctx.rollout(_lib.ROLLOUT_LEAVES, sim.repetitions, sim.max_moves, self.stream_keys.data_ptr(),
                          self.val_s2.data_ptr(), self.roll_results.data_ptr(), self.roll_plies.data_ptr())
 
+    # threads > 1: the two kernel phases of a wave step (the tower phases are the same calls on G*T rows)
+    def phase_wave_select(self):
+        self.ctx.wave_select(self.pol_s2.data_ptr(), self.val_s2.data_ptr(), self.planes_s1.data_ptr())
+
+    def phase_wave_reply(self):
+        self.ctx.wave_reply(self.pol_s1.data_ptr(), self.planes_s2.data_ptr())
+
     def set_stream_keys(self, keys):
         """The 64-bit stream key of every slot (default: seed * 2^32 + slot index), copied into the tensor the
         captured step reads: int64 / uint64 tensor or array of n_games entries."""
@@ -382,6 +418,12 @@ class LockstepEngine(object):
 
     def _step_body(self):
         st = self.stamps
+        if self.threads > 1:
+            self.phase_wave_select()
+            self.phase_tower_s1()
+            self.phase_wave_reply()
+            self.phase_tower_s2()
+            return
         if st is None:
             self.phase_select_expand()
             self.phase_tower_s1()
@@ -409,6 +451,8 @@ class LockstepEngine(object):
         on first use, cached beside the plain graphs: switching between the two costs nothing, so a stamped leg can
         follow a timed window without a capture in between).  Stamped graphs write into the ring they were captured
         with: another ring drops them."""
+        if ring is not None and self.threads > 1:
+            raise ValueError("threads > 1 cannot be combined with set_stamps: the stamped step is the one-leaf step")
         if ring is not None and ring is not self._stamped_ring:
             self._graphs = {k: g for k, g in self._graphs.items() if not k[1]}
             self._stamped_ring = ring
@@ -431,7 +475,7 @@ class LockstepEngine(object):
         # warm the evaluator (library handles, autotuning, buffers it keeps between calls) outside of capture
         prepare = getattr(self.evaluator, "prepare", None)
         if prepare is not None:
-            prepare(self.G)
+            prepare(self.G * self.threads)
         if not self._graphs:
             side = torch.cuda.Stream(self.dev)
             side.wait_stream(torch.cuda.current_stream(self.dev))
@@ -482,7 +526,8 @@ class LockstepEngine(object):
             self._graph_of(1)
 
     def run_steps(self, n):
-        """``n`` simulations for every game (enqueue only, no host sync)."""
+        """``n`` steps for every game (enqueue only, no host sync): a step is one simulation per game, or with
+        ``threads`` > 1 one wave of up to ``threads`` simulations per game."""
         if not self.use_graph:
             for _ in range(n):
                 self._step_body()
@@ -496,7 +541,7 @@ class LockstepEngine(object):
             n -= 1
 
     def step(self):
-        """One simulation for every game (enqueue only, no host sync)."""
+        """One step for every game (enqueue only, no host sync): one simulation, or with ``threads`` > 1 one wave."""
         self.run_steps(1)
 
     # ---- SelfPlayTree surface -------------------------------------------------------------
@@ -504,11 +549,16 @@ class LockstepEngine(object):
         """Tree.__init__ for every slot + the root's policy (priors of its children).  ``keep_root``: slots whose
         root ``reroot`` kept go on with that tree (Tree(Node), mctree.py:98-111); the others start a fresh one."""
         self._bind_stream()
+        if keep_root and self.threads > 1:
+            raise ValueError("threads > 1 cannot be combined with keep_root=True: a wave search starts from a fresh tree")
         if keep_root:
             self.ctx.search_begin_kept(self.planes_s2.data_ptr())
         else:
             self.ctx.search_begin(self.planes_s2.data_ptr())
-        self._eval_into(self.planes_s2, self.pol_s2, self.val_s2)
+        if self.threads > 1:                     # the roots are the first G rows of the G*T-row buffers
+            self._eval_into(self.planes_s2[:self.G], self.pol_s2[:self.G], self.val_s2[:self.G])
+        else:
+            self._eval_into(self.planes_s2, self.pol_s2, self.val_s2)
         self.ctx.search_root_priors(self.pol_s2.data_ptr())
 
     def search(self, n_sims, keep_root=False):
@@ -517,8 +567,37 @@ class LockstepEngine(object):
         if n_sims > self.max_sims:
             raise ValueError("n_sims exceeds the max_sims this engine was created with")
         self.search_begin(keep_root=keep_root)
+        if self.threads > 1:
+            self.run_waves(n_sims)
+            return
         self.run_steps(n_sims)
         self.ctx.sim_backup(self.pri_s2.data_ptr(), self.val_s2.data_ptr())
+
+    def run_waves(self, n_sims, while_enqueued=None):
+        """After ``search_begin``: exactly ``n_sims`` simulations for every live game in waves of up to ``threads``,
+        the last backprop included.  ceil(n/T) steps are enqueued blind; a wave that ended short leaves budget
+        behind, so the largest remaining budget of the batch is then polled (one int) and at least the steps it
+        still needs are enqueued, until it is 0.  ``while_enqueued``: called once the blind steps are enqueued and
+        before the first poll synchronises -- host work that overlaps the GPU (the runner's noise draws).
+        Returns the number of steps (also kept in ``wave_steps``)."""
+        if n_sims > self.max_sims:
+            raise ValueError("n_sims exceeds the max_sims this engine was created with")
+        T = self.threads
+        self.ctx.wave_begin(n_sims)
+        steps = -(-n_sims // T)
+        self.run_steps(steps)
+        if while_enqueued is not None:
+            while_enqueued()
+        while True:
+            left = self.ctx.wave_remaining()
+            if left == 0:
+                break
+            more = -(-left // T)
+            self.run_steps(more)
+            steps += more
+        self.ctx.wave_backup(self.pol_s2.data_ptr(), self.val_s2.data_ptr())
+        self.wave_steps = steps
+        return steps
 
     def root_children(self):
         return self.ctx.root_children()
@@ -529,6 +608,8 @@ class LockstepEngine(object):
     def reroot(self, chosen, next_sims):
         """``advance`` that keeps the chosen child's subtree in every slot where kept nodes + ``next_sims`` fit
         ``max_nodes``; ``search(next_sims, keep_root=True)`` then continues on it."""
+        if self.threads > 1:
+            raise ValueError("threads > 1 cannot be combined with reroot: a wave search starts from a fresh tree")
         if next_sims > self.max_sims:
             raise ValueError("next_sims exceeds the max_sims this engine was created with")
         self._bind_stream()
@@ -543,7 +624,10 @@ class LockstepEngine(object):
         """agent.best_move(game, real_game=True) for the masked slots (+ gam.move(...))."""
         self._bind_stream()
         self.ctx.encode(self.planes_s1.data_ptr())
-        self._eval_into(self.planes_s1, self.pol_s1, None)
+        if self.threads > 1:
+            self._eval_into(self.planes_s1[:self.G], self.pol_s1[:self.G], None)
+        else:
+            self._eval_into(self.planes_s1, self.pol_s1, None)
         return self.ctx.greedy_moves(self.pol_s1.data_ptr(), mask=mask, push=push)
 
     def load_games(self, games):

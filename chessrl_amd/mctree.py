@@ -22,8 +22,12 @@ search there: a ``Node`` can be continued only while its tree is the last one th
 size otherwise).  As in the reference, the kept children keep their visits while the root restarts
 at 1, so ``compute_policy`` of a continued tree sums to more than 1.
 
-``threads`` is accepted for signature compatibility; simulations run with the
-reference's sequential (threads=1) semantics, its only deterministic mode.
+``threads`` is accepted for signature compatibility and, by default, ignored: simulations run with the
+reference's sequential (threads=1) semantics.  ``SelfPlayTree(game, threads=T, virtual_loss=True)`` honours it:
+the search runs T workers per tree in the wave schedule (csrc/search_wave.hpp) -- the deterministic one among the
+legal schedules of the reference's virtual-loss thread pool (mctree.py:12,173-176,226-227,289-293).  It is opt-in
+because ``Agent`` passes ``threads=6`` today and honouring it would change what every caller gets.  A wave search
+starts from a fresh tree: continuing a ``Node`` with ``virtual_loss=True`` raises.
 """
 import numpy as np
 
@@ -97,6 +101,9 @@ class Tree(object):
         if eng is None or getattr(eng, "_tree_owner", None) is not src:
             raise RuntimeError("the device tree of this Node is gone: its engine has searched another tree since "
                                "(a Node can be continued only while its tree is the last one searched there)")
+        if getattr(eng, "threads", 1) > 1:
+            raise ValueError("this Node comes from a search with virtual_loss=True and threads > 1: a wave engine starts "
+                             "every search from a fresh tree and cannot continue a Node (construct the tree from the Game)")
         if node.reply is None:
             raise ValueError("search_move on a finished game (attempt to get argmax of an empty sequence)")
         nodes, edges, info = eng.ctx.fetch_tree(0)
@@ -115,12 +122,22 @@ class Tree(object):
 
 class SelfPlayTree(Tree):
 
-    def __init__(self, root, threads=6, simulate=None):
+    def __init__(self, root, threads=6, simulate=None, virtual_loss=False):
         """``simulate``: None -- leaves are valued by ``agent.predict_outcome`` (the value head) -- or a
-        ``chessrl_amd.simulation.Rollouts``: by random playouts, the alternative mctree.py:272-274 names."""
+        ``chessrl_amd.simulation.Rollouts``: by random playouts, the alternative mctree.py:272-274 names.
+        ``virtual_loss``: the search uses ``threads`` workers per tree (the wave schedule)."""
+        if virtual_loss:
+            if not 1 <= int(threads) <= _lib.WAVE_MAX_THREADS:
+                raise ValueError("threads must lie in [1, %d]" % _lib.WAVE_MAX_THREADS)
+            if simulate is not None and threads > 1:
+                raise ValueError("virtual_loss=True with threads > 1 cannot be combined with rollouts (simulate=Rollouts)")
+            if isinstance(root, Node) and root._tree is not None and threads > 1:
+                raise ValueError("virtual_loss=True with threads > 1 cannot continue a Node: a wave search starts from "
+                                 "a fresh tree (construct the tree from the Game)")
         super().__init__(root)
         self.num_threads = threads
         self.simulate = simulate
+        self.virtual_loss = bool(virtual_loss)
 
     def search_move(self, agent, max_iters=200, verbose=False, noise=True, ai_move=False):
         # the tree searches its own snapshot of the caller's game (taken at construction, as the
@@ -130,7 +147,10 @@ class SelfPlayTree(Tree):
             eng = self._continue_on_device(max_iters)
             eng.search(max_iters, keep_root=True)
         else:
-            eng = agent.engine_for(max_iters, self.simulate) if self.simulate is not None else agent.engine_for(max_iters)
+            if self.virtual_loss and self.num_threads > 1:
+                eng = agent.engine_for(max_iters, threads=int(self.num_threads))
+            else:
+                eng = agent.engine_for(max_iters, self.simulate) if self.simulate is not None else agent.engine_for(max_iters)
             eng._tree_owner = None
             eng.ctx.copy_game_from(0, arena().ctx, game._slot)
             eng.search(max_iters)

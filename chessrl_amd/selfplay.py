@@ -81,8 +81,17 @@ class SelfPlayRunner(object):
 
     def __init__(self, evaluator, n_parallel, sims, seed=0, noise=True, rank=0, world=1, device=0,
                  max_plies=4096, numpy_promotion="auto", use_graph=True, total_games=None,
-                 compact=True, round_size=None, steps_per_graph=None, reuse_tree=False, tree_nodes=None):
+                 compact=True, round_size=None, steps_per_graph=None, reuse_tree=False, tree_nodes=None, threads=1):
         _warm_numpy()
+        # threads > 1: every move is searched by `threads` workers per tree in the wave schedule (virtual loss,
+        # csrc/search_wave.hpp): a step evaluates up to `threads` leaves per game, a move takes between
+        # ceil(sims / threads) and sims steps.  Every search starts from a fresh tree.
+        threads = int(threads)
+        if not 1 <= threads <= _lib.WAVE_MAX_THREADS:
+            raise ValueError("threads must lie in [1, %d]" % _lib.WAVE_MAX_THREADS)
+        if threads > 1 and reuse_tree:
+            raise ValueError("threads > 1 cannot be combined with reuse_tree=True: a wave search starts from a fresh tree")
+        self.threads = threads
         # reuse_tree: the subtree below the move that was played is kept for the next search (Tree(Node),
         # mctree.py:98-111) wherever kept nodes + sims fit tree_nodes; every move still runs `sims` NEW
         # simulations for every game.  Off (the default): a fresh tree per move, today's calls exactly.
@@ -93,7 +102,7 @@ class SelfPlayRunner(object):
         self.reuse_tree, self.tree_nodes = bool(reuse_tree), tree_nodes
         self.engine = LockstepEngine(evaluator, n_parallel, sims, device=device, max_plies=max_plies,
                                      numpy_promotion=numpy_promotion, use_graph=use_graph,
-                                     steps_per_graph=steps_per_graph, max_nodes=tree_nodes)
+                                     steps_per_graph=steps_per_graph, max_nodes=tree_nodes, threads=threads)
         self.G, self.sims, self.seed, self.noise = n_parallel, sims, seed, noise
         self.rank, self.world = rank, world
         self.total_games = total_games           # global cap on started games (None = endless)
@@ -167,6 +176,9 @@ class SelfPlayRunner(object):
         ``step()``: the steps in between are handed to the engine in one piece (``run_steps``: several steps per
         hipGraph launch), cut where the runner has something to do -- the noise draw half-way through a move,
         the boundary."""
+        if self.threads > 1:
+            raise ValueError("threads > 1 cannot be stepped one simulation at a time: a wave step runs up to `threads` "
+                             "simulations per game (use play_move / run / run_rolling)")
         crossed = 0
         half = max(1, self.sims // 2)
         while n > 0:
@@ -341,7 +353,12 @@ class SelfPlayRunner(object):
     def play_move(self):
         """search_move + the two pushes for every running game (``sims`` lockstep steps)."""
         self.begin_move()
-        self.engine.run_steps(self.sims)
+        if self.threads > 1:
+            # (polls the remaining budget: the number of steps is data-dependent; the noise is drawn while the blind
+            # steps are enqueued, before the first poll waits for the GPU)
+            self.engine.run_waves(self.sims, while_enqueued=self._draw_noise_ahead)
+        else:
+            self.engine.run_steps(self.sims)
         self._sims_in_move = self.sims
         self._draw_noise_ahead()                 # the steps are enqueued; the GPU is busy with them
         return self.end_move() * self.sims
@@ -676,14 +693,25 @@ class BackgroundTrainer(object):
                 self._q.task_done()
 
 
-def main(argv=None):
+def effective_threads(args):
+    """Workers per search tree of a CLI run: ``--threads`` with ``--virtual-loss``, else 1 (as ever)."""
+    return args.threads if args.virtual_loss else 1
+
+
+def build_parser():
     parser = argparse.ArgumentParser(description="Plays self-play chess games on MI355X GPUs, "
                                      "stores the game records and trains the model on them.")
     parser.add_argument("model_dir", metavar="modeldir",
                         help="where to load the model from and store the records")
     parser.add_argument("--games", type=int, default=1)
     parser.add_argument("--threads", type=int, default=6,
-                        help="accepted for compatibility (simulations are sequential per game)")
+                        help="workers per search tree (the reference's SelfPlayTree(threads=...)); effective only with "
+                             "--virtual-loss, otherwise accepted for compatibility: simulations are sequential per game")
+    parser.add_argument("--virtual-loss", action="store_true",
+                        help="honour --threads: every move is searched by that many workers per tree, kept apart by the "
+                             "reference's virtual loss, in the deterministic wave schedule (1..64; a step evaluates up "
+                             "to --threads leaves per game).  Widens the tower batch where few games run; not "
+                             "combinable with --reuse-tree.  Default: one worker per tree")
     parser.add_argument("--debug", action="store_true", default=False)
     parser.add_argument("--sims", type=int, default=900, help="MCTS iterations per move")
     parser.add_argument("--parallel", type=int, default=None, help="games in lockstep per GPU")
@@ -734,7 +762,14 @@ def main(argv=None):
                         help="arithmetic of the PUCT term 10 * prior (mctree.py:79-87): 'legacy' = the float64 "
                              "product of the reference's pinned numpy 1.17.2, 'nep50' = the float32 product "
                              "of numpy >= 2, 'auto' = whichever the installed numpy computes")
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
+    if args.virtual_loss and args.reuse_tree:
+        parser.error("--virtual-loss cannot be combined with --reuse-tree")
     logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO)
 
     import datetime
@@ -832,7 +867,7 @@ def main(argv=None):
                                 rank=rank, world=world, device=local, max_plies=max_plies,
                                 total_games=args.games * args.rounds, round_size=args.games,
                                 numpy_promotion=args.numpy_promotion, reuse_tree=args.reuse_tree,
-                                tree_nodes=args.tree_nodes)
+                                tree_nodes=args.tree_nodes, threads=effective_threads(args))
         t0 = time.perf_counter()
         poll = (lambda: background.ready() if background is not None else 0) if not args.no_train else None
         share = min(max(args.trainer_share, 0.0), 0.9)
@@ -865,7 +900,7 @@ def main(argv=None):
                                     noise=not args.no_noise, rank=rank, world=world, device=local,
                                     max_plies=max_plies, total_games=args.games,
                                     numpy_promotion=args.numpy_promotion, reuse_tree=args.reuse_tree,
-                                    tree_nodes=args.tree_nodes)
+                                    tree_nodes=args.tree_nodes, threads=effective_threads(args))
             t0 = time.perf_counter()
             recs = runner.run()
             dt = time.perf_counter() - t0

@@ -268,6 +268,33 @@ int  crl_rollout_games(crl_ctx *ctx, const uint32_t *words /*G x stride*/, const
 int  crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, const uint64_t *dev_keys,
                  void *dev_value_f32, int8_t *dev_results_i8, uint16_t *dev_plies_u16);
 
+/* ---- threads > 1: virtual-loss waves of simulations per game (csrc/search_wave.hpp) --------------------------
+ * The reference runs `threads` explore_tree workers on one tree, kept apart by a virtual loss (mctree.py:12,173-176,
+ * 226-227,289-293).  The wave schedule is the deterministic one among its legal schedules: per game, up to `threads`
+ * workers select one after the other on frozen statistics, all simulate, all back up in thread order; a worker whose
+ * descent would step onto a node created in the same wave stays idle (the wave ends short).  Evaluator rows are
+ * game-major: leaf t of window slot r is row r * threads + t, so every evaluator buffer has slots * threads rows.
+ * CRL_POLICY_FULL only (CRL_ERR_STATE otherwise).  The step is
+ *     crl_wave_select -> policy(S1 rows) -> crl_wave_reply -> policy/value(S2 rows)
+ * and enqueues only (it captures into a hipGraph); a game whose budget is spent idles.
+ * crl_wave_config: 1 <= threads <= CRL_WAVE_MAX_THREADS; allocates the wave arrays (about 6 bytes x threads x
+ * max_games x (max_sims + 1)); synchronises and reads the pending state from the device: CRL_ERR_STATE while a
+ * simulation or a wave is pending (also one enqueued by a replayed hipGraph).  crl_wave_begin / crl_wave_select on a
+ * slot with a pending one-leaf simulation raise the sticky device error (CRL_ERR_STATE at the next synchronising call).
+ * crl_wave_begin: after crl_search_begin + crl_search_root_priors; every live slot gets a budget of n_sims
+ * (1 <= n_sims <= max_sims) simulations and the wave statistics restart.
+ * crl_wave_backup: the backprop of the last wave (the counterpart of crl_sim_backup).
+ * crl_wave_remaining (synchronises): the largest budget not yet selected over the window; 0 = only crl_wave_backup
+ * is left.  crl_wave_stats (synchronises): per window slot, since crl_wave_begin: waves, short waves, leaves. */
+#define CRL_WAVE_MAX_THREADS 64
+int  crl_wave_config(crl_ctx *ctx, int threads);
+int  crl_wave_begin(crl_ctx *ctx, int n_sims);
+int  crl_wave_select(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32, void *dev_planes_s1);
+int  crl_wave_reply(crl_ctx *ctx, const void *dev_policy_s1_f32, void *dev_planes_s2);
+int  crl_wave_backup(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32);
+int  crl_wave_remaining(crl_ctx *ctx, int32_t *max_remaining);
+int  crl_wave_stats(crl_ctx *ctx, int32_t *waves /*G*/, int32_t *short_waves /*G*/, int32_t *leaves /*G*/);
+
 /* ---- tower seam (model.py) -------------------------------------------------------------- */
 /* Residual trunk of ChessModel (model.py:33-37,111-122: stem conv + n_blocks residual blocks,
  * BatchNorm folded) for `filters` in {64, 128, 256} (BASELINE configs C2, C3/C4, C5; 256 is the
