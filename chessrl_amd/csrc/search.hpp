@@ -14,6 +14,14 @@
 //   k_legal/k_push/... Game.get_legal_moves/move/get_result   game.py:28-57,92-109
 //   k_greedy           AgentDistributed.best_move(real_game)  agentdistributed.py:56-58
 //
+// The pieces of a simulation are device functions, each defined once here and called by the one-leaf kernels above
+// and by the wave schedule (search_wave.hpp); a schedule decides only where a leaf is kept and in which order:
+//   best_child         Node.get_value / get_best_child        mctree.py:71-95
+//   descent_step       one level of select                    mctree.py:216-231
+//   expand_child       expand, our move                       mctree.py:231-243
+//   reply_child        expand, the opponent's reply; Node()   mctree.py:244-250,28-37
+//   backup_leaf        simulate + backprop + child priors     mctree.py:259-303
+//
 // Float contract of get_value (mctree.py:71-87), reproduced with explicit
 // round-to-nearest intrinsics (and the file is built with -ffp-contract=off):
 //   Q = value / (1 + visits)                       float64 divide
@@ -182,7 +190,10 @@ __device__ inline void dev_error(const Dev &d, int code)
 // record, which the scan of the level above has just read: one dependent read per level instead of two.
 constexpr u32 HINT_FULL = 1u << 31;
 constexpr int HINT_EDGE_BITS = 23;                 // edge slots per game < 2^23 (38 000 simulations per move)
+constexpr int HINT_EDGE_CAP = 1 << HINT_EDGE_BITS;
 __device__ inline u32 hint_pack(int edge0, int nmoves) { return HINT_FULL | ((u32)nmoves << HINT_EDGE_BITS) | (u32)edge0; }
+__device__ inline int hint_edge0(u32 hint) { return (int)(hint & ((1u << HINT_EDGE_BITS) - 1)); }
+__device__ inline int hint_nmoves(u32 hint) { return (int)((hint >> HINT_EDGE_BITS) & 0xFFu); }
 static_assert(MAX_BRANCH < 256, "nmoves fits the hint");
 
 __device__ inline void init_edges(const Dev &d, size_t eb, int edge0, int n, const u16 *mv, int lane)
@@ -336,6 +347,18 @@ __global__ __launch_bounds__(64) void k_legal_moves(Dev d, u16 *moves, int32_t *
     if (lane == 0) counts[r] = mi.n;
 }
 
+// the legality test of Game.move (game.py:92-109): is mv one of b's legal moves?  (s.mv is free again on return)
+__device__ inline bool is_legal_move(const Board &b, u32 mv, int lane, WaveLds &s)
+{
+    MoveGenInfo mi = wave_movegen(b, lane, s.mv);
+    __syncthreads();
+    bool found = false;
+    for (int j = lane; j < mi.n; j += 64) found = found || s.mv[j] == mv;
+    const bool legal = __ballot(found) != 0;
+    __syncthreads();
+    return legal;
+}
+
 __global__ __launch_bounds__(64) void k_push(Dev d, const u16 *moves, uint8_t *ok)
 {
     __shared__ WaveLds s;
@@ -343,12 +366,7 @@ __global__ __launch_bounds__(64) void k_push(Dev d, const u16 *moves, uint8_t *o
     const u32 mv = moves[r];
     if (mv == NO_MOVE) { if (lane == 0) ok[r] = 0; return; }
     Board b = d.cur[g];
-    MoveGenInfo mi = wave_movegen(b, lane, s.mv);
-    __syncthreads();
-    bool found = false;
-    for (int j = lane; j < mi.n; j += 64) found = found || s.mv[j] == mv;
-    const bool legal = __ballot(found) != 0;
-    __syncthreads();
+    const bool legal = is_legal_move(b, mv, lane, s);
     if (lane == 0) ok[r] = legal ? 1 : 0;
     if (legal) game_push(d, g, b, mv, lane, s);
 }
@@ -366,13 +384,7 @@ __global__ __launch_bounds__(64) void k_push_seq(Dev d, const u16 *seq, const in
         const u32 mv = seq[(size_t)r * stride + i];
         if (mv == NO_MOVE) break;
         Board b = d.cur[g];
-        MoveGenInfo mi = wave_movegen(b, lane, s.mv);
-        __syncthreads();
-        bool found = false;
-        for (int j = lane; j < mi.n; j += 64) found = found || s.mv[j] == mv;
-        const bool legal = __ballot(found) != 0;
-        __syncthreads();
-        if (!legal) break;
+        if (!is_legal_move(b, mv, lane, s)) break;
         game_push(d, g, b, mv, lane, s);
         __threadfence_block();               // lane 0 wrote cur / ply / history ring: the next ply reads them
         __syncthreads();
@@ -414,31 +426,10 @@ __global__ __launch_bounds__(64) void k_greedy(Dev d, const float *pol, const ui
     if (push && d.game[g].game_result == RESULT_NONE) game_push(d, g, b, mv, lane, s);
 }
 
-// Game.get_copy (game.py:79-80): deep copy incl. the move stack, slot src -> slot dst
-__global__ __launch_bounds__(64) void k_copy_game(Dev d, int dst, int src)
+// Game.get_copy (game.py:79-80): deep copy incl. the move stack, slot src of context sd -> slot dst of context d
+// (within one context sd is d, and the ply-pool test cannot fail)
+__device__ inline void copy_game(const Dev &d, int dst, const Dev &sd, int src, int lane)
 {
-    const int lane = threadIdx.x;
-    const int p = d.game[src].ply;
-    for (int i = lane; i < HIST_RING; i += 64) {
-        d.hist[(size_t)dst * HIST_RING + i] = d.hist[(size_t)src * HIST_RING + i];
-        d.hist_hash[(size_t)dst * HIST_RING + i] = d.hist_hash[(size_t)src * HIST_RING + i];
-    }
-    for (int i = lane; i < p; i += 64)
-        d.rec_moves[(size_t)dst * d.MAXPLY + i] = d.rec_moves[(size_t)src * d.MAXPLY + i];
-    if (lane == 0) {
-        d.cur[dst] = d.cur[src];
-        d.game[dst].ply = p;
-        d.game[dst].game_result = d.game[src].game_result;
-        d.game[dst].root_dead = 1;
-        d.game[dst].leaf_kind = LEAF_NONE;
-    }
-}
-
-// Tree.__init__ (mctree.py:105-109: ``Node(root.get_copy())``) when the caller's Game lives in another
-// context (the Game arena) than the search engine: the same deep copy across two contexts of one GPU.
-__global__ __launch_bounds__(64) void k_copy_game_across(Dev d, int dst, Dev sd, int src)
-{
-    const int lane = threadIdx.x;
     const int p = sd.game[src].ply;
     if (p > d.MAXPLY) { if (lane == 0) dev_error(d, DERR_PLY_POOL); return; }
     for (int i = lane; i < HIST_RING; i += 64) {
@@ -454,6 +445,18 @@ __global__ __launch_bounds__(64) void k_copy_game_across(Dev d, int dst, Dev sd,
         d.game[dst].root_dead = 1;
         d.game[dst].leaf_kind = LEAF_NONE;
     }
+}
+
+__global__ __launch_bounds__(64) void k_copy_game(Dev d, int dst, int src)
+{
+    copy_game(d, dst, d, src, threadIdx.x);
+}
+
+// Tree.__init__ (mctree.py:105-109: ``Node(root.get_copy())``) when the caller's Game lives in another
+// context (the Game arena) than the search engine: the same deep copy across two contexts of one GPU.
+__global__ __launch_bounds__(64) void k_copy_game_across(Dev d, int dst, Dev sd, int src)
+{
+    copy_game(d, dst, sd, src, threadIdx.x);
 }
 
 // ---- SelfPlayTree seam kernels -------------------------------------------------------------------
@@ -510,41 +513,59 @@ __global__ __launch_bounds__(64) void k_root_priors(Dev d, const float *pol)
     if (lane == 0) d.counters[(size_t)g * CNT_N + CNT_EVALS] += 1;
 }
 
-// simulate + backprop (+ priors of the new node's future children) for the pending simulation
+// what backed-up leaves add to the per-game counters
+struct SimCounts { unsigned long long sims = 0, depth = 0, evals = 0, term = 0, nodes = 0, branch = 0; };
+
+// simulate + backprop (+ priors of the new node's future children) of ONE leaf (mctree.py:259-303): `kind` is
+// LEAF_TERMINAL_HIT, LEAF_NEW_S1_OVER or LEAF_NEW_S2, `path` the plen edges that lead to it, `row` its evaluator row
+__device__ inline void backup_leaf(const Dev &d, int g, int row, int lane, int kind, int leaf, int plen,
+                                   const int32_t *path, const float *pol2, const float *val2, int fmt,
+                                   const float2 *stats, SimCounts &n)
+{
+    const size_t eb = (size_t)g * d.ECAP;
+    const NodeMeta m = d.node[(size_t)g * d.N + leaf].meta;
+    double v;
+    if (m.result != RESULT_NONE) {
+        v = (double)m.result;                          // state.get_result() (mctree.py:268)
+    } else {
+        v = (double)val2[row];                         // python float of the f32 value head
+        gather_priors(d, row, eb, m.edge0, m.nmoves, pol2, lane, fmt, stats);
+        n.evals += 1;                                  // policy/value(S2)
+    }
+    if (kind == LEAF_NEW_S2) n.evals += 1;             // policy(S1) chose the reply
+    for (int l = lane; l < plen; l += 64) {
+        Edge *e = d.edge + eb + path[l];
+        e->visits += 1;
+        e->value = __dadd_rn(e->value, v);
+    }
+    n.sims += 1;
+    n.depth += plen;
+    if (kind == LEAF_TERMINAL_HIT) n.term += 1;
+    else { n.nodes += 1; n.branch += m.nmoves; }
+}
+
+__device__ inline void add_counts(const Dev &d, int g, const SimCounts &n)     // one lane
+{
+    d.game[g].root_visits += (int)n.sims;
+    unsigned long long *c = d.counters + (size_t)g * CNT_N;
+    c[CNT_SIMS] += n.sims; c[CNT_DEPTH] += n.depth; c[CNT_EVALS] += n.evals;
+    if (n.term) c[CNT_TERMINAL] += n.term;
+    if (n.nodes) { c[CNT_NODES] += n.nodes; c[CNT_BRANCH] += n.branch; }
+}
+
+// ... for the pending simulation
 __device__ inline void backup_pending(const Dev &d, int g, int row, int lane, const float *pol2,
                                       const float *val2)
 {
     const int kind = uni(d.game[g].leaf_kind);
     if (kind == LEAF_NONE) return;
-    const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
     if (kind == LEAF_NEW_REPLY) { dev_error(d, DERR_STATE); return; }
-    const int leaf = uni(d.game[g].leaf_node);
-    NodeMeta m = d.node[nb + leaf].meta;
-    double v;
-    unsigned long long evals = 0;
-    if (m.result != RESULT_NONE) {
-        v = (double)m.result;                          // state.get_result() (mctree.py:268)
-    } else {
-        v = (double)val2[row];                           // python float of the f32 value head
-        gather_priors(d, row, eb, m.edge0, m.nmoves, pol2, lane, d.policy_fmt, d.stats_s2);
-        evals = 1;                                     // policy/value(S2)
-    }
-    if (kind == LEAF_NEW_S2) evals += 1;               // policy(S1) chose the reply
-    const int plen = uni(d.game[g].path_len);
-    for (int l = lane; l < plen; l += 64) {
-        Edge *e = d.edge + eb + d.path_edge[nb + l];
-        e->visits += 1;
-        e->value = __dadd_rn(e->value, v);
-    }
+    SimCounts n;
+    backup_leaf(d, g, row, lane, kind, uni(d.game[g].leaf_node), uni(d.game[g].path_len),
+                d.path_edge + (size_t)g * d.N, pol2, val2, d.policy_fmt, d.stats_s2, n);
     if (lane == 0) {
-        d.game[g].root_visits += 1;
         d.game[g].leaf_kind = LEAF_NONE;
-        unsigned long long *c = d.counters + (size_t)g * CNT_N;
-        c[CNT_SIMS] += 1;
-        c[CNT_DEPTH] += plen;
-        c[CNT_EVALS] += evals;
-        if (kind == LEAF_TERMINAL_HIT) c[CNT_TERMINAL] += 1;
-        else { c[CNT_NODES] += 1; c[CNT_BRANCH] += m.nmoves; }
+        add_counts(d, g, n);
     }
     __syncthreads();
 }
@@ -556,154 +577,168 @@ __global__ __launch_bounds__(64) void k_backup(Dev d, const float *pol2, const f
     backup_pending(d, g, r, lane, pol2, val2);
 }
 
-__global__ __launch_bounds__(64, 4) void k_select_expand(Dev d, const float *pol2, const float *val2,
-                                                      void *planes1)
-{
-    __shared__ WaveLds s;
-    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
-    if (lane == 0) d.lab_n1[r] = 0;                     // no policy(S1) wanted unless a reply is needed
-    if (d.game[g].root_dead) return;
-    backup_pending(d, g, r, lane, pol2, val2);
-
-    const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
-    const bool legacy = (d.flags & 1u) != 0;
-    const int p = uni(d.game[g].ply);
+// ---- the pieces of one simulation, shared by the one-leaf kernels below and the waves of search_wave.hpp ---------
+// Where a descent stands: the node, its depth, and what select needs of the node's record (wave-uniform).
+struct Descent {
     int node = 0, level = 0;
     int edge0 = 0, nmoves = 0, nexp = 0, result = RESULT_NONE, parent_edge = -1;
     bool need_meta = true;                                             // false: the parent's edge record said it all
-    if (d.ECAP >= (1 << HINT_EDGE_BITS)) { dev_error(d, DERR_EDGE_POOL); return; }   // edge slots fit the hint
-    for (;;) {
-        if (need_meta) {
-            NodeMeta m = d.node[nb + node].meta;
-            edge0 = uni(m.edge0); nmoves = uni(m.nmoves); nexp = uni(m.nexp);
-            result = uni(m.result); parent_edge = uni(m.parent_edge);
-        }
-        if (result != RESULT_NONE) {                                   // is_terminal_state
-            if (lane == 0) { d.game[g].leaf_kind = LEAF_TERMINAL_HIT; d.game[g].leaf_node = node; }
-            break;
-        }
-        if (nexp < nmoves) {                                           // not fully expanded
-            const int j = nmoves - 1 - nexp;                           // list.pop(): last first
-            const int edge = edge0 + j;
-            const u32 mv = d.edge[eb + edge].move;
-            const int c = uni(d.game[g].n_nodes);                           // wave-uniform: scalar addressing
-            if (c >= d.N || level + 1 >= d.N) { dev_error(d, DERR_NODE_POOL); break; }
-            if (lane == 0) {
-                d.node[nb + node].meta.nexp = (u16)(nexp + 1);
-                if (nexp + 1 == nmoves && parent_edge >= 0)            // fully expanded from now on: leave the hint
-                    d.edge[eb + parent_edge].pad = hint_pack(edge0, nmoves);
-                d.path_edge[nb + level] = edge;
-                d.path_node[nb + level + 1] = (u16)c;
-                d.game[g].n_nodes = c + 1;
-            }
-            level++;
-            Board parent = d.node[nb + node].s2;
-            Board s1 = apply_move(parent, mv);
-            __syncthreads();                                           // path_node visible
-            PosEval e = eval_position(d, g, s1, 2 * level - 1, p, p, lane, s);
-            NodeMeta cm;
-            cm.edge0 = 0; cm.nmoves = (u16)e.n; cm.nexp = 0; cm.result = (int8_t)e.result;
-            cm.has_s2 = 0; cm.parent = (u16)node; cm.parent_edge = edge;
-            if (lane == 0) {
-                d.node[nb + c].s1 = e.b;
-                d.node[nb + c].h1 = e.hash;
-                d.node[nb + c].meta = cm;
-                d.game[g].leaf_node = c;
-            }
-            if (e.result != RESULT_NONE) {                              // game ended on our move
-                if (lane == 0) {
-                    d.node[nb + c].s2 = e.b;
-                    d.node[nb + c].h2 = e.hash;
-                    d.edge[eb + edge].child = (u16)(c | CHILD_TERMINAL);
-                    d.game[g].leaf_kind = LEAF_NEW_S1_OVER;
-                }
-            } else {
-                for (int i = lane; i < e.n; i += 64) d.s1_moves[(size_t)g * MAX_MOVES + i] = s.mv[i];
-                if (d.policy_fmt) write_labels(d, r, s.mv, e.n, d.lab_s1, d.lab_n1, lane);
-                if (lane == 0) {
-                    d.edge[eb + edge].child = (u16)c;
-                    d.game[g].s1_n = e.n;
-                    d.game[g].leaf_kind = LEAF_NEW_REPLY;
-                }
-                __syncthreads();
-                encode_position(d, g, e.b, 2 * level - 1, p, p, lane, s, planes1, r);
-            }
-            break;
-        }
-        // ---- get_best_child (mctree.py:89-95): argmax of Q+U, first max in children order,
-        // i.e. the LARGEST legal index among equals
-        double best = -__builtin_inf();
-        int bj = -1, bchild = 0;
-        u32 bhint = 0;
-        for (int base = 0; base < nmoves; base += 64) {
-            const int j = base + lane;
-            if (j < nmoves) {
-                const Edge e = d.edge[eb + edge0 + j];                 // one 24-byte record per lane
-                const int n = e.visits;
-                const bool term = (e.child & CHILD_TERMINAL) != 0;
-                const double den = (double)(1 + n);
-                const double q = __ddiv_rn(e.value, den);
-                const double sumv = term ? 0.0 : (double)(n - 1);
-                const double cp = legacy ? __dmul_rn(10.0, (double)e.prior)
-                                         : (double)__fmul_rn(10.0f, e.prior);
-                const double u = __dmul_rn(cp, __ddiv_rn(__dsqrt_rn(sumv), den));
-                const double sc = __dadd_rn(q, u);
-                if (bj < 0 || sc > best || (sc == best && j > bj)) { best = sc; bj = j; bchild = e.child; bhint = e.pad; }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const double ob = __shfl_xor(best, o);
-            const int oj = __shfl_xor(bj, o);
-            const int oc = __shfl_xor(bchild, o);
-            const u32 oh = __shfl_xor(bhint, o);
-            const bool take = oj >= 0 && (bj < 0 || ob > best || (ob == best && oj > bj));
-            if (take) { best = ob; bj = oj; bchild = oc; bhint = oh; }
-        }
-        bj = uni(bj);
-        const int edge = edge0 + bj;
-        const int child = uni(bchild) & CHILD_NONE;                    // the winner's record held it
-        if (level + 1 >= d.N) { dev_error(d, DERR_NODE_POOL); break; }
-        if (lane == 0) {
-            d.path_edge[nb + level] = edge;
-            d.path_node[nb + level + 1] = (u16)child;
-        }
-        level++;
-        node = uni(child);
-        const u32 hint = uni(bhint);
-        if (uni(bchild) & CHILD_TERMINAL) {                            // the child's state ended the game: as its
-            need_meta = false;                                         // record would say (result != RESULT_NONE)
-            result = 0;                                                // any value but RESULT_NONE: only tested
-        } else if (hint & HINT_FULL) {                                 // fully expanded: straight to its edge records
-            need_meta = false;
-            edge0 = (int)(hint & ((1u << HINT_EDGE_BITS) - 1)); nmoves = (int)((hint >> HINT_EDGE_BITS) & 0xFFu); nexp = nmoves;
-            result = RESULT_NONE;
-        } else {
-            need_meta = true;
-        }
-    }
-    if (lane == 0) d.game[g].path_len = level;
+};
+
+__device__ inline void descent_load_meta(const Dev &d, int g, Descent &x)
+{
+    if (!x.need_meta) return;
+    const NodeMeta m = d.node[(size_t)g * d.N + x.node].meta;
+    x.edge0 = uni(m.edge0); x.nmoves = uni(m.nmoves); x.nexp = uni(m.nexp);
+    x.result = uni(m.result); x.parent_edge = uni(m.parent_edge);
 }
 
-__global__ __launch_bounds__(64) void k_reply(Dev d, const float *pol1, void *planes2)
+// get_best_child (mctree.py:89-95): argmax of get_value over the node's edge run, first max in children order, i.e.
+// the LARGEST legal index among equals.  The value is Q + U of the float contract at the top of this file.  VLOSS (the
+// wave schedule) makes it (Q + U) - vloss, vloss = how many of the wave's `cnt` leaf edges in `ledge` (LDS) are this
+// edge, and counts no children for a child without visits.
+struct BestChild { int j, child; u32 hint; };                          // legal index, the edge's child word and hint
+
+template <bool VLOSS>
+__device__ inline BestChild best_child(const Dev &d, int g, int edge0, int nmoves, int lane,
+                                       const int *ledge = nullptr, int cnt = 0)
 {
-    __shared__ WaveLds s;
-    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
-    if (lane == 0) d.lab_n2[r] = 0;                     // no policy(S2) wanted unless a new node gets priors
-    if (d.game[g].root_dead || d.game[g].leaf_kind != LEAF_NEW_REPLY) return;
+    const bool legacy = (d.flags & 1u) != 0;
+    const Edge *run = d.edge + (size_t)g * d.ECAP + edge0;
+    double best = -__builtin_inf();
+    int bj = -1, bchild = 0;
+    u32 bhint = 0;
+    for (int base = 0; base < nmoves; base += 64) {
+        const int j = base + lane;
+        if (j < nmoves) {
+            const Edge e = run[j];                                     // one 24-byte record per lane
+            const int n = e.visits;
+            const bool term = (e.child & CHILD_TERMINAL) != 0;
+            const double den = (double)(1 + n);
+            const double q = __ddiv_rn(e.value, den);
+            const bool childless = VLOSS ? (term || n == 0) : term;
+            const double sumv = childless ? 0.0 : (double)(n - 1);
+            const double cp = legacy ? __dmul_rn(10.0, (double)e.prior)
+                                     : (double)__fmul_rn(10.0f, e.prior);
+            const double u = __dmul_rn(cp, __ddiv_rn(__dsqrt_rn(sumv), den));
+            double sc = __dadd_rn(q, u);
+            if constexpr (VLOSS) {
+                int vl = 0;
+                for (int k = 0; k < cnt; k++) vl += ledge[k] == edge0 + j ? 1 : 0;
+                sc = __dsub_rn(sc, (double)vl);
+            }
+            if (bj < 0 || sc > best || (sc == best && j > bj)) { best = sc; bj = j; bchild = e.child; bhint = e.pad; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double ob = __shfl_xor(best, o);
+        const int oj = __shfl_xor(bj, o);
+        const int oc = __shfl_xor(bchild, o);
+        const u32 oh = __shfl_xor(bhint, o);
+        const bool take = oj >= 0 && (bj < 0 || ob > best || (ob == best && oj > bj));
+        if (take) { best = ob; bj = oj; bchild = oc; bhint = oh; }
+    }
+    BestChild bc;
+    bc.j = uni(bj); bc.child = uni(bchild); bc.hint = uni(bhint);      // the winner's record held them
+    return bc;
+}
+
+// step into the chosen child: the path grows, and the edge record tells what is known of the child without its own
+// record.  false: the path pool is exhausted (nothing was written).
+__device__ inline bool descent_step(const Dev &d, int g, int lane, Descent &x, const BestChild &bc)
+{
+    const size_t nb = (size_t)g * d.N;
+    const int child = bc.child & CHILD_NONE;
+    if (x.level + 1 >= d.N) { dev_error(d, DERR_NODE_POOL); return false; }
+    if (lane == 0) {
+        d.path_edge[nb + x.level] = x.edge0 + bc.j;
+        d.path_node[nb + x.level + 1] = (u16)child;
+    }
+    x.level++;
+    x.node = child;
+    x.need_meta = false;
+    if (bc.child & CHILD_TERMINAL) {                                   // the child's state ended the game: as its
+        x.result = 0;                                                  // record would say (any value but RESULT_NONE)
+    } else if (bc.hint & HINT_FULL) {                                  // fully expanded: straight to its edge records
+        x.edge0 = hint_edge0(bc.hint); x.nmoves = hint_nmoves(bc.hint); x.nexp = x.nmoves;
+        x.result = RESULT_NONE;
+    } else {
+        x.need_meta = true;
+    }
+    return true;
+}
+
+// expand (mctree.py:231-243), our half: the next unexpanded move of node x.node becomes node c.  Everything up to the
+// encoded planes of S1 in row `row` of planes1; the caller records the leaf where its schedule keeps it.  kind:
+// LEAF_NEW_S1_OVER, LEAF_NEW_REPLY (then s.mv holds the n legal moves of S1), or LEAF_NONE when a pool is exhausted
+// (nothing was written).  `fence`: the wave schedule's block fence in front of the barrier that publishes the path.
+struct NewLeaf { int kind, edge, n; };
+
+__device__ inline NewLeaf expand_child(const Dev &d, int g, int row, int lane, WaveLds &s, Descent &x, int c, int ply,
+                                       void *planes1, bool fence)
+{
     const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
-    const int c = uni(d.game[g].leaf_node), level = uni(d.game[g].path_len), n1 = uni(d.game[g].s1_n), p = uni(d.game[g].ply);
+    NewLeaf lf;
+    lf.kind = LEAF_NONE; lf.n = 0;
+    lf.edge = x.edge0 + (x.nmoves - 1 - x.nexp);                       // list.pop(): last first
+    if (c >= d.N || x.level + 1 >= d.N) { dev_error(d, DERR_NODE_POOL); return lf; }
+    const u32 mv = d.edge[eb + lf.edge].move;
+    if (lane == 0) {
+        d.node[nb + x.node].meta.nexp = (u16)(x.nexp + 1);
+        if (x.nexp + 1 == x.nmoves && x.parent_edge >= 0)              // fully expanded from now on: leave the hint
+            d.edge[eb + x.parent_edge].pad = hint_pack(x.edge0, x.nmoves);
+        d.path_edge[nb + x.level] = lf.edge;
+        d.path_node[nb + x.level + 1] = (u16)c;
+    }
+    x.level++;
+    Board parent = d.node[nb + x.node].s2;
+    Board s1 = apply_move(parent, mv);
+    if (fence) __threadfence_block();
+    __syncthreads();                                                   // path_node visible
+    PosEval e = eval_position(d, g, s1, 2 * x.level - 1, ply, ply, lane, s);
+    NodeMeta cm;
+    cm.edge0 = 0; cm.nmoves = (u16)e.n; cm.nexp = 0; cm.result = (int8_t)e.result;
+    cm.has_s2 = 0; cm.parent = (u16)x.node; cm.parent_edge = lf.edge;
+    if (lane == 0) {
+        d.node[nb + c].s1 = e.b;
+        d.node[nb + c].h1 = e.hash;
+        d.node[nb + c].meta = cm;
+    }
+    lf.n = e.n;
+    if (e.result != RESULT_NONE) {                                     // game ended on our move
+        if (lane == 0) {
+            d.node[nb + c].s2 = e.b;
+            d.node[nb + c].h2 = e.hash;
+            d.edge[eb + lf.edge].child = (u16)(c | CHILD_TERMINAL);
+        }
+        lf.kind = LEAF_NEW_S1_OVER;
+    } else {
+        if (lane == 0) d.edge[eb + lf.edge].child = (u16)c;
+        lf.kind = LEAF_NEW_REPLY;
+        __syncthreads();
+        encode_position(d, g, e.b, 2 * x.level - 1, ply, ply, lane, s, planes1, row);   // (leaves s.mv alone)
+    }
+    return lf;
+}
+
+// expand, the opponent's half (mctree.py:244-250) and Node() of the new state (mctree.py:28-37): node c, reached by a
+// path of `level` edges, whose S1 has the n1 legal moves mv1, gets the reply agent.best_move(S1, real_game=True) picks
+// from row `row` of pol1, its S2, an edge run from slot edge0 on and the planes of S2 in row `row` of planes2.
+// Returns the length of the run, -1 when the edge pool is exhausted (nothing was written).
+__device__ inline int reply_child(const Dev &d, int g, int row, int lane, WaveLds &s, int c, int level, int ply,
+                                  const u16 *mv1, int n1, int edge0, const float *pol1, int fmt, const float2 *stats,
+                                  uint8_t *kind, void *planes2)
+{
+    const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
     Board s1 = d.node[nb + c].s1;
-    // agent.best_move(S1, real_game=True): legal[argmax(policy masked to legal)]
-    const u16 *mv1 = d.s1_moves + (size_t)g * MAX_MOVES;
-    const int bi = argmax_policy(d, r, mv1, n1, pol1, lane, d.policy_fmt, d.stats_s1);
+    const int bi = argmax_policy(d, row, mv1, n1, pol1, lane, fmt, stats);   // legal[argmax(policy masked to legal)]
     const u32 reply = mv1[bi];
     Board s2 = apply_move(s1, reply);
-    PosEval e = eval_position(d, g, s2, 2 * level, p, p, lane, s);
-    const int edge0 = uni(d.game[g].edge_top);
-    if (edge0 + e.n > d.ECAP) { dev_error(d, DERR_EDGE_POOL); return; }
+    PosEval e = eval_position(d, g, s2, 2 * level, ply, ply, lane, s);
+    if (edge0 + e.n > d.ECAP) { dev_error(d, DERR_EDGE_POOL); return -1; }
     init_edges(d, eb, edge0, e.n, s.mv, lane);
-    if (d.policy_fmt && e.result == RESULT_NONE) write_labels(d, r, s.mv, e.n, d.lab_s2, d.lab_n2, lane);
+    if (fmt != FMT_FULL && e.result == RESULT_NONE) write_labels(d, row, s.mv, e.n, d.lab_s2, d.lab_n2, lane);
     if (lane == 0) {
         NodeMeta m = d.node[nb + c].meta;
         m.edge0 = edge0; m.nmoves = (u16)e.n; m.nexp = 0; m.result = (int8_t)e.result; m.has_s2 = 1;
@@ -713,10 +748,57 @@ __global__ __launch_bounds__(64) void k_reply(Dev d, const float *pol1, void *pl
         d.node[nb + c].reply = (u16)reply;
         d.game[g].edge_top = edge0 + e.n;
         if (e.result != RESULT_NONE) d.edge[eb + m.parent_edge].child = (u16)(c | CHILD_TERMINAL);
-        d.game[g].leaf_kind = LEAF_NEW_S2;
+        *kind = LEAF_NEW_S2;
     }
     __syncthreads();
-    encode_position(d, g, e.b, 2 * level, p, p, lane, s, planes2, r);
+    encode_position(d, g, e.b, 2 * level, ply, ply, lane, s, planes2, row);
+    return e.n;
+}
+
+__global__ __launch_bounds__(64, 4) void k_select_expand(Dev d, const float *pol2, const float *val2,
+                                                      void *planes1)
+{
+    __shared__ WaveLds s;
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    if (lane == 0) d.lab_n1[r] = 0;                     // no policy(S1) wanted unless a reply is needed
+    if (d.game[g].root_dead) return;
+    backup_pending(d, g, r, lane, pol2, val2);
+
+    const int p = uni(d.game[g].ply);
+    if (d.ECAP >= HINT_EDGE_CAP) { dev_error(d, DERR_EDGE_POOL); return; }   // edge slots fit the hint
+    Descent x;
+    for (;;) {
+        descent_load_meta(d, g, x);
+        if (x.result != RESULT_NONE) {                                 // is_terminal_state
+            if (lane == 0) { d.game[g].leaf_kind = LEAF_TERMINAL_HIT; d.game[g].leaf_node = x.node; }
+            break;
+        }
+        if (x.nexp < x.nmoves) {                                       // not fully expanded
+            const int c = uni(d.game[g].n_nodes);                      // wave-uniform: scalar addressing
+            const NewLeaf lf = expand_child(d, g, r, lane, s, x, c, p, planes1, false);
+            if (lf.kind == LEAF_NONE) break;
+            if (lf.kind == LEAF_NEW_REPLY) {
+                for (int i = lane; i < lf.n; i += 64) d.s1_moves[(size_t)g * MAX_MOVES + i] = s.mv[i];
+                if (d.policy_fmt) write_labels(d, r, s.mv, lf.n, d.lab_s1, d.lab_n1, lane);
+                if (lane == 0) d.game[g].s1_n = lf.n;
+            }
+            if (lane == 0) { d.game[g].n_nodes = c + 1; d.game[g].leaf_node = c; d.game[g].leaf_kind = lf.kind; }
+            break;
+        }
+        if (!descent_step(d, g, lane, x, best_child<false>(d, g, x.edge0, x.nmoves, lane))) break;
+    }
+    if (lane == 0) d.game[g].path_len = x.level;
+}
+
+__global__ __launch_bounds__(64) void k_reply(Dev d, const float *pol1, void *planes2)
+{
+    __shared__ WaveLds s;
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    if (lane == 0) d.lab_n2[r] = 0;                     // no policy(S2) wanted unless a new node gets priors
+    if (d.game[g].root_dead || d.game[g].leaf_kind != LEAF_NEW_REPLY) return;
+    reply_child(d, g, r, lane, s, uni(d.game[g].leaf_node), uni(d.game[g].path_len), uni(d.game[g].ply),
+                d.s1_moves + (size_t)g * MAX_MOVES, uni(d.game[g].s1_n), uni(d.game[g].edge_top), pol1,
+                d.policy_fmt, d.stats_s1, &d.game[g].leaf_kind, planes2);
 }
 
 __global__ __launch_bounds__(64) void k_root_children(Dev d, int32_t *nchild, int32_t *visits,
@@ -745,6 +827,31 @@ __global__ __launch_bounds__(64) void k_root_children(Dev d, int32_t *nchild, in
     }
 }
 
+// gam.move(bm); gam.move(am) (selfplay.py:77-78) with the moves of root child c, reached over edge record ed: the
+// game goes on by one ply (the game ended on our move) or two, to ply np; the tree is consumed.  One lane.
+__device__ inline void advance_game(const Dev &d, int g, int r, int c, const Edge &ed, const NodeMeta &cm, int np,
+                                    u16 *bm, u16 *am)
+{
+    const NodeRow &n = d.node[(size_t)g * d.N + c];
+    const int p = d.game[g].ply;
+    size_t hi = (size_t)g * HIST_RING + ((p + 1) & (HIST_RING - 1));
+    d.hist[hi] = n.s1;
+    d.hist_hash[hi] = n.h1;
+    d.rec_moves[(size_t)g * d.MAXPLY + p] = ed.move;
+    bm[r] = ed.move;
+    if (cm.has_s2) {
+        hi = (size_t)g * HIST_RING + ((p + 2) & (HIST_RING - 1));
+        d.hist[hi] = n.s2;
+        d.hist_hash[hi] = n.h2;
+        d.rec_moves[(size_t)g * d.MAXPLY + p + 1] = n.reply;
+        am[r] = n.reply;
+    }
+    d.cur[g] = n.s2;                              // node state (S1 copy when the game ended there)
+    d.game[g].ply = np;
+    d.game[g].game_result = cm.result;
+    d.game[g].root_dead = 1;                      // the tree is consumed: fresh tree per move
+}
+
 __global__ __launch_bounds__(64) void k_advance(Dev d, const int32_t *chosen, u16 *bm, u16 *am)
 {
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
@@ -758,25 +865,9 @@ __global__ __launch_bounds__(64) void k_advance(Dev d, const int32_t *chosen, u1
     const Edge ed = d.edge[eb + m.edge0 + (m.nmoves - 1 - k)];
     const int c = ed.child & CHILD_NONE;
     NodeMeta cm = d.node[nb + c].meta;
-    const int p = d.game[g].ply;
-    const int np = p + (cm.has_s2 ? 2 : 1);
+    const int np = d.game[g].ply + (cm.has_s2 ? 2 : 1);
     if (np > d.MAXPLY) { dev_error(d, DERR_PLY_POOL); return; }
-    size_t hi = (size_t)g * HIST_RING + ((p + 1) & (HIST_RING - 1));
-    d.hist[hi] = d.node[nb + c].s1;
-    d.hist_hash[hi] = d.node[nb + c].h1;
-    d.rec_moves[(size_t)g * d.MAXPLY + p] = ed.move;
-    bm[r] = ed.move;
-    if (cm.has_s2) {
-        hi = (size_t)g * HIST_RING + ((p + 2) & (HIST_RING - 1));
-        d.hist[hi] = d.node[nb + c].s2;
-        d.hist_hash[hi] = d.node[nb + c].h2;
-        d.rec_moves[(size_t)g * d.MAXPLY + p + 1] = d.node[nb + c].reply;
-        am[r] = d.node[nb + c].reply;
-    }
-    d.cur[g] = d.node[nb + c].s2;                 // node state (S1 copy when the game ended there)
-    d.game[g].ply = np;
-    d.game[g].game_result = cm.result;
-    d.game[g].root_dead = 1;                       // the tree is consumed: fresh tree per move
+    advance_game(d, g, r, c, ed, cm, np, bm, am);
 }
 
 // ---- Tree(Node) (mctree.py:98-111): the chosen child becomes the root and keeps its subtree --------------------
@@ -811,23 +902,8 @@ __global__ __launch_bounds__(64) void k_reroot(Dev d, const int32_t *chosen, int
     const int np = p + (cm.has_s2 ? 2 : 1);
     if (np > d.MAXPLY) { if (lane == 0) dev_error(d, DERR_PLY_POOL); return; }
     const int n = uni(d.game[g].n_nodes);
-    if (lane == 0) {                                                   // gam.move(bm); gam.move(am) as in k_advance
-        size_t hi = (size_t)g * HIST_RING + ((p + 1) & (HIST_RING - 1));
-        d.hist[hi] = d.node[nb + c].s1;
-        d.hist_hash[hi] = d.node[nb + c].h1;
-        d.rec_moves[(size_t)g * d.MAXPLY + p] = ed.move;
-        bm[r] = ed.move;
-        if (cm.has_s2) {
-            hi = (size_t)g * HIST_RING + ((p + 2) & (HIST_RING - 1));
-            d.hist[hi] = d.node[nb + c].s2;
-            d.hist_hash[hi] = d.node[nb + c].h2;
-            d.rec_moves[(size_t)g * d.MAXPLY + p + 1] = d.node[nb + c].reply;
-            am[r] = d.node[nb + c].reply;
-        }
-        d.cur[g] = d.node[nb + c].s2;
-        d.game[g].ply = np;
-        d.game[g].game_result = cm.result;
-        d.game[g].root_dead = 1;
+    if (lane == 0) {
+        advance_game(d, g, r, c, ed, cm, np, bm, am);
         d.game[g].root_kept = 0;
     }
     if (!cm.has_s2 || cm.result != RESULT_NONE) return;
@@ -904,7 +980,7 @@ __global__ __launch_bounds__(64) void k_reroot(Dev d, const int32_t *chosen, int
                     if (e.child != CHILD_NONE) {
                         const int cid = e.child & CHILD_NONE;
                         e.child = (u16)(map[cid] | (e.child & CHILD_TERMINAL));
-                        if (e.pad & HINT_FULL) e.pad = hint_pack(ne0[cid], (int)((e.pad >> HINT_EDGE_BITS) & 0xFFu));
+                        if (e.pad & HINT_FULL) e.pad = hint_pack(ne0[cid], hint_nmoves(e.pad));
                     }
                 }
                 __syncthreads();                                       // 64 records read before they are written
