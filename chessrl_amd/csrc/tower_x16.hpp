@@ -151,6 +151,20 @@ __device__ inline void stage_bias_x16(const float *bias, lds_byte *lds, int conv
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
+// Rank tiles (128 filters, four boards per workgroup, pair ring, f16): a wave owns 2 boards x 4 ranks x 64
+// channels instead of 1 board x 8 ranks x 64 channels, so that a 16-position MFMA block is ONE rank of a pair
+// of boards and a block whose rank + dy is off the board is off the board as a whole: its MFMAs and its
+// activation fragment reads are not issued (k_trunk_x16 below).  0 builds the board tiles of before
+// (tools/ubench/trunk_r3.hip times both).
+#ifndef CRL_TRUNK_RANKPAIR
+#define CRL_TRUNK_RANKPAIR 1
+#endif
+template <int F, int NB, int ALT, int PAIR, int GROUP, int SPLIT, int IDX>
+struct RankTiles {
+    static constexpr bool value = CRL_TRUNK_RANKPAIR != 0 && F == 128 && NB == 4 && PAIR == 1 && GROUP == 0 &&
+                                  SPLIT == 0 && IDX == 0 && (ALT == 0 || ALT == 2);
+};
+
 template <int N> __device__ __forceinline__ void wait_vmcnt_n()
 {
     static_assert(N >= 0 && N < 64, "vmcnt immediate");
@@ -218,11 +232,26 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
     lds_byte *lds = (lds_byte *)lds_raw;
     const int lds_base = (int)(size_t)lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int board = wave / G::WPB;
+    const int board_w = wave / G::WPB;
     const int obase = (16 * CT) * ((wave / G::PH) % G::CG);      // first output channel of this wave
     const int pbase = 32 * (wave % G::PH);              // first position of this wave
     const int r = lane & 15, q = lane >> 4;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    // Rank tiles (RP): wave w = pair (w >> 1) & 1 of the workgroup's boards, channel group w & 1, rank half w >> 2.
+    // Block ("slot") pt is one rank: lanes r < 8 are file r of the pair's first board, lanes r >= 8 file r - 8 of
+    // its second.  The upper half enumerates its ranks in reverse -- slot s = rank s for half 0, rank 7 - s for
+    // half 1 -- so that the block that leaves the board is slot 0 for both: rank 0 under dy = -1, rank 7 under
+    // dy = +1.  Waves w and w + 4 are the two waves of one SIMD (waves go to the four SIMDs round robin; the
+    // stage_wtile_x16 ALT 1 experiment above and the requesting halves of csrc/tower_layer.hpp rest on the same
+    // assignment): same pair and channel group, opposite rank halves, so in each of the six dy != 0 taps every
+    // SIMD has exactly one wave that skips -- 112 MFMAs per tap and SIMD instead of 128 -- and no wave waits
+    // at the tap's barrier for a partner with more work.
+    constexpr bool RP = RankTiles<F, NB, ALT, PAIR, GROUP, SPLIT, IDX>::value;
+    const int rp_half = wave_u >> 2;                    // RP: 0 = ranks 0-3 (slot = rank), 1 = ranks 7-4
+    const int board = RP ? 2 * ((wave >> 1) & 1) + (r >> 3) : board_w;           // RP: per lane
+    // position of the lane in block 0 and the step to the next block, in positions (= activation rows)
+    const int pos0 = RP ? (rp_half ? 56 : 0) + (r & 7) : pbase + r;
+    const int pstep = RP ? (rp_half ? -8 : 8) : 16;
     const int n_convs = 1 + 2 * n_blocks;
     // SPLIT: two weight parts per tap (the planes of Whi, then of Wlo)
     const int tiles_stem = 9 * (SPLIT ? 2 : 1) * (128 / G::KT), tiles_conv = 9 * (SPLIT ? 2 : 1) * (F / G::KT);
@@ -290,17 +319,21 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
     __builtin_amdgcn_sched_barrier(0);
 
     // position of the lane in block pt: p = pbase + 16 pt + r, i.e. file r & 7, rank (pbase >> 3) + 2 pt + (r >> 3)
+    // (RP: file r & 7, rank = slot pt or 7 - pt for every lane of the block; ABOARD and 8 AROW are both 0 mod 256
+    // bytes, so a lane group reads and writes the bank residues of the board tiles)
     const int px = r & 7, py0 = (pbase >> 3) + (r >> 3);
-    const int base0 = lds_base + board * G::ABOARD + (pbase + r) * G::AROW + q * 16;   // block 0's own row
+    const int base0 = lds_base + board * G::ABOARD + pos0 * G::AROW + q * 16;   // block 0's own row
     const int zero_q = lds_base + G::ZERO_OFF + q * 16;
-    const int act_row0 = board * G::ABOARD + (pbase + r) * G::AROW;    // the lane's row in block 0
+    const int act_row0 = board * G::ABOARD + pos0 * G::AROW;           // the lane's row in block 0
+    const int row_step = pstep * G::AROW;               // bytes from a block's row to the next block's
     // which lanes have an on-board neighbour to the left / right, and (per block) above / below
+    // (RP: above / below is a property of the whole block -- it is computed or skipped, never masked)
     const unsigned long long xm_left = __ballot(px >= 1), xm_right = __ballot(px <= 6);
     unsigned long long ym_up[PT], ym_down[PT];
 #pragma unroll
     for (int pt = 0; pt < PT; pt++) {
-        ym_up[pt] = __ballot(py0 + 2 * pt >= 1);
-        ym_down[pt] = __ballot(py0 + 2 * pt <= 6);
+        ym_up[pt] = RP ? ~0ull : __ballot(py0 + 2 * pt >= 1);
+        ym_down[pt] = RP ? ~0ull : __ballot(py0 + 2 * pt <= 6);
     }
     // Weight fragment address: row o = obase + 16 ct + r of a tile plane, quarter q.  The swizzle
     // (-(o >> 2)) & 3 does not depend on ct (16 ct >> 2 is a multiple of 4), so ONE per-lane address
@@ -349,16 +382,21 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         // TWO MFMA sub-steps, first against the hi half of the activation rows, then against the lo
         // half LO_OFF bytes further -- the products hi.Whi and lo.Whi share one pass of Whi through the
         // ring and one set of weight fragment reads.  NS counts MFMA sub-steps, NS / DUP weight sub-steps.
-        auto run_tap = [&](auto NSC, auto DUPC, bool first_tap, bool last_tap) {
+        // SK / NSK (rank tiles): block 0 of this tap / of the next tap is off the board as a whole.  Its
+        // fragment xa[0] is not read and its CT MFMAs are not issued; every lgkmcnt immediate below counts the
+        // reads that are really issued (xb is always HP reads, the next xa HP - its skip).
+        auto run_tap = [&](auto NSC, auto DUPC, bool first_tap, bool last_tap, auto SKC, auto NSKC) {
             constexpr int NS = decltype(NSC)::value, DUP = decltype(DUPC)::value;
+            constexpr int SK = decltype(SKC)::value ? 1 : 0, NSK = decltype(NSKC)::value ? 1 : 0;
+            static_assert(RP || (SK == 0 && NSK == 0), "whole blocks leave the board only with rank tiles");
             static_assert(DUP == 1 || (SPLIT && DUP == 2 && ALT != 8), "shared weight sub-steps belong to the split kernels");
             const int t_tap0 = t;
-            auto fetch_xa = [&](auto IC, bool next_tap) {
+            auto fetch_xa = [&](auto IC, bool next_tap, auto SC) {
                 constexpr int i = decltype(IC)::value;
                 if constexpr (ALT == 7) return;
                 if constexpr (ALT == 6) { if (t > 1) return; }       // timing only: no fragment reads
 #pragma unroll
-                for (int pt = 0; pt < HP; pt++)
+                for (int pt = decltype(SC)::value; pt < HP; pt++)
                     xa[pt] = lds_read16_asm<(i / DUP) * 64 + (i % DUP) * G::LO_OFF>(ab[next_tap ? 1 : 0][pt]);
             };
             auto fetch_xb = [&](auto IC) {
@@ -395,7 +433,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 static_for<0, CT>([&](auto CC) { fetch_w1(IC, CC, next_tap, dst); });
             };
             if (first_tap) {
-                fetch_xa(std::integral_constant<int, 0>{}, false);
+                fetch_xa(std::integral_constant<int, 0>{}, false, std::integral_constant<int, SK>{});
                 fetch_w(std::integral_constant<int, 0>{}, false, w[0]);
             }
             static_for<0, NS>([&](auto IC) {
@@ -456,7 +494,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (ALT != 7) {
 #pragma unroll
-                for (int pt = 0; pt < HP; pt++)
+                for (int pt = SK; pt < HP; pt++)
 #pragma unroll
                     for (int ct = 0; ct < CT; ct++)
                         acc[pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xa[pt], acc[pt][ct], 0, 0, 0);
@@ -473,11 +511,11 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     // clumped schedule of round 2; same MFMA order, bit-identical results)
                     if (!wrap || !last_tap) {
                         issued = true;
-                        if constexpr (wrap) fetch_xa(std::integral_constant<int, 0>{}, true);
-                        else fetch_xa(std::integral_constant<int, i + 1>{}, false);
+                        if constexpr (wrap) fetch_xa(std::integral_constant<int, 0>{}, true, std::integral_constant<int, NSK>{});
+                        else fetch_xa(std::integral_constant<int, i + 1>{}, false, std::integral_constant<int, SK>{});
                     }
                     if (!issued) wait_lgkm<0>();
-                    else wait_lgkm<HP>();                // xb has landed
+                    else wait_lgkm<HP - (wrap ? NSK : SK)>();            // xb has landed
                     __builtin_amdgcn_sched_barrier(0);
                     static_for<0, HP * CT>([&](auto KC) {
                         constexpr int k = decltype(KC)::value, pt = k / CT, ct = k % CT;
@@ -496,10 +534,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 if (!wrap || !last_tap) {
                     issued = true;
                     if constexpr (wrap) {
-                        fetch_xa(std::integral_constant<int, 0>{}, true);
+                        fetch_xa(std::integral_constant<int, 0>{}, true, std::integral_constant<int, 0>{});
                         fetch_w(std::integral_constant<int, 0>{}, true, w[nxt]);
                     } else {
-                        fetch_xa(std::integral_constant<int, i + 1>{}, false);
+                        fetch_xa(std::integral_constant<int, i + 1>{}, false, std::integral_constant<int, 0>{});
                         fetch_w(std::integral_constant<int, wi + 1>{}, false, w[nxt]);
                     }
                 }
@@ -535,6 +573,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         // (8 dy + dx) rows when that neighbour is on the board, else the zero row whose index has
         // the same residue mod 16 (same banks).  The zero-row address and the file test do not
         // depend on pt: per block only the rank test and one select remain.
+        int base0_tap = base0, r_tap = r;               // (RP: per tap, see there)
         auto vtap_rows = [&](int v, int (&dst)[PT]) {
             int tap, choff;
             if constexpr (SPLIT) {
@@ -549,15 +588,15 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             }
             const int dy = tap / 3 - 1, dx = tap % 3 - 1;
             const int shift = 8 * dy + dx;
-            const int zrow = zero_q + ((r + shift) & 15) * G::ZSTRIDE + choff;
-            const int inb = base0 + shift * G::AROW + choff;
+            const int zrow = zero_q + ((r_tap + shift) & 15) * G::ZSTRIDE + choff;
+            const int inb = base0_tap + shift * G::AROW + choff;
             // on-board tests as wave masks in SGPRs (computed once per kernel): per block only a
             // scalar AND, one add and one select remain
             const unsigned long long xm = dx < 0 ? xm_left : (dx > 0 ? xm_right : ~0ull);
 #pragma unroll
             for (int pt = 0; pt < PT; pt++) {
                 const unsigned long long m = xm & (dy < 0 ? ym_up[pt] : (dy > 0 ? ym_down[pt] : ~0ull));
-                const int row = inb + pt * 16 * G::AROW;
+                const int row = inb + pt * row_step;
                 asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(dst[pt]) : "v"(zrow), "v"(row), "s"(m));
             }
         };
@@ -637,7 +676,41 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 slot_tap += GK;
                 slot_tap = slot_tap >= GR ? slot_tap - GR : slot_tap;
             }
+        } else if constexpr (RP) {
+            // The nine taps as straight-line code, once per rank half: half 0 skips block 0 in taps 0-2 (dy = -1),
+            // half 1 in taps 6-8 (dy = +1).  Whether a tap and its successor skip is then a compile-time property
+            // of every body (SK, NSK), the prefetch across the tap boundary stays, and no fragment read is in flight
+            // across a join or a back-edge: the two halves meet again behind the last tap's lgkmcnt(0).
+            constexpr std::integral_constant<int, 1> once{};
+            auto run_conv = [&](auto HC) {
+                constexpr int hh = decltype(HC)::value;
+                // (the lane's row and file as values the compiler cannot see through, anew for every tap: the row
+                // addresses are constants of the kernel, and with the tap a compile-time number hipcc would
+                // otherwise compute them all once, ahead of the layer loop, and spill)
+                auto fresh = [&] {
+                    base0_tap = base0;
+                    r_tap = r;
+                    asm volatile("" : "+v"(base0_tap), "+v"(r_tap));
+                };
+                fresh();
+                vtap_rows(0, ab[1]);
+                static_for<0, 9>([&](auto VC) {
+                    constexpr int v = decltype(VC)::value;
+                    constexpr bool sk = hh == 0 ? v < 3 : v >= 6;
+                    constexpr bool nsk = v + 1 < 9 && (hh == 0 ? v + 1 < 3 : v + 1 >= 6);
+#pragma unroll
+                    for (int pt = 0; pt < PT; pt++) ab[0][pt] = ab[1][pt];
+                    fresh();
+                    vtap_rows(v + 1 < 9 ? v + 1 : 0, ab[1]);
+                    run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == 8, std::integral_constant<bool, sk>{},
+                            std::integral_constant<bool, nsk>{});
+                    slot_tap = slot_add(slot_tap, 4 / G::SPT);
+                });
+            };
+            if (rp_half == 0) run_conv(std::integral_constant<int, 0>{});
+            else run_conv(std::integral_constant<int, 1>{});
         } else {
+        constexpr std::false_type nsk{};
         vtap_rows(0, ab[1]);
         for (int v = 0; v < nv; v++) {
 #pragma unroll
@@ -648,13 +721,13 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 constexpr std::integral_constant<int, 2> twice{};
                 const bool whi = ((v % per_tap) >> hshift) == 0;         // part 0
                 if (conv != 0 && whi) {                                  // Whi against hi and lo
-                    if (F == 64) run_tap(std::integral_constant<int, 4>{}, twice, v == 0, v == nv - 1);
-                    else run_tap(std::integral_constant<int, 8>{}, twice, v == 0, v == nv - 1);
-                } else if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1);
-                else run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == nv - 1);
+                    if (F == 64) run_tap(std::integral_constant<int, 4>{}, twice, v == 0, v == nv - 1, nsk, nsk);
+                    else run_tap(std::integral_constant<int, 8>{}, twice, v == 0, v == nv - 1, nsk, nsk);
+                } else if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1, nsk, nsk);
+                else run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == nv - 1, nsk, nsk);
             } else
-            if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1);
-            else run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == nv - 1);
+            if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1, nsk, nsk);
+            else run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == nv - 1, nsk, nsk);
             if constexpr (PAIR) slot_tap = slot_add(slot_tap, 4 / G::SPT);
             // The fragments prefetched for the next tap are in flight across this loop's back-edge, where
             // hipcc -- which cannot see the inline-asm reads -- is free to COPY their registers (phi moves)
@@ -680,7 +753,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         // channel blocks 2g, 2g+1 of a position block: 8 consecutive channels per lane, one 16-byte write
         auto store_pair = [&](int pt, int g, const half4 &lo, const half4 &hi) {
             *reinterpret_cast<__attribute__((address_space(3))) half8 *>(
-                lds + act_row0 + pt * 16 * G::AROW + (obase + 32 * g + 8 * q) * 2) =
+                lds + act_row0 + pt * row_step + (obase + 32 * g + 8 * q) * 2) =
                 half8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         };
         const half4 zero4 = {(_Float16)0, (_Float16)0, (_Float16)0, (_Float16)0};
@@ -694,7 +767,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 lo8[j] = (_Float16)(a[j] - (float)hi8[j]);
                 lo8[4 + j] = (_Float16)(b[j] - (float)hi8[4 + j]);
             }
-            lds_byte *dst = lds + act_row0 + pt * 16 * G::AROW + (obase + 32 * g + 8 * q) * 2;
+            lds_byte *dst = lds + act_row0 + pt * row_step + (obase + 32 * g + 8 * q) * 2;
             *reinterpret_cast<__attribute__((address_space(3))) half8 *>(dst) = hi8;
             *reinterpret_cast<__attribute__((address_space(3))) half8 *>(dst + G::LO_OFF) = lo8;
         };
@@ -791,7 +864,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
     if (!IDX && out) {
 #pragma unroll
         for (int pt = 0; pt < PT; pt++) {
-            const int p = pbase + 16 * pt + r;
+            const int p = pos0 + pstep * pt;
 #pragma unroll
             for (int ct = 0; ct < CT; ct++) {
                 const int o0 = obase + G::chan_of(ct, 0) + 8 * q;
@@ -829,7 +902,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         for (int pt = 0; pt < PT; pt++)
 #pragma unroll
             for (int k = 0; k < 3; k++)
-                scratch[(((board * 64 + pbase + 16 * pt + r) * 3) + k) * NC + (obase / (16 * CT)) * 4 + q] = part[pt][k];
+                scratch[(((board * 64 + pos0 + pstep * pt) * 3) + k) * NC + (obase / (16 * CT)) * 4 + q] = part[pt][k];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         for (int i = tid; i < G::NB * 64 * 3; i += 512) {

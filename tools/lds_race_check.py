@@ -22,6 +22,10 @@ wait that retires it).  Reported:
      (exact on the executed path: no path-feasibility guesswork);
   4. an address or branch that depends on an unknown value (the emulation would be meaningless).
 
+The statistics printed per kernel count what was executed: instructions, barrier epochs, DMA transfers, LDS reads and
+writes and "mfma", the MFMA wave-instructions of the 8 waves (a 128-filter wave tile issues 576 per convolution, 528
+with the rank tiles that skip off-board blocks; tests/test_trunk_rank_tiles_cpu.py holds the kernels to that).
+
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -S --offload-device-only \\
           chessrl_amd/csrc/api.hip -o api.s ;  python tools/lds_race_check.py api.s [n_blocks=2] [kernel filter]
 """
@@ -147,6 +151,8 @@ class Wave(object):
         self.lgkm = []                            # outstanding LGKM ops: (dest registers frozenset or empty, text)
         self.findings = []
         self.n_exec = 0
+        self.n_mfma = 0                           # MFMA wave-instructions executed
+        self.asm_reads = []                       # lowest LDS byte of every inline-asm (fragment) ds_read
 
     # ---- register access -------------------------------------------------------------------------
     def exec_mask(self):
@@ -498,6 +504,8 @@ class Wave(object):
                 sz = {"ds_read_b128": 16, "ds_read_b64": 8, "ds_read_b32": 4, "ds_read_u16": 2, "ds_read_u8": 1}[op]
                 self.events.append(["read", self.epoch, self.lds_bytes(addr + U32(off), sz), text])
             self.vunknown(t[0])
+            if in_asm:
+                self.asm_reads.append(int(self.events[-1][2].min()))
             self.lgkm.append((frozenset(range(d[0], d[0] + d[1])) if in_asm else frozenset(), text))
         elif op in ("ds_write_b128", "ds_write_b64", "ds_write_b32", "ds_write_b16", "ds_write_b8", "ds_write2_b32", "ds_write2_b64"):
             addr, known = self.vsrc(t[0])
@@ -646,7 +654,8 @@ class Wave(object):
                 raise EmuError("sdwa dst_sel: " + text)
             self.vdst(t[0], r, k)
         elif base in ("v_lshl_add_u32", "v_lshl_or_b32", "v_add3_u32", "v_or3_b32", "v_and_or_b32", "v_mad_u32_u24",
-                      "v_bfe_u32", "v_add_lshl_u32", "v_xad_u32", "v_bitop3_b32", "v_mad_u32_u16", "v_alignbit_b32", "v_perm_b32"):
+                      "v_bfe_u32", "v_add_lshl_u32", "v_xad_u32", "v_bitop3_b32", "v_mad_u32_u16", "v_alignbit_b32", "v_perm_b32",
+                      "v_mad_i32_i24"):
             a, ka = src(1)
             b, kb = src(2)
             c, kc = src(3)
@@ -663,6 +672,9 @@ class Wave(object):
                 r = (a & b) | c
             elif base == "v_mad_u32_u24":
                 r = ((a & U32(0xFFFFFF)).astype(u64) * (b & U32(0xFFFFFF)).astype(u64)).astype(U32) + c
+            elif base == "v_mad_i32_i24":                            # signed 24 x 24 + 32 (a negative row step)
+                sx = lambda x: ((x & U32(0xFFFFFF)).astype(np.int64) ^ 0x800000) - 0x800000
+                r = (sx(a) * sx(b) + c.astype(np.int64)).astype(U32)
             elif base == "v_mad_u32_u16":
                 r = (a & U32(0xFFFF)) * (b & U32(0xFFFF)) + c
             elif base == "v_bfe_u32":
@@ -788,14 +800,18 @@ class Wave(object):
             if not re.match(r"v_(mfma|add_f|sub_f|mul_f|max_f|min_f|fma|mac_f|cvt|pk_|exp|log|rcp|rsq|sqrt|med3|fmac|dot|"
                             r"max3|min3|mad_f|ldexp|frexp|trunc|floor|ceil|rndne|fract|cndmask|swap|permlane|smfmac)", base):
                 raise EmuError("vector opcode %s (line %d)" % (op, self.cur_line))
+            if base.startswith(("v_mfma", "v_smfmac")):
+                self.n_mfma += 1
             for tok in t[1:]:
                 if _vreg(tok) is not None:
                     self.vsrc(tok)
             self.vunknown(t[0])
 
 
-def check_workgroup(ins, labels, n_blocks, lds_bytes=160 * 1024, want_out=False, listed=None, kernarg=None):
-    """Emulate the 8 waves of workgroup 0 and cross-check their LDS traffic epoch by epoch."""
+def check_workgroup(ins, labels, n_blocks, lds_bytes=160 * 1024, want_out=False, listed=None, kernarg=None, ring_at=None):
+    """Emulate the 8 waves of workgroup 0 and cross-check their LDS traffic epoch by epoch.
+    ``ring_at``: LDS offset of the weight ring; the statistics then also count, per wave, the fragment reads
+    (inline-asm ds_read) below it (activation and zero rows) and at or above it (weight tiles)."""
     waves = [Wave(ins, labels, w, n_blocks, want_out=want_out, listed=listed, kernarg=kernarg).run() for w in range(8)]
     findings = []
     for w in waves:
@@ -857,7 +873,12 @@ def check_workgroup(ins, labels, n_blocks, lds_bytes=160 * 1024, want_out=False,
                     findings.append("epoch %d: %s (%d bytes, first at LDS offset 0x%x)" % (ep, name, int(mask.sum()), lo))
     stats = {"instructions": sum(w.n_exec for w in waves), "epochs": n_epochs, "dma_transfers": dma_total,
              "lds_reads": sum(1 for w in waves for e in w.events if e[0] == "read"),
-             "lds_writes": sum(1 for w in waves for e in w.events if e[0] == "write")}
+             "lds_writes": sum(1 for w in waves for e in w.events if e[0] == "write"),
+             "mfma": sum(w.n_mfma for w in waves)}
+    if ring_at is not None:
+        stats["mfma_per_wave"] = [w.n_mfma for w in waves]
+        stats["act_frag_reads_per_wave"] = [sum(1 for a in w.asm_reads if a < ring_at) for w in waves]
+        stats["w_frag_reads_per_wave"] = [sum(1 for a in w.asm_reads if a >= ring_at) for w in waves]
     return findings, stats
 
 

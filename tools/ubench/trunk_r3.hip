@@ -7,8 +7,13 @@
 // (A third variant was measured with this harness and removed again: warming each XCD's L2 for the weight
 // tiles 8 / 16 tiles ahead, 1/32 of the lines per workgroup through 4-byte LDS-DMAs: +1.0 ... +1.5 % SLOWER
 // at both sizes -- profiles/r03/trunk_r3_l2_prefetch.log.  The L2 -> LDS stream is not waiting for the fabric.)
+// Round 7: the rank tiles of the 128-filter NB = 4 kernel (tower_x16.hpp, CRL_TRUNK_RANKPAIR).  The default build
+// times them; -DCRL_TRUNK_RANKPAIR=0 builds the board tiles of before into a second binary.  Alternate the two
+// binaries in ONE run on ONE device (MATCH selects rows by name): devices differ by up to 12 % on MFMA loops.
+// ALT 7 and ALT 8 were written for the board tiles and keep them in both builds.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I chessrl_amd/csrc tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3
-//   ./trunk_r3 [boards=4096] [reps=20]
+// hipcc ... -DCRL_TRUNK_RANKPAIR=0 tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3_boards
+//   [MATCH="x16<128,4> pair (production)"] ./trunk_r3 [boards=4096] [reps=20]
 #define CRL_HARNESS 1
 #include "tower_x16.hpp"
 #include <cmath>
@@ -86,7 +91,8 @@ int main(int argc, char **argv)
     std::vector<float> ref, out;
     for (int rep = 0; rep < 2; rep++) {
         Bufs b = make(128, 10, boards, 1);
-        printf("== 10 x 128, %d boards (pass %d)\n", boards, rep);
+        printf("== 10 x 128, %d boards (pass %d), production = %s tiles\n", boards, rep,
+               RankTiles<128, 4, 0, 1, 0, 0, 0>::value ? "rank" : "board");
         const int lds = Geo16<128, 4>::lds_bytes(5);
         run("x16<128,4> pair (production)", k_trunk_x16<128, 4, 1, 0, 1>, lds, 4, 128, 10, boards, reps, b, ref, nullptr);
         run("x16<128,4> pair, ALT 8 clumped w reads (r2)", k_trunk_x16<128, 4, 1, 8, 1>, lds, 4, 128, 10, boards, reps, b, out, &ref);
