@@ -1066,7 +1066,7 @@ static int trunk_forward(void *hip_stream, int filters, const void *dev_planes_f
     if (filters == F_ && pk.nb == NB_ && pk.pair == PAIR_ && pk.group == GROUP_ && split == (SPLIT_ != 0)) { \
         kern = bits ? crl_tower::k_trunk_x16<F_, NB_, 1, 0, PAIR_, GROUP_, SPLIT_>               \
                     : crl_tower::k_trunk_x16<F_, NB_, 0, 0, PAIR_, GROUP_, SPLIT_>;              \
-        lds_bytes = crl_tower::Geo16<F_, NB_, SPLIT_>::lds_bytes(GROUP_ ? 9 : (PAIR_ ? 5 : crl_tower::PIPE_RING)); \
+        lds_bytes = crl_tower::Geo16<F_, NB_, SPLIT_>::lds_bytes(crl_tower::ring_slots<NB_, PAIR_, GROUP_>());    \
     }
     CRL_X16(256, 1, 1, 0, 0) CRL_X16(256, 2, 1, 0, 0)
     CRL_X16(64, 2, 0, 0, 0) CRL_X16(64, 4, 0, 1, 0)

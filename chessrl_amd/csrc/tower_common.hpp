@@ -81,12 +81,23 @@ __device__ __forceinline__ half8 lds_read16_asm(int addr)
     return v;
 }
 
+// The counted waits of the hand-written pipelines: N is an immediate of the instruction, and a count the
+// instruction cannot encode does not compile.
 template <int N> __device__ __forceinline__ void wait_vmcnt()
 {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    static_assert(N >= 0 && N <= 63, "vmcnt immediate");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// (lgkmcnt as one operand-free statement per count, not as an "n" operand: hipcc's unrolling cost counts the
+// operands of an asm statement, and with one more the nine-tap loop of the 64-filter NB = 2 kernels is no
+// longer unrolled whole -- docs/history/experiments.md, round 8)
+template <int N> __device__ __forceinline__ void wait_lgkm()
+{
+    static_assert(N >= 0 && N <= 15, "lgkmcnt immediate");
+#define CRL_LGKM(n) if constexpr (N == n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory");
+    CRL_LGKM(0) CRL_LGKM(1) CRL_LGKM(2) CRL_LGKM(3) CRL_LGKM(4) CRL_LGKM(5) CRL_LGKM(6) CRL_LGKM(7)
+    CRL_LGKM(8) CRL_LGKM(9) CRL_LGKM(10) CRL_LGKM(11) CRL_LGKM(12) CRL_LGKM(13) CRL_LGKM(14) CRL_LGKM(15)
+#undef CRL_LGKM
 }
 
 // Input given as 128 plane bitboards per board (u64 [n_boards][128]; bit sq of plane c = channel c

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_conv(const unsigned char *__re
     const int w0 = lds_base + G::WRING_OFF + (obase + r) * 64 + ((q ^ WG::wswz(obase + r)) << 4);
     const int w0hi = w0 + 4 * G::TILE;                  // (a third pair lies beyond the 16-bit offset of ds_read_b128)
 
-    wait_vmcnt_n<0>();
+    wait_vmcnt<0>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -396,18 +396,18 @@ __global__ __launch_bounds__(512, 2) void k_layer_conv(const unsigned char *__re
         // reads would invite phi copies of registers whose data has not landed, tower_x16.hpp)
         // S1
         rd_w(w[1 - P], SHI{}, I1{});
-        wait_lgkm_n<HC>();                              // x[P] and w[P] have landed
+        wait_lgkm<HC>();                              // x[P] and w[P] have landed
         __builtin_amdgcn_sched_barrier(0);
         mfma16(w[P], x[P], I0{});
         __builtin_amdgcn_sched_barrier(0);
         // S2
         rd_x(x[1 - P], ab, I1{});
-        wait_lgkm_n<PT>();                              // w[1-P] = Whi[4:8]
+        wait_lgkm<PT>();                              // w[1-P] = Whi[4:8]
         __builtin_amdgcn_sched_barrier(0);
         mfma16(w[1 - P], x[P], I1{});
         __builtin_amdgcn_sched_barrier(0);
         // S3
-        wait_lgkm_n<0>();                               // the lo rows
+        wait_lgkm<0>();                               // the lo rows
         __builtin_amdgcn_sched_barrier(0);
         mfma16(w[1 - P], x[1 - P], I1{});
         __builtin_amdgcn_sched_barrier(0);
@@ -424,15 +424,15 @@ __global__ __launch_bounds__(512, 2) void k_layer_conv(const unsigned char *__re
         // S5
         rd_w(w[P], SLO{}, I0{});
         rd_x(x[1 - P], abn, I0{});
-        wait_lgkm_n<HC + PT>();                         // w[1-P] = Wlo[4:8]
+        wait_lgkm<HC + PT>();                         // w[1-P] = Wlo[4:8]
         __builtin_amdgcn_sched_barrier(0);
         mfma16(w[1 - P], x[P], I1{});
         __builtin_amdgcn_sched_barrier(0);
         // barrier: every fragment read of this tap's two planes has landed (only the next tap's x may be in flight)
-        wait_lgkm_n<PT>();
+        wait_lgkm<PT>();
 #if defined(CRL_LAYER_STAMPS)
         const unsigned long long s0 = __builtin_amdgcn_s_memtime();
-        wait_vmcnt_n<YOUNGEST>();
+        wait_vmcnt<YOUNGEST>();
         const unsigned long long s1 = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_conv(const unsigned char *__re
         st_vm += s1 - s0;
         st_sb += s2 - s1;
 #else
-        wait_vmcnt_n<YOUNGEST>();
+        wait_vmcnt<YOUNGEST>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
 #endif
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_conv(const unsigned char *__re
         });
         // the reads in flight across the back-edge are drained: hipcc cannot see them and is free to copy their registers
         // there (phi moves) before the data has landed (tower_x16.hpp, tools/check_asm_hazards.py)
-        wait_lgkm_n<0>();
+        wait_lgkm<0>();
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #if CRL_LAYER_ASM_MFMA

@@ -91,43 +91,31 @@ struct Geo16 {
     }
 };
 
-// stage weight tile t (global image = the plane image above, contiguous) into ring slot t & 3.
-// (ALT 2: in-kernel cycle stamps; ALT 3, 4, 5, 6, 7: timing-only builds without the weight staging, without
-// the per-tile barrier, without both, without the fragment reads from LDS, with NOTHING BUT the weight
-// staging, barriers and epilogues (no fragment reads, no MFMAs) -- harness diagnostics, WRONG
-// results, never dispatched.  ALT 8: correct results, round 2's schedule: the weight-fragment reads of the
-// next sub-step issued in one clump before the MFMAs of half 1 instead of one by one between them.)
-// ALT = 0: every wave moves GL pieces of 1 KiB.  ALT = 1: the tile is moved by ONE half of the
-// workgroup -- waves 0-3 move even tiles, waves 4-7 odd tiles, 2 GL pieces each -- so that of the
-// two waves sharing a SIMD only one sits in the LDS-DMA issue queue after a barrier while the other
-// goes straight back to its MFMAs.
-template <class G, int ALT>
+// Slots of the weight ring: 4 in the plain ring, 5 with pair publishing, with the group pipeline 3 groups of 3
+// tiles (4 groups at two boards per workgroup).  The kernel's LDS budget and every launch take it from here.
+constexpr int GROUP_TAPS = 3;                           // group pipeline: taps (= weight tiles) per barrier
+template <int NB, int PAIR, int GROUP>
+constexpr int ring_slots()
+{
+    return GROUP ? GROUP_TAPS * (NB == 2 ? 4 : 3) : (PAIR ? 5 : PIPE_RING);
+}
+
+// stage weight tile t (global image = the plane image above, contiguous) into ring slot `slot`, or t & 3
+// when none is given (the plain ring): every wave moves GL pieces of 1 KiB.
+template <class G>
 __device__ inline void stage_wtile_x16(const unsigned char *wts, lds_byte *lds, int t, int tid, int wave_u,
                                        int slot = -1)
 {
     const unsigned char *src = wts + (size_t)t * G::TILE_BYTES;
     const int slot0 = G::WRING_OFF + (slot < 0 ? (t & (PIPE_RING - 1)) : slot) * G::TILE_BYTES;
-    if constexpr (ALT == 1) {
-        if ((wave_u >> 2) != (t & 1)) return;
-        const int dst0 = slot0 + (wave_u & 3) * 1024;   // uniform
+    const int dst0 = slot0 + wave_u * 1024;             // uniform
 #pragma unroll
-        for (int j = 0; j < 2 * G::GL; j++) {
-            const int idx = j * 256 + (tid & 255);      // 16-byte slot of the tile image (global = LDS order)
-            const unsigned off = (unsigned)(idx * 16);
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(src + off),
-                (__attribute__((address_space(3))) void *)(lds + dst0 + j * 4096), 16, 0, 0);
-        }
-    } else {
-        const int dst0 = slot0 + wave_u * 1024;         // uniform
-#pragma unroll
-        for (int j = 0; j < G::GL; j++) {
-            const int idx = j * 512 + tid;              // 16-byte slot of the tile image (global = LDS order)
-            const unsigned off = (unsigned)(idx * 16);
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(src + off),
-                (__attribute__((address_space(3))) void *)(lds + dst0 + j * 8192), 16, 0, 0);
-        }
+    for (int j = 0; j < G::GL; j++) {
+        const int idx = j * 512 + tid;                  // 16-byte slot of the tile image (global = LDS order)
+        const unsigned off = (unsigned)(idx * 16);
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void *)(src + off),
+            (__attribute__((address_space(3))) void *)(lds + dst0 + j * 8192), 16, 0, 0);
     }
 }
 
@@ -159,35 +147,11 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 #ifndef CRL_TRUNK_RANKPAIR
 #define CRL_TRUNK_RANKPAIR 1
 #endif
-template <int F, int NB, int ALT, int PAIR, int GROUP, int SPLIT, int IDX>
+template <int F, int NB, int PAIR, int GROUP, int SPLIT, int IDX>
 struct RankTiles {
     static constexpr bool value = CRL_TRUNK_RANKPAIR != 0 && F == 128 && NB == 4 && PAIR == 1 && GROUP == 0 &&
-                                  SPLIT == 0 && IDX == 0 && (ALT == 0 || ALT == 2);
+                                  SPLIT == 0 && IDX == 0;
 };
-
-template <int N> __device__ __forceinline__ void wait_vmcnt_n()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_lgkm_n()
-{
-    static_assert(N >= 0 && N < 16, "lgkmcnt immediate");
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int N> __device__ __forceinline__ void wait_lgkm()
-{
-    static_assert(N >= 0 && N <= 8 && N != 7, "lgkmcnt immediate");
-    if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt lgkmcnt(5)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-}
 
 //   planes  fp16 [n_boards][64][128], or 128 plane bitboards per board (BITS)
 //   wts     fp16 weight planes in consumption order [conv][tap][in-ch/32][F rows][4 chunks][8 in],
@@ -222,11 +186,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                                                        const float *__restrict__ head_b,
                                                        float *__restrict__ head_out)
 {
-#if !defined(CRL_HARNESS)
-    static_assert(ALT == 0, "diagnostic variants are for the harnesses under tools/ubench/ only");
-#endif
+    // ALT selected diagnostic variants until round 7; the slot stays so that every kernel keeps its mangled name
+    static_assert(ALT == 0, "reserved");
     typedef Geo16<F, NB, SPLIT> G;
-    static_assert(!SPLIT || (!GROUP && (ALT == 0 || ALT == 2)), "split precision runs the plain / pair pipelines");
+    static_assert(!SPLIT || !GROUP, "split precision runs the plain / pair pipelines");
     constexpr int PT = G::PT, CT = G::CT;
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds_raw[];
     lds_byte *lds = (lds_byte *)lds_raw;
@@ -242,11 +205,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
     // its second.  The upper half enumerates its ranks in reverse -- slot s = rank s for half 0, rank 7 - s for
     // half 1 -- so that the block that leaves the board is slot 0 for both: rank 0 under dy = -1, rank 7 under
     // dy = +1.  Waves w and w + 4 are the two waves of one SIMD (waves go to the four SIMDs round robin; the
-    // stage_wtile_x16 ALT 1 experiment above and the requesting halves of csrc/tower_layer.hpp rest on the same
-    // assignment): same pair and channel group, opposite rank halves, so in each of the six dy != 0 taps every
-    // SIMD has exactly one wave that skips -- 112 MFMAs per tap and SIMD instead of 128 -- and no wave waits
-    // at the tap's barrier for a partner with more work.
-    constexpr bool RP = RankTiles<F, NB, ALT, PAIR, GROUP, SPLIT, IDX>::value;
+    // requesting halves of csrc/tower_layer.hpp rest on the same assignment): same pair and channel group,
+    // opposite rank halves, so in each of the six dy != 0 taps every SIMD has exactly one wave that skips -- 112
+    // MFMAs per tap and SIMD instead of 128 -- and no wave waits at the tap's barrier for a partner with more work.
+    constexpr bool RP = RankTiles<F, NB, PAIR, GROUP, SPLIT, IDX>::value;
     const int rp_half = wave_u >> 2;                    // RP: 0 = ranks 0-3 (slot = rank), 1 = ranks 7-4
     const int board = RP ? 2 * ((wave >> 1) & 1) + (r >> 3) : board_w;           // RP: per lane
     // position of the lane in block 0 and the step to the next block, in positions (= activation rows)
@@ -259,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
     const size_t wg_board0 = (size_t)blockIdx.x * G::NB;
     int rows[G::NB];                                    // IDX: the listed boards this workgroup holds (wave-uniform)
     if constexpr (IDX) {
-        static_assert(BITS == 1 && ALT == 0, "the indexed launch reads plane bitboards");
+        static_assert(BITS == 1, "the indexed launch reads plane bitboards");
         const int *list = reinterpret_cast<const int *>(out);
         const int listed = __builtin_amdgcn_readfirstlane(list[0]);
         if ((int)wg_board0 >= listed) return;           // before any DMA or barrier: the whole workgroup leaves
@@ -270,23 +232,22 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         }
     }
 
-    static_assert(!PAIR || ((F == 128 || F == 256) && (ALT == 0 || ALT == 2 || ALT == 7 || ALT == 8)), "pair publishing: even tile counts per layer");
-    static_assert(!SPLIT || ALT != 8, "the split-precision kernels run the production schedule");
-    constexpr int GK = 3;                               // GROUP: taps (= tiles) per barrier
-    constexpr int GRG = NB == 2 ? 4 : 3;                // GROUP: groups in the weight ring
-    constexpr int GR = GK * GRG;                        // GROUP: ring slots
-    static_assert(G::lds_bytes(GROUP ? GR : (PAIR ? 5 : PIPE_RING)) <= 160 * 1024, "LDS budget");
-    static_assert(!GROUP || (F == 64 && !PAIR && (ALT == 0 || ALT == 2) && G::SPT == 2 && G::GL == 1 &&
-                             2 * (PT + CT) < 16), "group pipeline: 64 filters");
+    static_assert(!PAIR || F == 128 || F == 256, "pair publishing: even tile counts per layer");
+    constexpr int GK = GROUP_TAPS;                      // GROUP: taps (= tiles) per barrier
+    constexpr int GR = ring_slots<NB, PAIR, GROUP>();   // ring slots
+    constexpr int GRG = GR / GK;                        // GROUP: groups in the weight ring
+    static_assert(G::lds_bytes(GR) <= 160 * 1024, "LDS budget");
+    static_assert(!GROUP || (F == 64 && !PAIR && G::SPT == 2 && G::GL == 1 && 2 * (PT + CT) < 16),
+                  "group pipeline: 64 filters");
     stage_bias_x16<G, F>(bias, lds, 0, lane, wave_u);   // oldest transfer: landed when tile 0 has
     if constexpr (GROUP) {
 #pragma unroll
-        for (int k = 0; k < GK * (GRG - 1); k++) stage_wtile_x16<G, 0>(wts, lds, k, tid, wave_u, k);   // groups 0 .. GRG-2
+        for (int k = 0; k < GK * (GRG - 1); k++) stage_wtile_x16<G>(wts, lds, k, tid, wave_u, k);   // groups 0 .. GRG-2
     } else {
-        stage_wtile_x16<G, ALT>(wts, lds, 0, tid, wave_u, PAIR ? 0 : -1);
-        stage_wtile_x16<G, ALT>(wts, lds, 1, tid, wave_u, PAIR ? 1 : -1);
-        stage_wtile_x16<G, ALT>(wts, lds, 2, tid, wave_u, PAIR ? 2 : -1);
-        if constexpr (PAIR) stage_wtile_x16<G, ALT>(wts, lds, 3, tid, wave_u, 3);
+        stage_wtile_x16<G>(wts, lds, 0, tid, wave_u, PAIR ? 0 : -1);
+        stage_wtile_x16<G>(wts, lds, 1, tid, wave_u, PAIR ? 1 : -1);
+        stage_wtile_x16<G>(wts, lds, 2, tid, wave_u, PAIR ? 2 : -1);
+        if constexpr (PAIR) stage_wtile_x16<G>(wts, lds, 3, tid, wave_u, 3);
     }
 
     {   // planes (128 channels = 16 chunks per position) -> padded LDS rows; zero rows
@@ -309,12 +270,11 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             *reinterpret_cast<__attribute__((address_space(3))) u32x4 *>(lds + G::ZERO_OFF + i * 16) =
                 u32x4{0u, 0u, 0u, 0u};
     }
-    // tile 0 landed (tiles 1,2 may be in flight).  ALT: waves 0-3 moved tiles 0 and 2, waves 4-7 tile 1.
+    // tile 0 landed (tiles 1,2 may be in flight).
     // PAIR: tiles 0 AND 1 landed (1 is first read before the first sync), 2 and 3 in flight
-    if constexpr (GROUP) wait_vmcnt_n<GK * (GRG - 2)>();              // group 0 landed, groups 1 .. GRG-2 in flight
-    else if constexpr (ALT == 1) { if (wave_u < 4) wait_vmcnt<2 * G::GL>(); }
+    if constexpr (GROUP) wait_vmcnt<GK * (GRG - 2)>();              // group 0 landed, groups 1 .. GRG-2 in flight
     else wait_vmcnt<2 * G::GL>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
@@ -350,9 +310,6 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
 
     constexpr int HP = PT / 2;                          // position blocks per half sub-step
 
-    constexpr bool STAMP = ALT == 2;                    // harness diagnostic: in-kernel cycle stamps
-    unsigned long long t_loop = 0, t_epi = 0, t_begin = 0, t_mark = 0, t_ba = 0, t_wr = 0, t_vm = 0, t_sb = 0;
-    if constexpr (STAMP) { t_begin = __builtin_amdgcn_s_memtime(); t_mark = t_begin; }
     int t = 0;                                          // tile of the K-step being computed
     int slot_tap = 0;                                   // PAIR: ring slot (t mod 5) of the tap's first tile
     auto slot_add = [](int s, int k) { const int x = s + k; return x >= 5 ? x - 5 : x; };
@@ -389,20 +346,16 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             constexpr int NS = decltype(NSC)::value, DUP = decltype(DUPC)::value;
             constexpr int SK = decltype(SKC)::value ? 1 : 0, NSK = decltype(NSKC)::value ? 1 : 0;
             static_assert(RP || (SK == 0 && NSK == 0), "whole blocks leave the board only with rank tiles");
-            static_assert(DUP == 1 || (SPLIT && DUP == 2 && ALT != 8), "shared weight sub-steps belong to the split kernels");
+            static_assert(DUP == 1 || (SPLIT && DUP == 2), "shared weight sub-steps belong to the split kernels");
             const int t_tap0 = t;
             auto fetch_xa = [&](auto IC, bool next_tap, auto SC) {
                 constexpr int i = decltype(IC)::value;
-                if constexpr (ALT == 7) return;
-                if constexpr (ALT == 6) { if (t > 1) return; }       // timing only: no fragment reads
 #pragma unroll
                 for (int pt = decltype(SC)::value; pt < HP; pt++)
                     xa[pt] = lds_read16_asm<(i / DUP) * 64 + (i % DUP) * G::LO_OFF>(ab[next_tap ? 1 : 0][pt]);
             };
             auto fetch_xb = [&](auto IC) {
                 constexpr int i = decltype(IC)::value;
-                if constexpr (ALT == 7) return;
-                if constexpr (ALT == 6) { if (t > 1) return; }
 #pragma unroll
                 for (int pt = 0; pt < HP; pt++)
                     xb[pt] = lds_read16_asm<(i / DUP) * 64 + (i % DUP) * G::LO_OFF>(ab[0][HP + pt]);
@@ -424,8 +377,6 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             }
             auto fetch_w1 = [&](auto IC, auto CC, bool next_tap, half8 (&dst)[CT]) {     // IC: weight sub-step
                 constexpr int i = decltype(IC)::value, ct = decltype(CC)::value;
-                if constexpr (ALT == 7) return;
-                if constexpr (ALT == 6) { if (t > 1) return; }
                 constexpr int off = ct * 1024 + (i % G::SPT) * G::WPLANE + (PAIR ? 0 : (i / G::SPT) * G::TILE_BYTES);
                 dst[ct] = lds_read16_asm<off>(next_tap ? wv_nxt : wv[PAIR ? i / G::SPT : 0]);
             };
@@ -449,110 +400,68 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                         // start of the last sub-step of an odd tile t: tiles t+1, t+2 (moved at the
                         // previous sync, the only transfers in flight) are published; tiles <= t-1
                         // are dead and their slots take tiles t+3, t+4
-                        unsigned long long s0 = 0, s1 = 0;
-                        if constexpr (STAMP) s0 = __builtin_amdgcn_s_memtime();
                         wait_vmcnt<0>();
-                        if constexpr (STAMP) { s1 = __builtin_amdgcn_s_memtime(); t_vm += s1 - s0; }
                         __builtin_amdgcn_s_barrier();
                         __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (STAMP) t_sb += __builtin_amdgcn_s_memtime() - s1;
                         if (!bias_staged) {
                             bias_staged = true;
                             if (conv + 1 < n_convs) stage_bias_x16<G, F>(bias, lds, conv + 1, lane, wave_u);
                         }
                         const int slot_cur = slot_add(slot_tap, wi / G::SPT);
-                        if (t + 3 < n_tiles) stage_wtile_x16<G, 0>(wts, lds, t + 3, tid, wave_u, slot_add(slot_cur, 3));
-                        if (t + 4 < n_tiles) stage_wtile_x16<G, 0>(wts, lds, t + 4, tid, wave_u, slot_add(slot_cur, 4));
+                        if (t + 3 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 3, tid, wave_u, slot_add(slot_cur, 3));
+                        if (t + 4 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 4, tid, wave_u, slot_add(slot_cur, 4));
                     }
                 } else if constexpr (s == G::SPT - 1) {
                     // publish tile t+1 before the half that prefetches its first fragments;
                     // recycle tile t-1's slot
-                    unsigned long long s0 = 0, s1 = 0;
-                    if constexpr (STAMP) s0 = __builtin_amdgcn_s_memtime();
-                    if constexpr (ALT == 1) {
-                        // tile t+1 was moved by the half with (t+1) & 1, three syncs ago, and is
-                        // the only transfer that half has in flight
-                        if ((wave_u >> 2) == ((t + 1) & 1)) wait_vmcnt<0>();
-                    } else if constexpr (ALT < 3) {
-                        if (t + 2 < n_tiles) wait_vmcnt<G::GL>();
-                        else wait_vmcnt<0>();
-                    }
-                    if constexpr (STAMP) { s1 = __builtin_amdgcn_s_memtime(); t_vm += s1 - s0; }
-                    if constexpr (ALT != 4 && ALT != 5) __builtin_amdgcn_s_barrier();   // 4, 5: timing only
+                    if (t + 2 < n_tiles) wait_vmcnt<G::GL>();
+                    else wait_vmcnt<0>();
+                    __builtin_amdgcn_s_barrier();
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (STAMP) t_sb += __builtin_amdgcn_s_memtime() - s1;
                     if (!bias_staged) {
                         bias_staged = true;
                         if (conv + 1 < n_convs) stage_bias_x16<G, F>(bias, lds, conv + 1, lane, wave_u);
                     }
-                    if constexpr (ALT != 3 && ALT != 5)                                  // 3, 5: timing only
-                        if (t + 3 < n_tiles) stage_wtile_x16<G, ALT>(wts, lds, t + 3, tid, wave_u);
+                    if (t + 3 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 3, tid, wave_u);
                 }
                 // ---- half 0: position blocks [0, HP)
                 fetch_xb(IC);
                 wait_lgkm<HP>();                         // xa and w[cur] have landed
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ALT != 7) {
 #pragma unroll
                 for (int pt = SK; pt < HP; pt++)
 #pragma unroll
                     for (int ct = 0; ct < CT; ct++)
                         acc[pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xa[pt], acc[pt][ct], 0, 0, 0);
-                }
                 __builtin_amdgcn_sched_barrier(0);
                 // ---- half 1: position blocks [HP, PT); prefetch the next sub-step
                 constexpr bool wrap = i + 1 >= NS;
                 bool issued = false;
-                if constexpr (ALT != 8 && ALT != 7) {
-                    // the next sub-step's activation fragments before the wait; its CT weight fragments
-                    // one by one behind the first CT MFMAs of this half: a wave that issues all HP + CT
-                    // reads in one clump keeps its MFMAs waiting behind 6 KiB of LDS transfers, -1.1 ..
-                    // -1.6 % of kernel time at 128 and 256 filters (tools/ubench/trunk_r3.hip; ALT 8 = the
-                    // clumped schedule of round 2; same MFMA order, bit-identical results)
-                    if (!wrap || !last_tap) {
-                        issued = true;
-                        if constexpr (wrap) fetch_xa(std::integral_constant<int, 0>{}, true, std::integral_constant<int, NSK>{});
-                        else fetch_xa(std::integral_constant<int, i + 1>{}, false, std::integral_constant<int, SK>{});
-                    }
-                    if (!issued) wait_lgkm<0>();
-                    else wait_lgkm<HP - (wrap ? NSK : SK)>();            // xb has landed
-                    __builtin_amdgcn_sched_barrier(0);
-                    static_for<0, HP * CT>([&](auto KC) {
-                        constexpr int k = decltype(KC)::value, pt = k / CT, ct = k % CT;
-                        acc[HP + pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xb[pt], acc[HP + pt][ct], 0, 0, 0);
-                        if constexpr (k < CT && w_last) {                 // the next MFMA sub-step has new weights
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (issued) {
-                                if constexpr (wrap) fetch_w1(std::integral_constant<int, 0>{}, KC, true, w[nxt]);
-                                else fetch_w1(std::integral_constant<int, wi + 1>{}, KC, false, w[nxt]);
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    });
-                    __builtin_amdgcn_sched_barrier(0);
-                } else {
+                // the next sub-step's activation fragments before the wait; its CT weight fragments
+                // one by one behind the first CT MFMAs of this half: a wave that issues all HP + CT
+                // reads in one clump keeps its MFMAs waiting behind 6 KiB of LDS transfers, -1.1 ..
+                // -1.6 % of kernel time at 128 and 256 filters (round 3, docs/history/experiments.md)
                 if (!wrap || !last_tap) {
                     issued = true;
-                    if constexpr (wrap) {
-                        fetch_xa(std::integral_constant<int, 0>{}, true, std::integral_constant<int, 0>{});
-                        fetch_w(std::integral_constant<int, 0>{}, true, w[nxt]);
-                    } else {
-                        fetch_xa(std::integral_constant<int, i + 1>{}, false, std::integral_constant<int, 0>{});
-                        fetch_w(std::integral_constant<int, wi + 1>{}, false, w[nxt]);
-                    }
+                    if constexpr (wrap) fetch_xa(std::integral_constant<int, 0>{}, true, std::integral_constant<int, NSK>{});
+                    else fetch_xa(std::integral_constant<int, i + 1>{}, false, std::integral_constant<int, SK>{});
                 }
                 if (!issued) wait_lgkm<0>();
-                else wait_lgkm<HP + CT>();               // xb has landed
+                else wait_lgkm<HP - (wrap ? NSK : SK)>();            // xb has landed
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ALT != 7) {
-#pragma unroll
-                for (int pt = 0; pt < HP; pt++)
-#pragma unroll
-                    for (int ct = 0; ct < CT; ct++)
-                        acc[HP + pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xb[pt], acc[HP + pt][ct], 0, 0, 0);
-                }
+                static_for<0, HP * CT>([&](auto KC) {
+                    constexpr int k = decltype(KC)::value, pt = k / CT, ct = k % CT;
+                    acc[HP + pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xb[pt], acc[HP + pt][ct], 0, 0, 0);
+                    if constexpr (k < CT && w_last) {                 // the next MFMA sub-step has new weights
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (issued) {
+                            if constexpr (wrap) fetch_w1(std::integral_constant<int, 0>{}, KC, true, w[nxt]);
+                            else fetch_w1(std::integral_constant<int, wi + 1>{}, KC, false, w[nxt]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
                 __builtin_amdgcn_sched_barrier(0);
-                }
                 if constexpr (s == G::SPT - 1 && w_last) t++;
             });
         };
@@ -636,14 +545,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                         // slots take group tg + GRG - 1
                         const int tg = t / GK;
                         if (tg + 1 < n_groups) {
-                            unsigned long long s0 = 0, s1 = 0;
-                            if constexpr (STAMP) s0 = __builtin_amdgcn_s_memtime();
-                            if (tg + GRG - 2 < n_groups) wait_vmcnt_n<GK * (GRG - 3)>();   // younger groups stay in flight
-                            else wait_vmcnt_n<0>();
-                            if constexpr (STAMP) { s1 = __builtin_amdgcn_s_memtime(); t_vm += s1 - s0; }
+                            if (tg + GRG - 2 < n_groups) wait_vmcnt<GK * (GRG - 3)>();   // younger groups stay in flight
+                            else wait_vmcnt<0>();
                             __builtin_amdgcn_s_barrier();
                             __builtin_amdgcn_sched_barrier(0);
-                            if constexpr (STAMP) t_sb += __builtin_amdgcn_s_memtime() - s1;
                             if (!bias_staged) {
                                 bias_staged = true;
                                 if (conv + 1 < n_convs) stage_bias_x16<G, F>(bias, lds, conv + 1, lane, wave_u);
@@ -653,7 +558,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                                 slot = slot < 0 ? slot + GR : slot;
 #pragma unroll
                                 for (int k = 0; k < GK; k++)
-                                    stage_wtile_x16<G, 0>(wts, lds, (tg + GRG - 1) * GK + k, tid, wave_u, slot + k);
+                                    stage_wtile_x16<G>(wts, lds, (tg + GRG - 1) * GK + k, tid, wave_u, slot + k);
                             }
                         }
                     }
@@ -661,9 +566,9 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     if constexpr (i + 2 < 2 * GK) fetch(std::integral_constant<int, i + 2>{});
                     else if (more) fetch(std::integral_constant<int, i + 2>{});
                     // sub-step i's fragments have landed: at most the younger fetches stay outstanding
-                    if constexpr (i + 2 < 2 * GK) wait_lgkm_n<2 * FR>();
-                    else if constexpr (i == 2 * GK - 2) { if (more) wait_lgkm_n<2 * FR>(); else wait_lgkm_n<FR>(); }
-                    else { if (more) wait_lgkm_n<2 * FR>(); else wait_lgkm_n<0>(); }
+                    if constexpr (i + 2 < 2 * GK) wait_lgkm<2 * FR>();
+                    else if constexpr (i == 2 * GK - 2) { if (more) wait_lgkm<2 * FR>(); else wait_lgkm<FR>(); }
+                    else { if (more) wait_lgkm<2 * FR>(); else wait_lgkm<0>(); }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int pt = 0; pt < PT; pt++)
@@ -717,16 +622,18 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             for (int pt = 0; pt < PT; pt++) ab[0][pt] = ab[1][pt];
             vtap_rows(v + 1 < nv ? v + 1 : 0, ab[1]);
             constexpr std::integral_constant<int, 1> once{};
+            bool whi_twice = false;                     // SPLIT, part 0 of a residual conv: Whi against hi and lo
             if constexpr (SPLIT) {
-                constexpr std::integral_constant<int, 2> twice{};
                 const bool whi = ((v % per_tap) >> hshift) == 0;         // part 0
-                if (conv != 0 && whi) {                                  // Whi against hi and lo
+                whi_twice = conv != 0 && whi;
+            }
+            if (whi_twice) {
+                if constexpr (SPLIT) {
+                    constexpr std::integral_constant<int, 2> twice{};
                     if (F == 64) run_tap(std::integral_constant<int, 4>{}, twice, v == 0, v == nv - 1, nsk, nsk);
                     else run_tap(std::integral_constant<int, 8>{}, twice, v == 0, v == nv - 1, nsk, nsk);
-                } else if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1, nsk, nsk);
-                else run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == nv - 1, nsk, nsk);
-            } else
-            if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1, nsk, nsk);
+                }
+            } else if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1, nsk, nsk);
             else run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == nv - 1, nsk, nsk);
             if constexpr (PAIR) slot_tap = slot_add(slot_tap, 4 / G::SPT);
             // The fragments prefetched for the next tap are in flight across this loop's back-edge, where
@@ -740,12 +647,9 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         }
 
         // ---- epilogue ------------------------------------------------------------------------------
-        if constexpr (STAMP) { const unsigned long long now = __builtin_amdgcn_s_memtime(); t_loop += now - t_mark; t_mark = now; }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();                   // all reads of the activation buffer done
         __builtin_amdgcn_sched_barrier(0);
-        unsigned long long t_a = 0;
-        if constexpr (STAMP) { t_a = __builtin_amdgcn_s_memtime(); t_ba += t_a - t_mark; }
         // three wave-uniform shapes (branches, not selects: every VALU instruction competes with the
         // partner wave's MFMAs for issue slots): stem = linear (no BN, no activation,
         // model.py:33-34); conv1 = ReLU, skip stream untouched; conv2 = + skip, ReLU, new skip
@@ -845,22 +749,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     store_pair(pt, g, o16[0], o16[1]);
                 }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (STAMP) t_wr += __builtin_amdgcn_s_memtime() - t_a;
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (STAMP) { const unsigned long long now = __builtin_amdgcn_s_memtime(); t_epi += now - t_mark; t_mark = now; }
     }
-    if constexpr (STAMP) {
-        // per wave: [loop cycles, epilogue cycles, epilogue phases, total, loop cycles waiting for weight DMA, at the tile barrier]
-        if (lane == 0 && out) {
-            unsigned long long *dbg = reinterpret_cast<unsigned long long *>(out) + ((size_t)blockIdx.x * 8 + wave) * 6;
-            dbg[0] = t_loop; dbg[1] = t_epi; dbg[2] = (t_ba << 32) | (t_wr & 0xffffffffull); dbg[3] = __builtin_amdgcn_s_memtime() - t_begin;
-            dbg[4] = t_vm; dbg[5] = t_sb;
-        }
-        return;
-    }
-
     if (!IDX && out) {
 #pragma unroll
         for (int pt = 0; pt < PT; pt++) {
@@ -903,7 +795,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
 #pragma unroll
             for (int k = 0; k < 3; k++)
                 scratch[(((board * 64 + pos0 + pstep * pt) * 3) + k) * NC + (obase / (16 * CT)) * 4 + q] = part[pt][k];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
         for (int i = tid; i < G::NB * 64 * 3; i += 512) {
             const int k = i % 3, bp = i / 3;

@@ -540,3 +540,27 @@ def test_board_list_header_is_one_number_in_the_header_the_kernels_and_the_bindi
     k = int(re.search(r"constexpr int LIST_HEADER = (\d+);", common).group(1))
     assert h == k == _lib.LIST_HEADER == 4
     assert int(re.search(r"#define\s+CRL_ABI_VERSION\s+(\d+)", header).group(1)) == _lib.ABI_VERSION
+
+
+def test_every_harness_under_tools_ubench_still_compiles_against_the_kernel_headers():
+    """The harnesses under tools/ubench/ include the library's kernel headers (csrc/tower_x16.hpp,
+    tower_layer.hpp, ...) and instantiate kernels from them, but no build and no other test compiles them: a
+    header change that renames a helper or a template parameter would break them silently.  ``hipcc
+    -fsyntax-only`` with the library's flags and ``-I chessrl_amd/csrc`` on every one of them."""
+    import glob
+    import shutil
+    import subprocess
+    from chessrl_amd import _lib
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc not available")
+    harnesses = sorted(glob.glob(os.path.join(ROOT, "tools", "ubench", "*.hip")))
+    assert len(harnesses) >= 7, harnesses
+    flags = [f for f in _lib.HIPCC_FLAGS if f not in ("-fPIC", "-shared")]
+    jobs = [(h, subprocess.Popen(["hipcc"] + flags + ["-fsyntax-only", "-I", os.path.join(ROOT, "chessrl_amd", "csrc"), h],
+                                 stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)) for h in harnesses]
+    failed = {}
+    for h, p in jobs:
+        out = p.communicate()[0]
+        if p.returncode != 0:
+            failed[os.path.basename(h)] = out[-2000:]
+    assert not failed, failed

@@ -7,7 +7,6 @@
 // Also checks that both geometries leave the same bits for the same boards.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I chessrl_amd/csrc tools/ubench/conv_indexed.hip -o tools/ubench/conv_indexed
 //   ./conv_indexed [batch=4096] [reps=10]
-#define CRL_HARNESS 1
 #include "tower_layer.hpp"
 #include <cmath>
 #include <cstdio>

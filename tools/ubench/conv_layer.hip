@@ -6,7 +6,6 @@
 // The kernel is the product's (chessrl_amd/csrc/tower_layer.hpp: k_layer_conv<8, 1 | 2, 0>).
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I chessrl_amd/csrc tools/ubench/conv_layer.hip -o tools/ubench/conv_layer
 //   ./conv_layer [boards=4096] [reps=20]
-#define CRL_HARNESS 1
 #include "tower_layer.hpp"
 #include <cmath>
 #include <cstdio>

@@ -8,7 +8,6 @@
 // must be bit-identical.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I chessrl_amd/csrc tools/ubench/tower_persist.hip -o tools/ubench/tower_persist
 //   ./tower_persist [boards=4096] [blocks=20] [reps=5]
-#define CRL_HARNESS 1
 #include "tower_layer.hpp"
 #include <cmath>
 #include <cstdio>
@@ -148,7 +147,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_tower(unsigned char *__restric
 #pragma unroll
             for (int pt = 0; pt < PT; pt++) acc[pt][ct] = f32x4v{bv[0], bv[1], bv[2], bv[3]};
         }
-        wait_vmcnt_n<0>();
+        wait_vmcnt<0>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -164,16 +163,16 @@ __global__ __launch_bounds__(512, 2) void k_layer_tower(unsigned char *__restric
             typedef std::integral_constant<int, 2 * (1 - P)> SNEXT;
             const int u = c * G::TAPS + t;
             rd_w(w[1 - P], SHI{}, I1{});
-            wait_lgkm_n<HC>();
+            wait_lgkm<HC>();
             __builtin_amdgcn_sched_barrier(0);
             mfma16(w[P], x[P], I0{});
             __builtin_amdgcn_sched_barrier(0);
             rd_x(x[1 - P], ab, I1{});
-            wait_lgkm_n<PT>();
+            wait_lgkm<PT>();
             __builtin_amdgcn_sched_barrier(0);
             mfma16(w[1 - P], x[P], I1{});
             __builtin_amdgcn_sched_barrier(0);
-            wait_lgkm_n<0>();
+            wait_lgkm<0>();
             __builtin_amdgcn_sched_barrier(0);
             mfma16(w[1 - P], x[1 - P], I1{});
             __builtin_amdgcn_sched_barrier(0);
@@ -188,12 +187,12 @@ __global__ __launch_bounds__(512, 2) void k_layer_tower(unsigned char *__restric
             __builtin_amdgcn_sched_barrier(0);
             rd_w(w[P], SLO{}, I0{});
             rd_x(x[1 - P], abn, I0{});
-            wait_lgkm_n<HC + PT>();
+            wait_lgkm<HC + PT>();
             __builtin_amdgcn_sched_barrier(0);
             mfma16(w[1 - P], x[P], I1{});
             __builtin_amdgcn_sched_barrier(0);
-            wait_lgkm_n<PT>();
-            wait_vmcnt_n<0>();
+            wait_lgkm<PT>();
+            wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             {
@@ -222,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_tower(unsigned char *__restric
                 constexpr int t = decltype(TC)::value;
                 tap_body(std::integral_constant<int, (1 + t) & 1>{}, c + 1, TC);
             });
-            wait_lgkm_n<0>();
+            wait_lgkm<0>();
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         // every wave is past its last fragment read: the ring and the chunk buffers are free

@@ -1,20 +1,15 @@
-// Scratch (GPU), round 3: the two bounded experiments on the production trunk kernels
-// (k_trunk_x16 with pair publishing) at 10 x 128 and 20 x 256, 4096 boards:
-//   ALT 7  staging only: weight DMA + barriers + epilogues, no fragment reads, no MFMAs (timing only)
-//   ALT 8  round 2's schedule: weight-fragment reads of the next sub-step in one clump before the MFMAs of half 1;
-//          production (ALT 0) now issues them one by one between those MFMAs (bit-identical)
-// and the time of the split-precision (f16x3) kernels on a random weight image.
-// (A third variant was measured with this harness and removed again: warming each XCD's L2 for the weight
-// tiles 8 / 16 tiles ahead, 1/32 of the lines per workgroup through 4-byte LDS-DMAs: +1.0 ... +1.5 % SLOWER
-// at both sizes -- profiles/r03/trunk_r3_l2_prefetch.log.  The L2 -> LDS stream is not waiting for the fabric.)
+// Scratch (GPU): the production trunk kernels (k_trunk_x16 with pair publishing) at 10 x 128 and 20 x 256,
+// 4096 boards, each timed twice and compared bit for bit with itself, and the time of the split-precision
+// (f16x3) kernels on a random weight image.
+// (Round 3 measured three variants of the kernel with this harness and removed them again: a staging-only
+// build, round 2's clumped weight-fragment reads and an L2 prefetch of the weight stream -- profiles/r03/,
+// docs/history/experiments.md.)
 // Round 7: the rank tiles of the 128-filter NB = 4 kernel (tower_x16.hpp, CRL_TRUNK_RANKPAIR).  The default build
 // times them; -DCRL_TRUNK_RANKPAIR=0 builds the board tiles of before into a second binary.  Alternate the two
 // binaries in ONE run on ONE device (MATCH selects rows by name): devices differ by up to 12 % on MFMA loops.
-// ALT 7 and ALT 8 were written for the board tiles and keep them in both builds.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I chessrl_amd/csrc tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3
 // hipcc ... -DCRL_TRUNK_RANKPAIR=0 tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3_boards
 //   [MATCH="x16<128,4> pair (production)"] ./trunk_r3 [boards=4096] [reps=20]
-#define CRL_HARNESS 1
 #include "tower_x16.hpp"
 #include <cmath>
 #include <cstdio>
@@ -80,7 +75,7 @@ static double run(const char *name, kern_t k, int lds, int nb, int F, int blocks
     const double flops = 2.0 * (73152.0 * F + 1152.0 * F * F * blocks + 192.0 * F) * boards;
     const bool same = ref && memcmp(ref->data(), out.data(), out.size() * 4) == 0;
     printf("%-44s %8.4f ms  %7.1f TFLOP/s (algorithmic)  frac %.3f  %s\n", name, best, flops / best / 1e9,
-           flops / best / 1e9 / 2500.0, !ref ? "reference" : (same ? "bit-identical" : "DIFFERENT (timing-only build)"));
+           flops / best / 1e9 / 2500.0, !ref ? "reference" : (same ? "bit-identical" : "DIFFERENT"));
     fflush(stdout);
     return best;
 }
@@ -92,30 +87,26 @@ int main(int argc, char **argv)
     for (int rep = 0; rep < 2; rep++) {
         Bufs b = make(128, 10, boards, 1);
         printf("== 10 x 128, %d boards (pass %d), production = %s tiles\n", boards, rep,
-               RankTiles<128, 4, 0, 1, 0, 0, 0>::value ? "rank" : "board");
-        const int lds = Geo16<128, 4>::lds_bytes(5);
+               RankTiles<128, 4, 1, 0, 0, 0>::value ? "rank" : "board");
+        const int lds = Geo16<128, 4>::lds_bytes(ring_slots<4, 1, 0>());
         run("x16<128,4> pair (production)", k_trunk_x16<128, 4, 1, 0, 1>, lds, 4, 128, 10, boards, reps, b, ref, nullptr);
-        run("x16<128,4> pair, ALT 8 clumped w reads (r2)", k_trunk_x16<128, 4, 1, 8, 1>, lds, 4, 128, 10, boards, reps, b, out, &ref);
         run("x16<128,4> pair (production) again", k_trunk_x16<128, 4, 1, 0, 1>, lds, 4, 128, 10, boards, reps, b, out, &ref);
-        run("x16<128,4> pair, ALT 7 staging only", k_trunk_x16<128, 4, 1, 7, 1>, lds, 4, 128, 10, boards, reps, b, out, &ref);
     }
     {
         Bufs b = make(256, 20, boards, 1);
         printf("== 20 x 256, %d boards\n", boards);
-        const int lds = Geo16<256, 2>::lds_bytes(5);
+        const int lds = Geo16<256, 2>::lds_bytes(ring_slots<2, 1, 0>());
         run("x16<256,2> pair (production)", k_trunk_x16<256, 2, 1, 0, 1>, lds, 2, 256, 20, boards, 5, b, ref, nullptr);
-        run("x16<256,2> pair, ALT 8 clumped w reads (r2)", k_trunk_x16<256, 2, 1, 8, 1>, lds, 2, 256, 20, boards, 5, b, out, &ref);
         run("x16<256,2> pair (production) again", k_trunk_x16<256, 2, 1, 0, 1>, lds, 2, 256, 20, boards, 5, b, out, &ref);
-        run("x16<256,2> pair, ALT 7 staging only", k_trunk_x16<256, 2, 1, 7, 1>, lds, 2, 256, 20, boards, 5, b, out, &ref);
     }
     {   // split precision: three MFMAs per product over a 2x weight image (random values: time only)
         Bufs b = make(128, 10, boards, 2);
         printf("== f16x3 (split operands), %d boards\n", boards);
-        run("x16<128,2> pair split, 10 x 128", k_trunk_x16<128, 2, 1, 0, 1, 0, 1>, Geo16<128, 2, 1>::lds_bytes(5), 2, 128, 10, boards, reps, b, ref, nullptr);
+        run("x16<128,2> pair split, 10 x 128", k_trunk_x16<128, 2, 1, 0, 1, 0, 1>, Geo16<128, 2, 1>::lds_bytes(ring_slots<2, 1, 0>()), 2, 128, 10, boards, reps, b, ref, nullptr);
         Bufs c = make(256, 20, boards, 2);
-        run("x16<256,1> split, 20 x 256", k_trunk_x16<256, 1, 1, 0, 0, 0, 1>, Geo16<256, 1, 1>::lds_bytes(4), 1, 256, 20, boards, 3, c, ref, nullptr);
+        run("x16<256,1> split, 20 x 256", k_trunk_x16<256, 1, 1, 0, 0, 0, 1>, Geo16<256, 1, 1>::lds_bytes(ring_slots<1, 0, 0>()), 1, 256, 20, boards, 3, c, ref, nullptr);
         Bufs d = make(64, 6, boards, 2);
-        run("x16<64,4> split, 6 x 64", k_trunk_x16<64, 4, 1, 0, 0, 0, 1>, Geo16<64, 4, 1>::lds_bytes(4), 4, 64, 6, boards, reps, d, ref, nullptr);
+        run("x16<64,4> split, 6 x 64", k_trunk_x16<64, 4, 1, 0, 0, 0, 1>, Geo16<64, 4, 1>::lds_bytes(ring_slots<4, 0, 0>()), 4, 64, 6, boards, reps, d, ref, nullptr);
     }
     return 0;
 }
