@@ -261,6 +261,137 @@ def uci_label_moves():
     return out
 
 
+# ---- the stream-level (stateless) entry points, typed --------------------------------------------------------------
+# Parameters carry the names of include/chessrl_hip.h.  A pointer argument is a tensor (anything with data_ptr();
+# it must be contiguous), an int address, or None where the header allows NULL; ``hip_stream`` is a
+# torch.cuda.Stream, an int, or None = the current stream of ``on``'s device.  Everything is checked before the
+# library is reached; dtypes and shapes are the C side's business.
+class _Dev(object):
+    """One pointer argument, checked: ``_Dev(x, "name")`` must be given, ``_Dev(x, "name", None)`` may be NULL."""
+
+    def __init__(self, x, name, *null_ok):
+        if x is None and not null_ok:
+            raise ValueError("%s must not be NULL" % name)
+        if hasattr(x, "data_ptr"):
+            if not x.is_contiguous():
+                raise ValueError("%s is not contiguous" % name)
+            x = x.data_ptr()
+        self.p = ctypes.c_void_p(None if x is None else int(x))
+
+
+def _call(name, hip_stream, on, *args):
+    if hip_stream is None:
+        import torch
+        hip_stream = torch.cuda.current_stream(getattr(on, "device", None))
+    rc = getattr(lib(), name)(ctypes.c_void_p(int(getattr(hip_stream, "cuda_stream", hip_stream))),
+                              *[a.p if isinstance(a, _Dev) else int(a) for a in args])
+    if rc != 0:
+        raise HipLibraryError("%s failed (%d)" % (name, rc))
+
+
+def trunk_forward_x(filters, flags, dev_planes, dev_wtiles_f16, dev_bias_f32, dev_out_f32, n_boards, n_blocks,
+                    dev_head_w_f32, dev_head_b_f32, dev_head_out_f32, dev_workspace=None, workspace_bytes=0,
+                    hip_stream=None):
+    _call("crl_trunk_forward_x", hip_stream, dev_planes, filters, flags, _Dev(dev_planes, "dev_planes"),
+          _Dev(dev_wtiles_f16, "dev_wtiles_f16"), _Dev(dev_bias_f32, "dev_bias_f32"), _Dev(dev_out_f32, "dev_out_f32", None),
+          n_boards, n_blocks, _Dev(dev_head_w_f32, "dev_head_w_f32"), _Dev(dev_head_b_f32, "dev_head_b_f32"),
+          _Dev(dev_head_out_f32, "dev_head_out_f32", None), _Dev(dev_workspace, "dev_workspace", None), workspace_bytes)
+
+
+def trunk_forward_indexed(filters, dev_bitplanes_u64, dev_wtiles_f16x3, dev_bias_f32, n_boards, n_blocks, dev_head_w_f32,
+                          dev_head_b_f32, dev_head_out_f32, dev_list, dev_workspace=None, workspace_bytes=0,
+                          hip_stream=None):
+    _call("crl_trunk_forward_indexed", hip_stream, dev_bitplanes_u64, filters, _Dev(dev_bitplanes_u64, "dev_bitplanes_u64"),
+          _Dev(dev_wtiles_f16x3, "dev_wtiles_f16x3"), _Dev(dev_bias_f32, "dev_bias_f32"), n_boards, n_blocks,
+          _Dev(dev_head_w_f32, "dev_head_w_f32"), _Dev(dev_head_b_f32, "dev_head_b_f32"),
+          _Dev(dev_head_out_f32, "dev_head_out_f32"), _Dev(dev_list, "dev_list"),
+          _Dev(dev_workspace, "dev_workspace", None), workspace_bytes)
+
+
+def _heads_weights(dev_policy_wp_f16, dev_policy_bias_f32, dev_value_w1p_f16, dev_value_b1_f32, dev_value_w2b2_f32):
+    return (_Dev(dev_policy_wp_f16, "dev_policy_wp_f16"), _Dev(dev_policy_bias_f32, "dev_policy_bias_f32"),
+            _Dev(dev_value_w1p_f16, "dev_value_w1p_f16"), _Dev(dev_value_b1_f32, "dev_value_b1_f32"),
+            _Dev(dev_value_w2b2_f32, "dev_value_w2b2_f32"))
+
+
+def heads_forward(dev_head_act_f32, n_boards, dev_policy_wp_f16, dev_policy_bias_f32, dev_value_w1p_f16,
+                  dev_value_b1_f32, dev_value_w2b2_f32, dev_policy_out_f32, dev_value_out_f32=None,
+                  dev_scratch_f32=None, hip_stream=None):
+    _call("crl_heads_forward", hip_stream, dev_head_act_f32, _Dev(dev_head_act_f32, "dev_head_act_f32"), n_boards,
+          *_heads_weights(dev_policy_wp_f16, dev_policy_bias_f32, dev_value_w1p_f16, dev_value_b1_f32, dev_value_w2b2_f32),
+          _Dev(dev_policy_out_f32, "dev_policy_out_f32"), _Dev(dev_value_out_f32, "dev_value_out_f32", None),
+          _Dev(dev_scratch_f32, "dev_scratch_f32", None))
+
+
+def heads_forward_legal(dev_head_act_f32, n_boards, dev_policy_wp_f16, dev_policy_bias_f32, dev_value_w1p_f16,
+                        dev_value_b1_f32, dev_value_w2b2_f32, dev_labels, dev_counts, dev_priors_out_f32,
+                        dev_value_out_f32=None, dev_scratch_f32=None, hip_stream=None):
+    _call("crl_heads_forward_legal", hip_stream, dev_head_act_f32, _Dev(dev_head_act_f32, "dev_head_act_f32"), n_boards,
+          *_heads_weights(dev_policy_wp_f16, dev_policy_bias_f32, dev_value_w1p_f16, dev_value_b1_f32, dev_value_w2b2_f32),
+          _Dev(dev_labels, "dev_labels"), _Dev(dev_counts, "dev_counts"), _Dev(dev_priors_out_f32, "dev_priors_out_f32"),
+          _Dev(dev_value_out_f32, "dev_value_out_f32", None), _Dev(dev_scratch_f32, "dev_scratch_f32", None))
+
+
+def heads_forward_legal_raw(dev_head_act_f32, n_boards, dev_policy_wp_f16, dev_policy_bias_f32, dev_value_w1p_f16,
+                            dev_value_b1_f32, dev_value_w2b2_f32, dev_labels, dev_counts, dev_logits_out_f32,
+                            dev_value_out_f32, dev_stats_out_f32, hip_stream=None):
+    _call("crl_heads_forward_legal_raw", hip_stream, dev_head_act_f32, _Dev(dev_head_act_f32, "dev_head_act_f32"), n_boards,
+          *_heads_weights(dev_policy_wp_f16, dev_policy_bias_f32, dev_value_w1p_f16, dev_value_b1_f32, dev_value_w2b2_f32),
+          _Dev(dev_labels, "dev_labels"), _Dev(dev_counts, "dev_counts"), _Dev(dev_logits_out_f32, "dev_logits_out_f32"),
+          _Dev(dev_value_out_f32, "dev_value_out_f32", None), _Dev(dev_stats_out_f32, "dev_stats_out_f32"))
+
+
+def reply_margin(dev_priors_f32, dev_counts, n_boards, dev_log_margin_f32, rows_are_logits, dev_list, hip_stream=None):
+    _call("crl_reply_margin", hip_stream, dev_priors_f32, _Dev(dev_priors_f32, "dev_priors_f32"),
+          _Dev(dev_counts, "dev_counts"), n_boards, _Dev(dev_log_margin_f32, "dev_log_margin_f32"), rows_are_logits,
+          _Dev(dev_list, "dev_list"))
+
+
+def stamp(dev_ring, capacity, id, hip_stream=None):
+    _call("crl_stamp", hip_stream, dev_ring, _Dev(dev_ring, "dev_ring"), capacity, id)
+
+
+def trunk_workspace_bytes(filters, n_boards, flags):
+    return int(lib().crl_trunk_workspace_bytes(int(filters), int(n_boards), int(flags)))
+
+
+def heads_raw_supported(n_boards):
+    return bool(lib().crl_heads_raw_supported(int(n_boards)))
+
+
+def trunk_kernel_name(filters, n_boards, flags):
+    """The kernel crl_trunk_forward_x launches for this filter count, batch and flags, as rocprofv3 prints it."""
+    buf = ctypes.create_string_buffer(256)
+    rc = lib().crl_trunk_kernel_name(int(filters), int(n_boards), int(flags), buf, len(buf))
+    if rc != 0:
+        raise HipLibraryError("crl_trunk_kernel_name failed (%d)" % rc)
+    return buf.value.decode()
+
+
+class _Setting(object):
+    """A process-global tuning value, set when this object is made; as a context manager it restores the default."""
+
+    def __init__(self, name, value, default):
+        self._set = lambda v: getattr(lib(), name)(int(v))
+        self._default = default
+        if self._set(value) != 0:
+            raise HipLibraryError("%s failed" % name)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._set(self._default)
+
+
+def trunk_set_small_batch(enabled):
+    return _Setting("crl_trunk_set_small_batch", 1 if enabled else 0, 1)
+
+
+def heads_set_sliced_max(boards):
+    return _Setting("crl_heads_set_sliced_max", boards, 2048)
+
+
 class Context(object):
     """One crl_ctx (one GPU).  Thin, numpy-in/numpy-out; device pointers are ints."""
 

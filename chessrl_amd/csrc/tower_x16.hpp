@@ -82,7 +82,7 @@ struct Geo16 {
     // Output channel held by row `row` of a weight plane (rows 16 ct + i of a wave's 16 CT rows): the
     // same bit rotation inside every 32-row block whatever the geometry.  The GLOBAL weight image is
     // stored in exactly the LDS image's order -- planes of [F rows][64 bytes], rows in this order,
-    // the four 16-byte chunks of a row at position chunk ^ wswz(row) (chessrl_amd/model.py:_pack_fused,
+    // the four 16-byte chunks of a row at position chunk ^ wswz(row) (chessrl_amd/packing.py:pack_trunk,
     // include/chessrl_hip.h) -- so a tile is one contiguous block that every wave copies in 1-KiB
     // pieces (sixteen 64-byte half lines per piece before: -0.8 % / -1.9 % at 128 / 256 filters).
     __host__ __device__ static constexpr int row_channel(int row)

@@ -21,12 +21,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib, packing, precision as rules
+from .packing import BN_EPS, N_POLICY, PAD_PLANES, fold as _fold  # noqa: F401  (names other modules import from here)
+
 log = logging.getLogger("chessrl_amd.model")
 
-BN_EPS = 1e-3            # keras.layers.BatchNormalization default
-N_POLICY = 1968
 IN_PLANES = 127
-PAD_PLANES = 128
 
 
 def init_weights(blocks, filters, seed=0):
@@ -70,26 +70,15 @@ def init_weights(blocks, filters, seed=0):
     return w
 
 
-def _fold(w, conv, bn=None):
-    """(OIHW fp32 kernel, bias) of `conv` with the following BatchNorm folded in."""
-    k = torch.from_numpy(np.asarray(w[conv + ".kernel"], np.float32)).permute(3, 2, 0, 1).contiguous()
-    b = torch.from_numpy(np.asarray(w[conv + ".bias"], np.float32)).clone()
-    if bn is not None:
-        g = torch.from_numpy(np.asarray(w[bn + ".gamma"], np.float32))
-        beta = torch.from_numpy(np.asarray(w[bn + ".beta"], np.float32))
-        mean = torch.from_numpy(np.asarray(w[bn + ".mean"], np.float32))
-        var = torch.from_numpy(np.asarray(w[bn + ".var"], np.float32))
-        s = g / torch.sqrt(var + BN_EPS)
-        k = k * s.view(-1, 1, 1, 1)
-        b = (b - mean) * s + beta
-    return k, b
-
-
 def _read_weights(path):
     if str(path).endswith((".h5", ".hdf5")):
         from .keras_h5 import load_keras_h5
         return load_keras_h5(path)
     return dict(np.load(path))
+
+
+def _dmax(a, b):
+    return float((a - b).abs().max())
 
 
 _PROBE = {}
@@ -342,75 +331,17 @@ class ChessModel(object):
             return torch.float32
         return self.dtype
 
-    @staticmethod
-    def _plane_order(F_):
-        """(row -> output channel, row -> chunk swizzle) of a weight plane as the trunk kernel keeps
-        it in LDS (csrc/tower_x16.hpp: Geo16::row_channel, wswz)."""
-        rows = np.arange(F_)
-        ct, i = (rows >> 4) & 1, rows & 15
-        chan = (rows & ~31) + 8 * (i >> 2) + 4 * ct + (i & 3)
-        return chan, (-(rows >> 2)) & 3
-
     def _pack_fused(self, w):
-        """BN-folded fp16 kernels as the planes the fused trunk consumes, in consumption order
-        [conv][tap=ky*3+kx][in-ch/32][F rows][4 chunks][8 in]: row r holds output channel
-        _plane_order(F)[0][r], its four 16-byte chunks (8 input channels each) sit at position
-        chunk ^ swizzle(r) -- byte for byte the image the kernel wants in LDS, so its weight DMA
-        copies contiguous blocks.  Biases f32 [conv][F]."""
-        F_ = self.filters
-        chan, swz = self._plane_order(F_)
-        chan_t = torch.from_numpy(chan)
-        src_chunk = torch.from_numpy(np.arange(4)[None, :] ^ swz[:, None])        # [row][phys] -> chunk
-        names = [("stem", None)]
-        for i in range(self.blocks):
-            names += [("block%d.conv1" % i, "block%d.bn1" % i), ("block%d.conv2" % i, "block%d.bn2" % i)]
+        """The weight images of the HIP tower (packing.pack_weights) on the device, under the ten attribute names of
+        ``packing.NAMES``.  An image of unchanged shape is overwritten in place: captured graphs stay valid."""
         want_f16 = self.precision_requested in ("auto", "f16", "hybrid")
         want_x3 = self.precision_requested in ("auto", "f16x3", "hybrid")
-        tiles, tiles3, biases = [], [], []
-
-        def planes_of(k16):
-            """fp16 OIHW kernel -> [tap][in-ch/32][row][chunk][8] in the LDS image's order."""
-            cin = k16.shape[1]                                 # 128 for the stem, F otherwise
-            t = k16.permute(2, 3, 0, 1).reshape(9, F_, cin // 32, 4, 8)                  # [tap][o][g][chunk][8]
-            t = t[:, chan_t]                                                              # rows in plane order
-            t = t.permute(0, 2, 1, 3, 4)                                                  # [tap][g][row][chunk][8]
-            idx = src_chunk.view(1, 1, F_, 4, 1).expand(9, cin // 32, F_, 4, 8)
-            return torch.gather(t, 3, idx)                                                # chunk ^ swizzle(row)
-
-        for conv, bn in names:
-            k, b = _fold(w, conv, bn)                          # OIHW fp32
-            if conv == "stem" and k.shape[1] < PAD_PLANES:    # 127 planes -> 128 channels
-                kp = torch.zeros(k.shape[0], PAD_PLANES, 3, 3)
-                kp[:, :k.shape[1]] = k
-                k = kp
-            hi = k.to(torch.float16)
-            t_hi = planes_of(hi)
-            if want_f16:
-                tiles.append(t_hi.contiguous().reshape(-1))
-            if want_x3:
-                # CRL_TRUNK_SPLIT: per tap the planes of Whi, then of Wlo = fp16(W - Whi); the kernel
-                # uses every Whi plane for hi.Whi and lo.Whi in one pass, the Wlo planes for hi.Wlo
-                t_lo = planes_of((k - hi.float()).to(torch.float16))
-                if F_ == 256:
-                    # the layer-wise kernels of csrc/tower_layer.hpp keep a 32-channel K-chunk of the activations in
-                    # LDS for all nine taps: planes K-CHUNK-major, [g][tap][part][row]...
-                    tiles3.append(torch.stack([t_hi, t_lo], dim=2).permute(1, 0, 2, 3, 4, 5).contiguous().reshape(-1))
-                else:
-                    tiles3.append(torch.stack([t_hi, t_lo], dim=1).contiguous().reshape(-1))   # [tap][part][g][row]...
-            biases.append(b)
-        kp, bp = _fold(w, "policy.conv", "policy.bn")          # [2][F][1][1]
-        kv, bv = _fold(w, "value.conv", "value.bn")            # [1][F][1][1]
-        empty = torch.zeros(8, dtype=torch.float16)
-        new = (torch.cat(tiles) if want_f16 else empty, torch.cat(tiles3) if want_x3 else empty,
-               torch.stack(biases).float(),
-               torch.cat([kp.reshape(2, F_), kv.reshape(1, F_)]).float(), torch.cat([bp, bv]).float())
-        new = new + self._pack_dense(w)
-        names = ("_wtiles", "_wtiles3", "_wbias", "_head_w", "_head_b", "_pol_wp", "_pol_bias", "_val_w1p", "_val_b1", "_val_w2")
+        new = packing.pack_weights(w, self.blocks, self.filters, want_f16, want_x3)
         first = getattr(self, "_wtiles", None) is None
         if first:
             self._pad_in = None
             self._pad_bits = None
-        for name, src in zip(names, new):
+        for name, src in zip(packing.NAMES, new):
             cur = None if first else getattr(self, name, None)
             if cur is not None and cur.shape == src.shape:
                 cur.copy_(src)                                 # in place: captured graphs stay valid
@@ -418,29 +349,6 @@ class ChessModel(object):
                 setattr(self, name, src.to(self.device).contiguous())
                 if cur is not None:
                     self.graph_epoch += 1                      # a captured graph holds the old tensor
-
-    @staticmethod
-    def _pack_split(x, tiles, ksteps):
-        """fp32 [tiles*16 units][ksteps*32 inputs] -> fp16 (hi, lo) MFMA fragments in the order
-        csrc/heads.hpp reads them: [tile][k-step][hi|lo][lane = 16 q + r][8], the lane holding
-        x[16 tile + r][32 s + 8 q + e]."""
-        hi = x.half()
-        lo = (x - hi.float()).half()
-        frag = torch.stack([hi, lo])                                         # [2][units][inputs]
-        frag = frag.reshape(2, tiles, 16, ksteps, 4, 8)                      # [hl][t][r][s][q][e]
-        return frag.permute(1, 3, 0, 4, 2, 5).contiguous().reshape(-1)       # [t][s][hl][q][r][e]
-
-    def _pack_dense(self, w):
-        """Dense layers of the two heads (model.py:44-48, 56-61) for crl_heads_forward."""
-        wp = torch.zeros((2048, 128))
-        wp[:N_POLICY] = torch.from_numpy(np.asarray(w["policy.dense.kernel"], np.float32)).t()
-        pb = torch.full((2048,), -1e30)
-        pb[:N_POLICY] = torch.from_numpy(np.asarray(w["policy.dense.bias"], np.float32))
-        w1 = torch.from_numpy(np.asarray(w["value.dense1.kernel"], np.float32)).t().contiguous()    # [256][64]
-        return (self._pack_split(wp, 128, 4), pb.float(), self._pack_split(w1, 16, 2),
-                torch.from_numpy(np.asarray(w["value.dense1.bias"], np.float32)).clone(),
-                torch.cat([torch.from_numpy(np.asarray(w["value.dense2.kernel"], np.float32)).reshape(-1),
-                           torch.from_numpy(np.asarray(w["value.dense2.bias"], np.float32)).reshape(-1)]))    # w2, b2
 
     def _run_fused(self, planes, want_trunk=False, precision=None):
         """One launch of the fused trunk kernel.  ``planes``: fp16 NHWC [B,8,8,128], or int64
@@ -458,8 +366,6 @@ class ChessModel(object):
         return planes_p, heads
 
     def _launch_fused(self, planes, want_trunk, precision):
-        import ctypes
-        from . import _lib
         b = planes.shape[0]
         bp = (b + 3) // 4 * 4
         bits = planes.dtype == torch.int64       # 128 plane bitboards per board (CRL_PLANES_BITS)
@@ -486,16 +392,8 @@ class ChessModel(object):
         flags = (_lib.TRUNK_BITPLANES if bits else 0) | (_lib.TRUNK_SPLIT if split else 0)
         ws = self._trunk_workspace(bp) if split else None
         ev = self._trunk_event("f16x3" if split else "f16")
-        rc = _lib.lib().crl_trunk_forward_x(
-            ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), self.filters, flags,
-            ctypes.c_void_p(planes.data_ptr()), ctypes.c_void_p(image.data_ptr()),
-            ctypes.c_void_p(self._wbias.data_ptr()),
-            ctypes.c_void_p(trunk.data_ptr() if want_trunk else None), bp, self.blocks,
-            ctypes.c_void_p(self._head_w.data_ptr()), ctypes.c_void_p(self._head_b.data_ptr()),
-            ctypes.c_void_p(heads.data_ptr()), ctypes.c_void_p(ws.data_ptr() if ws is not None else None),
-            ws.numel() if ws is not None else 0)
-        if rc != 0:
-            raise _lib.HipLibraryError("crl_trunk_forward_x failed (%d)" % rc)
+        _lib.trunk_forward_x(self.filters, flags, planes, image, self._wbias, trunk, bp, self.blocks, self._head_w,
+                             self._head_b, heads, ws, ws.numel() if ws is not None else 0)
         if ev is not None:
             ev[2].record()
         return planes, heads, trunk
@@ -508,8 +406,7 @@ class ChessModel(object):
         run only ever shrinks its batch, so in practice it is allocated once).  Contents are undefined between calls, so
         every caller of this model -- the engine's graph, ``guard_check``, the probe -- must launch on ONE stream at a
         time (every engine of the product does)."""
-        from . import _lib
-        n = int(_lib.lib().crl_trunk_workspace_bytes(self.filters, bp, _lib.TRUNK_BITPLANES | _lib.TRUNK_SPLIT))
+        n = _lib.trunk_workspace_bytes(self.filters, bp, _lib.TRUNK_BITPLANES | _lib.TRUNK_SPLIT)
         if n == 0:
             return None
         if self._workspace is None or self._workspace.numel() < n:
@@ -563,11 +460,17 @@ class ChessModel(object):
         self.precision_requested = "auto"
         self._pack_fused(self.weights)
         planes = _probe_bitplanes(self.device, self.PROBE_POSITIONS)
-        pa, va = self._forward_fused(planes, precision="f16")
-        pb, vb = self._forward_fused(planes, precision="f16x3")
+        (pa, va), (pb, vb) = self._both(planes)
         self.precision_requested, self.precision = keep_req, keep
-        return {"positions": int(planes.shape[0]), "dpolicy_max": float((pa - pb).abs().max()),
-                "dvalue_max": float((va - vb).abs().max())}
+        return {"positions": int(planes.shape[0]), "dpolicy_max": _dmax(pa, pb), "dvalue_max": _dmax(va, vb)}
+
+    def _both(self, planes):
+        """``planes`` in both arithmetics: (policy, value) of "f16", then (policy, value) of "f16x3"."""
+        return self._forward_fused(planes, precision="f16"), self._forward_fused(planes, precision="f16x3")
+
+    def _auto_kept_f16(self):
+        """Whether the model runs an "f16" that "auto" chose on the probe: what the run-time guard watches and leaves."""
+        return bool(self.fused and self.precision == "f16" and self.precision_requested == "auto")
 
     def _resolve_precision(self):
         """Fix ``self.precision`` for the weights just packed.  "auto": evaluate the probe positions in
@@ -580,23 +483,16 @@ class ChessModel(object):
             self.precision = self.precision_requested
         else:
             planes = _probe_bitplanes(self.device, self.PROBE_POSITIONS)
-            pa, va = self._forward_fused(planes, precision="f16")
-            pb, vb = self._forward_fused(planes, precision="f16x3")
-            dp, dv = float((pa - pb).abs().max()), float((va - vb).abs().max())
+            (pa, va), (pb, vb) = self._both(planes)
+            dp, dv = _dmax(pa, pb), _dmax(va, vb)
             # the same distance in log space: a rounding error of the trunk moves a LOGIT, i.e. a probability
             # by a factor -- what decides whether an argmax over the legal moves can flip
-            dlog = self._log_distance(pa, pb)
+            dlog = rules.log_distance(pa, pb)
             if dlog is None:                                 # (degenerate weights: no finite log-distance anywhere)
                 dlog = float("nan")                          # a NaN margin lists every board: f16x3 everywhere
-            # a run whose guard has fired once stays strict across reloads unless a later weight set passes the probe
-            # WITH margin (half the tolerance): a net at the edge would otherwise flip f16 <-> hybrid -- and re-capture
-            # every engine's graphs -- at each reload
-            sticky = self.guard.get("fired") is not None
-            tol = self.PROBE_TOL * (self.STICKY_FACTOR if sticky else 1.0)
-            if self.precision_requested == "hybrid":
-                self.precision = "hybrid"
-            else:
-                self.precision = "f16" if max(dp, dv) <= tol else self.AUTO_STRICT
+            sticky = self.guard.get("fired") is not None     # (the guard has fired in this run: precision.probe_tolerance)
+            tol = rules.probe_tolerance(self.PROBE_TOL, self.STICKY_FACTOR, sticky)
+            self.precision = rules.choose_mode(self.precision_requested, dp, dv, tol, self.AUTO_STRICT)
             self.reply_margin = self.HYBRID_K * dlog
             self._probe_margin = self.reply_margin
             self._publish_reply_margin()
@@ -619,11 +515,10 @@ class ChessModel(object):
         if self.fused and self.precision == "hybrid":
             self.margin_check(planes)
             return None
-        if not (self.fused and self.precision == "f16" and self.precision_requested == "auto"):
+        if not self._auto_kept_f16():
             return None
-        pa, va = self._forward_fused(planes, precision="f16")
-        pb, vb = self._forward_fused(planes, precision="f16x3")
-        d = max(float((pa - pb).abs().max()), float((va - vb).abs().max()))
+        (pa, va), (pb, vb) = self._both(planes)
+        d = max(_dmax(pa, pb), _dmax(va, vb))
         g = self.guard
         g["checks"] += 1
         g["positions"] += int(planes.shape[0])
@@ -638,7 +533,7 @@ class ChessModel(object):
         the run-time guard's action, also taken when ANOTHER rank's guard fired (SelfPlayRunner._follow_strictest).
         Sticky for the run: later weight sets are kept in f16 only when the probe passes with margin
         (``_resolve_precision``).  False when there is nothing to leave (a mode asked for by name, a strict mode)."""
-        if not (self.fused and self.precision == "f16" and self.precision_requested == "auto"):
+        if not self._auto_kept_f16():
             return False
         fired = dict(why) if isinstance(why, dict) else {"why": str(why)}
         fired.update({"from": "f16", "to": self.AUTO_STRICT})
@@ -658,9 +553,8 @@ class ChessModel(object):
         margin -- in the device float the captured graphs read, so from the very next step and without a
         re-capture.  A wider margin only lists more boards for the second, f16x3 evaluation; results do not change.
         Returns the distance measured."""
-        pa, _ = self._forward_fused(planes, precision="f16")
-        pb, _ = self._forward_fused(planes, precision="f16x3")
-        dlog = self._log_distance(pa, pb)
+        (pa, _), (pb, _) = self._both(planes)
+        dlog = rules.log_distance(pa, pb)
         g = self.guard
         g["margin_checks"] = g.get("margin_checks", 0) + 1
         g["margin_positions"] = g.get("margin_positions", 0) + int(planes.shape[0])
@@ -668,33 +562,20 @@ class ChessModel(object):
             return None
         g["worst_dlog"] = max(g.get("worst_dlog", 0.0), dlog)
         g.setdefault("margin_at_start", self.reply_margin)
-        if self.HYBRID_K * dlog > self.reply_margin:
-            # never beyond MARGIN_CAP x the probe's margin: a margin that wide lists most boards anyway, and one
-            # outlier (a policy entry at the edge of fp32 underflow in one arithmetic) must not turn every S1
-            # evaluation of the rest of the run into f16 + f16x3
-            cap = self.MARGIN_CAP * (getattr(self, "_probe_margin", None) or g["margin_at_start"])
-            wider = min(self.HYBRID_K * dlog, cap)
-            if self.HYBRID_K * dlog > cap:
-                g["margin_capped"] = g.get("margin_capped", 0) + 1
-                log.warning("hybrid reply margin: %.3e asked for by this run's positions, capped at %.3e (%g x the probe's)",
-                            self.HYBRID_K * dlog, cap, self.MARGIN_CAP)
-            if wider > self.reply_margin:
-                g["margin_widened"] = g.get("margin_widened", 0) + 1
-                self.reply_margin = wider
-                self._publish_reply_margin()
+        probe_margin = getattr(self, "_probe_margin", None) or g["margin_at_start"]
+        wider, capped = rules.widened_margin(self.reply_margin, probe_margin, dlog, self.HYBRID_K, self.MARGIN_CAP)
+        if capped:
+            g["margin_capped"] = g.get("margin_capped", 0) + 1
+            log.warning("hybrid reply margin: %.3e asked for by this run's positions, capped at %.3e (%g x the probe's)",
+                        self.HYBRID_K * dlog, self.MARGIN_CAP * probe_margin, self.MARGIN_CAP)
+        if wider > self.reply_margin:
+            g["margin_widened"] = g.get("margin_widened", 0) + 1
+            self.reply_margin = wider
+            self._publish_reply_margin()
         g["margin"] = self.reply_margin
         return dlog
 
-    @staticmethod
-    def _log_distance(pa, pb):
-        """max |log pa - log pb| over the entries both arithmetics can speak about: pb above 1e-12 AND pa > 0 (an f16
-        policy entry that underflowed to 0 has log -inf: the distance would be infinite, the margin with it, and every
-        S1 board would be evaluated twice until the next weight set).  None when no entry qualifies."""
-        ok = (pb > 1e-12) & (pa > 0)
-        if not bool(ok.any()):
-            return None
-        d = float((pa[ok].log() - pb[ok].log()).abs().max())
-        return d if np.isfinite(d) else None
+    _log_distance = staticmethod(rules.log_distance)
 
     @torch.no_grad()
     def reply_rule_check(self, planes, labels_ptr, counts_ptr):
@@ -707,34 +588,17 @@ class ChessModel(object):
         must be one the rule lists.  A board that is NOT listed and differs is a failure of the rule: it is counted
         (``guard["reply_rule"]``), logged, and the margin is widened past that board's gap at once.  Costs two legal-prior
         head passes beside margin_check's two trunk evaluations; returns the record of this check or None outside hybrid."""
-        import ctypes
-        from . import _lib
         if not (self.fused and self.precision == "hybrid"):
             return None
         n = planes.shape[0]
-        vp = ctypes.c_void_p
-        stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
         pri = []
         for mode in ("f16", "f16x3"):
             _, hp = self._run_fused(planes, precision=mode)
             out = torch.zeros((n, 256), dtype=torch.float32, device=self.device)
-            rc = _lib.lib().crl_heads_forward_legal(
-                stream, vp(hp.data_ptr()), n, vp(self._pol_wp.data_ptr()), vp(self._pol_bias.data_ptr()),
-                vp(self._val_w1p.data_ptr()), vp(self._val_b1.data_ptr()), vp(self._val_w2.data_ptr()), vp(labels_ptr),
-                vp(counts_ptr), vp(out.data_ptr()), None, vp(self._heads_scratch(n).data_ptr()))
-            if rc != 0:
-                raise _lib.HipLibraryError("crl_heads_forward_legal failed (%d)" % rc)
+            _lib.heads_forward_legal(hp, n, *self._dense_images(), labels_ptr, counts_ptr, out, None, self._heads_scratch(n))
             pri.append(out)
         counts = torch.as_tensor(_DeviceArray(counts_ptr, (n,), "<i4"), device=self.device).clone()
-        legal = torch.arange(256, device=self.device)[None, :] < counts[:, None]
-        p16 = torch.where(legal, pri[0], torch.full_like(pri[0], -1.0))
-        p48 = torch.where(legal, pri[1], torch.full_like(pri[1], -1.0))
-        a16, a48 = p16.argmax(dim=1), p48.argmax(dim=1)              # (first maximum, as np.argmax / the kernels take it)
-        top2 = p16.topk(2, dim=1).values
-        gap = torch.log(top2[:, 0].clamp_min(1e-38)) - torch.log(top2[:, 1].clamp_min(1e-38))
-        listed = (counts >= 2) & ~(gap >= float(self.reply_margin))   # (a NaN gap is listed, as in k_reply_margin)
-        differ = (a16 != a48) & (counts >= 2)
-        unlisted = differ & ~listed
+        listed, differ, unlisted, gap = rules.reply_rule(pri[0], pri[1], counts, self.reply_margin)
         g = self.guard.setdefault("reply_rule", {"checks": 0, "boards": 0, "listed": 0, "replies_that_differ": 0,
                                                  "differ_but_not_listed": 0, "largest_gap_of_a_differing_reply": 0.0})
         g["checks"] += 1
@@ -754,6 +618,23 @@ class ChessModel(object):
             self.guard["margin"] = self.reply_margin
         return {"boards": int((counts >= 2).sum()), "listed": int(listed.sum()), "differ": int(differ.sum()), "unlisted": bad}
 
+    def check_on_run(self, planes, labels_ptr=None, counts_ptr=None):
+        """What a run does every few move boundaries with the tower inputs its search has just evaluated: the guard of
+        an auto-kept "f16" or the margin check of "hybrid" (``guard_check``) and, in hybrid with the positions' legal
+        labels at hand, the reply rule itself on the same positions; what changed is logged.  Returns guard_check's."""
+        before, margin = self.precision, self.reply_margin
+        d = self.guard_check(planes)
+        if before == "hybrid":
+            if labels_ptr is not None:
+                self.reply_rule_check(planes, labels_ptr, counts_ptr)
+            if self.reply_margin != margin:
+                log.info("hybrid reply margin widened from %.3e to %.3e (log-policy distance of f16 on this run's own "
+                         "tree leaves)", margin, self.reply_margin)
+        if d is not None and self.precision != before:
+            log.warning("tower precision guard: |f16 - f16x3| = %.2e on this run's own tree leaves (tolerance %.1e): "
+                        "%s -> %s from the next move on", d, self.GUARD_TOL, before, self.precision)
+        return d
+
     def _publish_reply_margin(self):
         """Write ``reply_margin`` into the device float crl_reply_margin reads (allocated once, rewritten in
         place: captured graphs hold its address and see the margin of the weights they run with)."""
@@ -766,8 +647,6 @@ class ChessModel(object):
     def _forward_fused(self, planes, pol_out=None, val_out=None, precision=None):
         """Fused trunk + head convs in one HIP kernel, then the dense layers (model.py:44-48,56-61)
         in one launch per head (csrc/heads.hpp), written straight into the caller's buffers."""
-        import ctypes
-        from . import _lib
         _, hp = self._run_fused(planes, precision=precision)
         b = hp.shape[0]
         want_value = not (pol_out is not None and val_out is None)   # S1 evaluations only choose the reply
@@ -775,15 +654,12 @@ class ChessModel(object):
         v = None
         if want_value:
             v = val_out if val_out is not None else torch.empty((b,), dtype=torch.float32, device=self.device)
-        vp = ctypes.c_void_p
-        rc = _lib.lib().crl_heads_forward(
-            vp(torch.cuda.current_stream(self.device).cuda_stream), vp(hp.data_ptr()), b,
-            vp(self._pol_wp.data_ptr()), vp(self._pol_bias.data_ptr()), vp(self._val_w1p.data_ptr()),
-            vp(self._val_b1.data_ptr()), vp(self._val_w2.data_ptr()), vp(p.data_ptr()), vp(v.data_ptr() if v is not None else None),
-            vp(self._heads_scratch(b).data_ptr()))
-        if rc != 0:
-            raise _lib.HipLibraryError("crl_heads_forward failed (%d)" % rc)
+        _lib.heads_forward(hp, b, *self._dense_images(), p, v, self._heads_scratch(b))
         return p, v
+
+    def _dense_images(self):
+        """The dense layers of the two heads as the crl_heads_forward* entry points take them, in their order."""
+        return self._pol_wp, self._pol_bias, self._val_w1p, self._val_b1, self._val_w2
 
     def _heads_scratch(self, n_boards):
         """Slice statistics of the small-batch heads (crl_heads_forward: float [n_boards][16]); one
@@ -807,25 +683,16 @@ class ChessModel(object):
         With ``stats_out`` (fp32 [B,16]; only for batches ``raw_priors_supported``) the rows receive
         the LOGITS and ``stats_out`` the softmax statistics of the label slices: the search kernels
         normalise on read (CRL_POLICY_LEGAL_RAW) and the heads' normalising pass is not launched."""
-        import ctypes
-        from . import _lib
         if not self.fused:
             raise _lib.HipLibraryError("forward_legal_into needs the fused HIP tower")
-        vp = ctypes.c_void_p
-        L = _lib.lib()
-        stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
-        fn = L.crl_heads_forward_legal if stats_out is None else L.crl_heads_forward_legal_raw
-        who = "crl_heads_forward_legal" if stats_out is None else "crl_heads_forward_legal_raw"
 
         def heads(hp):
-            scratch = self._heads_scratch(hp.shape[0]) if stats_out is None else stats_out
-            rc = fn(stream, vp(hp.data_ptr()), hp.shape[0],
-                    vp(self._pol_wp.data_ptr()), vp(self._pol_bias.data_ptr()), vp(self._val_w1p.data_ptr()),
-                    vp(self._val_b1.data_ptr()), vp(self._val_w2.data_ptr()), vp(labels_ptr), vp(counts_ptr),
-                    vp(priors_out.data_ptr()), vp(val_out.data_ptr() if val_out is not None else None),
-                    vp(scratch.data_ptr()))
-            if rc != 0:
-                raise _lib.HipLibraryError("%s failed (%d)" % (who, rc))
+            if stats_out is None:
+                _lib.heads_forward_legal(hp, hp.shape[0], *self._dense_images(), labels_ptr, counts_ptr, priors_out, val_out,
+                                         self._heads_scratch(hp.shape[0]))
+            else:
+                _lib.heads_forward_legal_raw(hp, hp.shape[0], *self._dense_images(), labels_ptr, counts_ptr, priors_out,
+                                             val_out, stats_out)
 
         if self.precision == "hybrid" and val_out is None and planes.shape[0] >= self.HYBRID_MIN_BOARDS:
             # S1: the reply is an argmax over the legal labels.  Single-MFMA trunk for every board; the boards
@@ -840,19 +707,11 @@ class ChessModel(object):
             lst = self._fallback.get(bp)
             if lst is None:
                 lst = self._fallback[bp] = torch.zeros(_lib.LIST_HEADER + bp, dtype=torch.int32, device=self.device)
-            rc = L.crl_reply_margin(stream, vp(priors_out.data_ptr()), vp(counts_ptr), b,
-                                    vp(self._reply_margin_dev.data_ptr()), 0 if stats_out is None else 1,
-                                    vp(lst.data_ptr()))
-            if rc != 0:
-                raise _lib.HipLibraryError("crl_reply_margin failed (%d)" % rc)
+            _lib.reply_margin(priors_out, counts_ptr, b, self._reply_margin_dev, 0 if stats_out is None else 1, lst)
             ws = self._trunk_workspace(bp)
             ev = self._trunk_event("f16x3 indexed")
-            rc = L.crl_trunk_forward_indexed(stream, self.filters, vp(planes_p.data_ptr()), vp(self._wtiles3.data_ptr()),
-                                             vp(self._wbias.data_ptr()), bp, self.blocks, vp(self._head_w.data_ptr()),
-                                             vp(self._head_b.data_ptr()), vp(hp_full.data_ptr()), vp(lst.data_ptr()),
-                                             vp(ws.data_ptr() if ws is not None else None), ws.numel() if ws is not None else 0)
-            if rc != 0:
-                raise _lib.HipLibraryError("crl_trunk_forward_indexed failed (%d)" % rc)
+            _lib.trunk_forward_indexed(self.filters, planes_p, self._wtiles3, self._wbias, bp, self.blocks, self._head_w,
+                                       self._head_b, hp_full, lst, ws, ws.numel() if ws is not None else 0)
             if ev is not None:
                 ev[2].record()
             heads(hp_full[:b])
@@ -864,7 +723,6 @@ class ChessModel(object):
         """Allocate what an evaluation of ``n_boards`` keeps between calls (the hybrid mode's device list with its
         running counter) NOW: LockstepEngine calls this before it captures its hipGraph, so that no buffer
         is created -- and zero-filled at every replay -- inside the captured step."""
-        from . import _lib
         bp = (int(n_boards) + 3) // 4 * 4
         if self.fused and bp not in self._fallback:
             self._fallback[bp] = torch.zeros(_lib.LIST_HEADER + bp, dtype=torch.int32, device=self.device)
@@ -881,8 +739,7 @@ class ChessModel(object):
     def raw_priors_supported(self, n_boards):
         """Whether a batch of ``n_boards`` is served by the sliced heads, i.e. may leave the softmax
         normalisation to the search kernels (``forward_legal_into(..., stats_out=...)``)."""
-        from . import _lib
-        return bool(self.fused and _lib.lib().crl_heads_raw_supported(int(n_boards)))
+        return bool(self.fused and _lib.heads_raw_supported(n_boards))
 
     @torch.no_grad()
     def forward_into(self, planes, pol_out, val_out):

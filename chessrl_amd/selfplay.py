@@ -280,24 +280,11 @@ class SelfPlayRunner(object):
         self.boundaries += 1
         if self.GUARD_EVERY and self.boundaries % self.GUARD_EVERY == 0:
             # an evaluator that chose its arithmetic on a probe (ChessModel precision="auto" -> "f16") is shown the
-            # tower inputs this search has just evaluated and may leave that mode (model.py: guard_check)
-            check = getattr(eng.evaluator, "guard_check", None)
+            # tower inputs this search has just evaluated -- with their legal labels, where the engine has them -- and may
+            # leave that mode or widen its reply margin (model.py: check_on_run)
+            check = getattr(eng.evaluator, "check_on_run", None)
             if check is not None and eng.bitplanes:
-                before = getattr(eng.evaluator, "precision", None)
-                margin = getattr(eng.evaluator, "reply_margin", None)
-                d = check(eng.planes_s2)
-                rule = getattr(eng.evaluator, "reply_rule_check", None)
-                if before == "hybrid" and rule is not None and eng.legal_priors:
-                    # ... and the reply rule itself on the same positions: a board that chooses another reply in f16 than in
-                    # f16x3 must be one the margin lists (model.py: reply_rule_check; widens the margin at once if not)
-                    rule(eng.planes_s2, eng._lab_s2[0], eng._lab_s2[1])
-                if before == "hybrid" and getattr(eng.evaluator, "reply_margin", None) != margin:
-                    log.info("hybrid reply margin widened from %.3e to %.3e (log-policy distance of f16 on this run's own "
-                             "tree leaves)", margin, eng.evaluator.reply_margin)
-                if d is not None and getattr(eng.evaluator, "precision", None) != before:
-                    log.warning("tower precision guard: |f16 - f16x3| = %.2e on this run's own tree leaves (tolerance "
-                                "%.1e): %s -> %s from the next move on", d, eng.evaluator.GUARD_TOL, before,
-                                eng.evaluator.precision)
+                check(eng.planes_s2, *(eng._lab_s2[:2] if eng.legal_priors else ()))
         return live
 
     GUARD_EVERY = 8          # move boundaries between two guard checks (one f16 + one f16x3 evaluation of the batch:

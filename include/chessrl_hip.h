@@ -305,7 +305,7 @@ int  crl_wave_stats(crl_ctx *ctx, int32_t *waves /*G*/, int32_t *short_waves /*G
  * image the kernel keeps in LDS, so that its weight DMA copies contiguous blocks: row r of a
  * plane holds output channel (r & ~31) + 8*((r & 15) >> 2) + 4*((r >> 4) & 1) + (r & 3), and the
  * 16-byte chunk with input channels 8c .. 8c+7 of that row sits at position c ^ ((-(r >> 2)) & 3)
- * (chessrl_amd/model.py:_pack_fused is the reference packer); the stem has 128 input channels, every
+ * (chessrl_amd/packing.py:pack_trunk is the reference packer); the stem has 128 input channels, every
  * other conv `filters`; dev_bias_f32 is [1+2*n_blocks][filters].
  * Outputs (either may be NULL): dev_out_f32 = fp32 trunk activations [n_boards][8][8][filters];
  * dev_head_out_f32 = [n_boards][192] floats after ReLU: [0,128) the policy head in Keras Flatten

@@ -11,7 +11,7 @@ The kernels run both products on fp16 MFMAs over split operands (heads.hpp:10-13
 hi = fp16(x), lo = fp16(x - hi) (fp16 subnormals kept), and  W.h = Whi.hhi + Wlo.hhi + Whi.hlo  is accumulated in
 fp32 on top of the bias.  This module applies the same roundings in float64, so that what is left between a kernel
 and ``mode="split"`` is the kernel's fp32 summation order.  It works from the Keras-layout weight dict
-(oracle/tower_oracle.init_weights) and does NOT go through chessrl_amd.model.ChessModel._pack_dense / _pack_split:
+(oracle/tower_oracle.init_weights) and does NOT go through chessrl_amd.packing.pack_dense / pack_split:
 a packing bug is not shared by kernel and reference.  ``unpack_split`` inverts the documented fragment layout
 independently (heads.hpp:15-18), for the tests of the packing itself.
 

@@ -9,7 +9,7 @@ summation order (~1e-6 relative), so a comparison can see one wrong weight, bias
 Everything is plain torch float64 on ``device`` (the GPU tests run it on the card).  A 3x3 convolution is
 nine shifted ``[B*64, Cin] x [Cin, F]`` matmuls over an explicitly zero-bordered input -- no cuDNN / MIOpen.
 BatchNorm is folded HERE, in float64, from the Keras-layout weight dict (oracle/tower_oracle.init_weights),
-not by chessrl_amd.model._fold / _pack_fused: a folding or packing bug is not shared by kernel and reference.
+not by chessrl_amd.packing.fold / pack_trunk: a folding or packing bug is not shared by kernel and reference.
 "exact" runs on that float64 fold.  The rounded modes start from the weights as the host stores them: folded in
 fp32 (W32 = k * s, s = gamma / sqrt(var + eps), b32 = (b - mean) * s + beta: torch fp32 on the CPU, the operation
 order of the host), then Whi = fp16(W32), Wlo = fp16(W32 - Whi); biases and head weights are those fp32 values.

@@ -23,7 +23,6 @@ zero, the same at ~1e-3 (lo in fp16 subnormals) and at ~1e3.
 The probability tests record the relative error per bin of 10 in depth (test_zz_print_measured prints it); what slope
 to expect from __expf, and what an exp with a higher-precision argument reduction would give, stands at PROB_BOUND.
 """
-import ctypes
 
 import numpy as np
 import pytest
@@ -130,26 +129,21 @@ def _call(model, kind, act, n, scratch, labels=None, counts=None, value=True, im
     """One C-ABI call on the first n rows of act.  kind: "full" | "legal" | "raw".  Every output buffer carries
     ``guard`` rows behind the batch that must stay untouched.  Returns (policy / priors [n][...], value [n] or
     None, scratch [n][16] or None)."""
-    L = _lib().lib()
-    vp = ctypes.c_void_p
+    L = _lib()
     assert act.dtype == torch.float32 and act.is_contiguous() and act.shape[0] >= n and act.shape[1] == 192
     pol = torch.full((n + guard, 1968 if kind == "full" else 256), SENT, device=DEV)
     val = torch.full((n + guard,), SENT, device=DEV) if value else None
     st = torch.full((n + guard, 16), SENT, device=DEV) if scratch else None
     image = model._pol_wp if image is None else image
     bias = model._pol_bias if bias is None else bias
-    common = (vp(torch.cuda.current_stream().cuda_stream), vp(act.data_ptr()), n, vp(image.data_ptr()),
-              vp(bias.data_ptr()), vp(model._val_w1p.data_ptr()), vp(model._val_b1.data_ptr()),
-              vp(model._val_w2.data_ptr()))
-    out = (vp(pol.data_ptr()), vp(val.data_ptr() if value else None), vp(st.data_ptr() if scratch else None))
+    common = (act, n, image, bias, model._val_w1p, model._val_b1, model._val_w2)
     if kind == "full":
-        rc = L.crl_heads_forward(*common, *out)
+        L.heads_forward(*common, pol, val, st)
     else:
         assert labels.dtype == torch.int16 and labels.shape[0] >= n and labels.shape[1] == 256
         assert counts.dtype == torch.int32 and counts.shape[0] >= n
-        fn = L.crl_heads_forward_legal if kind == "legal" else L.crl_heads_forward_legal_raw
-        rc = fn(*common, vp(labels.data_ptr()), vp(counts.data_ptr()), *out)
-    assert rc == 0
+        fn = L.heads_forward_legal if kind == "legal" else L.heads_forward_legal_raw
+        fn(*common, labels, counts, pol, val, st)
     torch.cuda.synchronize()
     assert (pol[n:] == SENT).all(), "policy rows behind the batch were written"
     assert val is None or (val[n:] == SENT).all(), "values behind the batch were written"
@@ -164,15 +158,8 @@ def _sliced(st):
     return bool(touched.all())
 
 
-class _SlicedMax(object):
-    def __init__(self, boards):
-        self.boards = boards
-
-    def __enter__(self):
-        _lib().lib().crl_heads_set_sliced_max(self.boards)
-
-    def __exit__(self, *exc):
-        _lib().lib().crl_heads_set_sliced_max(2048)
+def _SlicedMax(boards):
+    return _lib().heads_set_sliced_max(boards)
 
 
 def _windows(rows, seed=1):
@@ -514,11 +501,11 @@ def test_dispatch_boundary_2048_2049_against_the_reference(kind):
     the last with one live wave).  Every board against the reference, in both forms."""
     e = _edge_runs(kind)
     P, model, act = e["P"], e["model"], e["act"]
-    assert _lib().lib().crl_heads_raw_supported(2048) == 1 and _lib().lib().crl_heads_raw_supported(2049) == 0
+    assert _lib().heads_raw_supported(2048) is True and _lib().heads_raw_supported(2049) is False
     with _SlicedMax(4096):                                                        # 2049 boards forced into slices
         p_f, v_f, st_f = _call(model, "full", act, 2049, True)
         assert _sliced(st_f)
-    assert _lib().lib().crl_heads_raw_supported(2049) == 0                        # (restored)
+    assert _lib().heads_raw_supported(2049) is False                              # (restored)
     p1, v1, _ = _call(model, "full", act, 2048, False)                            # 2048 boards one-pass
     assert _same_bits(p_f[:2048], e["sliced"][0]) and _same_bits(v_f[:2048], e["sliced"][1])
     assert _same_bits(p1, e["onepass"][0][:2048]) and _same_bits(v1, e["onepass"][1][:2048])

@@ -1,7 +1,6 @@
 """GPU: the measurement plumbing of round 6 must not change what is measured -- stamps captured into the step's
 hipGraph (crl_stamp), the steps-per-graph knob -- plus the advisor's findings of round 5 on the tower seam
 (workspace size checked by the library, the reply margin's guards, the guard's stickiness)."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -73,28 +72,25 @@ def test_the_library_refuses_a_workspace_that_is_too_small_for_the_batch():
     from chessrl_amd import _lib
     from chessrl_amd.model import ChessModel
     m = ChessModel(blocks=1, filters=256, seed=2, precision="f16x3")
-    L, vp = _lib.lib(), ctypes.c_void_p
     n = 8
-    need = int(L.crl_trunk_workspace_bytes(256, n, _lib.TRUNK_BITPLANES | _lib.TRUNK_SPLIT))
+    need = _lib.trunk_workspace_bytes(256, n, _lib.TRUNK_BITPLANES | _lib.TRUNK_SPLIT)
     assert need == 2 * n * 64 * 1024
     planes = torch.zeros((n, 128), dtype=torch.int64, device="cuda")
     heads = torch.zeros((n, 192), dtype=torch.float32, device="cuda")
     ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    st = vp(torch.cuda.current_stream().cuda_stream)
 
     def call(nbytes):
-        return L.crl_trunk_forward_x(st, 256, _lib.TRUNK_BITPLANES | _lib.TRUNK_SPLIT, vp(planes.data_ptr()),
-                                     vp(m._wtiles3.data_ptr()), vp(m._wbias.data_ptr()), None, n, 1,
-                                     vp(m._head_w.data_ptr()), vp(m._head_b.data_ptr()), vp(heads.data_ptr()),
-                                     vp(ws.data_ptr()), nbytes)
-    assert call(need) == 0
-    assert call(need - 1) == -1 and call(0) == -1                    # CRL_ERR_ARG, nothing launched
+        _lib.trunk_forward_x(256, _lib.TRUNK_BITPLANES | _lib.TRUNK_SPLIT, planes, m._wtiles3, m._wbias, None, n, 1,
+                             m._head_w, m._head_b, heads, ws, nbytes)
+    call(need)
+    for nbytes in (need - 1, 0):                                     # CRL_ERR_ARG, nothing launched
+        with pytest.raises(_lib.HipLibraryError, match=r"crl_trunk_forward_x failed \(-1\)"):
+            call(nbytes)
     lst = torch.zeros(_lib.LIST_HEADER + n, dtype=torch.int32, device="cuda")
     lst[0] = 1
-    for nbytes, rc in ((need, 0), (need // 2, -1)):
-        assert L.crl_trunk_forward_indexed(st, 256, vp(planes.data_ptr()), vp(m._wtiles3.data_ptr()), vp(m._wbias.data_ptr()),
-                                           n, 1, vp(m._head_w.data_ptr()), vp(m._head_b.data_ptr()), vp(heads.data_ptr()),
-                                           vp(lst.data_ptr()), vp(ws.data_ptr()), nbytes) == rc
+    _lib.trunk_forward_indexed(256, planes, m._wtiles3, m._wbias, n, 1, m._head_w, m._head_b, heads, lst, ws, need)
+    with pytest.raises(_lib.HipLibraryError, match=r"crl_trunk_forward_indexed failed \(-1\)"):
+        _lib.trunk_forward_indexed(256, planes, m._wtiles3, m._wbias, n, 1, m._head_w, m._head_b, heads, lst, ws, need // 2)
     torch.cuda.synchronize()
     # the model lends ONE buffer, sized for the largest batch it has seen, to every batch size
     a = m._trunk_workspace(64)

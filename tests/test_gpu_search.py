@@ -385,11 +385,8 @@ def _fused_trunk_vs_pytorch_trunk(filters, n_boards, precision):
     if n_boards == 8:
         # both geometries accumulate every output in the same order: identical trunk bits
         from chessrl_amd import _lib
-        _lib.lib().crl_trunk_set_small_batch(0)
-        try:
+        with _lib.trunk_set_small_batch(0):
             trunk_big, heads_big = model._run_fused(planes, want_trunk=True)
-        finally:
-            _lib.lib().crl_trunk_set_small_batch(1)
         assert torch.equal(trunk, trunk_big)
         assert (heads - heads_big).abs().max().item() <= 1e-5 * max(1.0, heads.abs().max().item())
 
@@ -402,7 +399,6 @@ def test_mfma_dense_heads_match_the_fp32_dense_layers(n_boards, sliced):
     incl. batches that are not a multiple of the 16-board blocks and the policy-only call; in the
     one-pass form and (scratch given: batches up to 1024 boards) as label slices + normalising pass
     with the value head riding along."""
-    import ctypes
     from chessrl_amd import _lib
     from chessrl_amd.model import ChessModel
     w = tower_oracle.init_weights(2, 64, seed=21, randomize_bn=True)
@@ -417,16 +413,11 @@ def test_mfma_dense_heads_match_the_fp32_dense_layers(n_boards, sliced):
     with torch.no_grad():
         ref_p = torch.softmax(n.policy_fc(hp[:, :128]), -1)
         ref_v = torch.tanh(n.value_fc2(F.relu(n.value_fc1(hp[:, 128:])))[:, 0])
-    vp = ctypes.c_void_p
     scratch = torch.full((n_boards + 3, 16), -7.0, device="cuda")
 
     def run(pol, val):
-        rc = _lib.lib().crl_heads_forward(
-            vp(torch.cuda.current_stream().cuda_stream), vp(hp.data_ptr()), n_boards,
-            vp(model._pol_wp.data_ptr()), vp(model._pol_bias.data_ptr()), vp(model._val_w1p.data_ptr()),
-            vp(model._val_b1.data_ptr()), vp(model._val_w2.data_ptr()), vp(pol.data_ptr()),
-            vp(val.data_ptr() if val is not None else None), vp(scratch.data_ptr() if sliced else None))
-        assert rc == 0
+        _lib.heads_forward(hp, n_boards, model._pol_wp, model._pol_bias, model._val_w1p, model._val_b1, model._val_w2,
+                           pol, val, scratch if sliced else None)
         torch.cuda.synchronize()
 
     pol = torch.full((n_boards + 3, 1968), -7.0, device="cuda")                 # guard rows stay untouched
@@ -523,7 +514,6 @@ def test_layerwise_split_trunk_of_256_filters_both_plane_formats_trunk_output_an
 def test_legal_priors_head_writes_the_full_policy_at_the_listed_labels(n_boards, sliced):
     """crl_heads_forward_legal: priors[b][j] == policy[b][labels[b][j]] bit for bit for j < counts[b]
     (0, 1, typical and the maximum 218 labels per board), nothing written past the count."""
-    import ctypes
     from chessrl_amd import _lib
     from chessrl_amd.model import ChessModel
     model = ChessModel(weights=tower_oracle.init_weights(2, 64, seed=22, randomize_bn=True))
@@ -535,19 +525,15 @@ def test_legal_priors_head_writes_the_full_policy_at_the_listed_labels(n_boards,
     for b in range(n_boards):
         labels[b, :counts[b]] = rng.permutation(1968)[:counts[b]]
     lab_d, cnt_d = torch.from_numpy(labels.view(np.int16)).cuda(), torch.from_numpy(counts).cuda()
-    vp = ctypes.c_void_p
-    args = (vp(torch.cuda.current_stream().cuda_stream), vp(hp.data_ptr()), n_boards,
-            vp(model._pol_wp.data_ptr()), vp(model._pol_bias.data_ptr()), vp(model._val_w1p.data_ptr()),
-            vp(model._val_b1.data_ptr()), vp(model._val_w2.data_ptr()))
+    args = (hp, n_boards, model._pol_wp, model._pol_bias, model._val_w1p, model._val_b1, model._val_w2)
     pol = torch.zeros((n_boards, 1968), device="cuda")
     val = torch.zeros((n_boards,), device="cuda")
     scratch = torch.zeros((n_boards, 16), device="cuda")
-    sc = vp(scratch.data_ptr() if sliced else None)     # both calls in the same form: identical values
-    assert _lib.lib().crl_heads_forward(*args, vp(pol.data_ptr()), vp(val.data_ptr()), sc) == 0
+    sc = scratch if sliced else None                     # both calls in the same form: identical values
+    _lib.heads_forward(*args, pol, val, sc)
     pri = torch.full((n_boards + 2, 256), -7.0, device="cuda")
     val2 = torch.full((n_boards + 2,), -7.0, device="cuda")
-    assert _lib.lib().crl_heads_forward_legal(*args, vp(lab_d.data_ptr()), vp(cnt_d.data_ptr()),
-                                              vp(pri.data_ptr()), vp(val2.data_ptr()), sc) == 0
+    _lib.heads_forward_legal(*args, lab_d, cnt_d, pri, val2, sc)
     torch.cuda.synchronize()
     pol, pri = pol.cpu().numpy(), pri.cpu().numpy()
     for b in range(n_boards):

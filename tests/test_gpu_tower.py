@@ -225,12 +225,8 @@ def test_reply_margin_lists_the_close_calls_and_the_indexed_trunk_evaluates_exac
     formats: probabilities and logits; boards with fewer than two legal moves never listed), and
     crl_trunk_forward_indexed: listed rows of the head activations become the split-precision kernel's bits,
     every other row keeps the bits it had (64, 128 and 256 filters, lists that do not fill a workgroup)."""
-    import ctypes
     from chessrl_amd import _lib, model as M
     from chessrl_amd.model import ChessModel
-    vp = ctypes.c_void_p
-    L = _lib.lib()
-    st = vp(torch.cuda.current_stream().cuda_stream)
     rng = np.random.default_rng(3)
     n = 300
     counts = rng.integers(0, 60, n).astype(np.int32)
@@ -254,8 +250,7 @@ def test_reply_margin_lists_the_close_calls_and_the_indexed_trunk_evaluates_exac
         lst = torch.full((H + n,), -5, dtype=torch.int32, device="cuda")
         lst[2:4] = torch.tensor([2 ** 31 - 3, 0], dtype=torch.int32)  # the 64-bit running total, about to pass 2^31
         thr_dev = torch.tensor([thr], dtype=torch.float32, device="cuda")        # the margin is read from device memory
-        assert L.crl_reply_margin(st, vp(torch.from_numpy(rows).cuda().data_ptr()), vp(torch.from_numpy(counts).cuda().data_ptr()),
-                                  n, vp(thr_dev.data_ptr()), int(logits), vp(lst.data_ptr())) == 0
+        _lib.reply_margin(torch.from_numpy(rows).cuda(), torch.from_numpy(counts).cuda(), n, thr_dev, int(logits), lst)
         got = lst.cpu().numpy()
         listed = set(got[H:H + got[0]].tolist())
         assert got[1] == -5 and int(got[2:4].view(np.int64)[0]) == 2 ** 31 - 3 + int(got[0]) and len(listed) == got[0]
@@ -279,10 +274,8 @@ def test_reply_margin_lists_the_close_calls_and_the_indexed_trunk_evaluates_exac
             lst[_lib.LIST_HEADER:_lib.LIST_HEADER + len(pick)] = torch.tensor(pick, dtype=torch.int32)[torch.randperm(len(pick))] if pick else 0
             hp = h16.clone()
             ws = m._trunk_workspace(n)                               # 256 filters: the layer-wise kernels' activation images
-            assert L.crl_trunk_forward_indexed(st, filters, vp(planes.data_ptr()), vp(m._wtiles3.data_ptr()),
-                                               vp(m._wbias.data_ptr()), n, blocks, vp(m._head_w.data_ptr()),
-                                               vp(m._head_b.data_ptr()), vp(hp.data_ptr()), vp(lst.data_ptr()),
-                                               vp(ws.data_ptr() if ws is not None else None), ws.numel() if ws is not None else 0) == 0
+            _lib.trunk_forward_indexed(filters, planes, m._wtiles3, m._wbias, n, blocks, m._head_w, m._head_b, hp, lst, ws,
+                                       ws.numel() if ws is not None else 0)
             torch.cuda.synchronize()
             mask = torch.zeros(n, dtype=torch.bool, device="cuda")
             mask[pick] = True
@@ -443,13 +436,11 @@ def test_trunk_outputs_do_not_change_while_another_process_uses_the_gpu(disturba
     from chessrl_amd import model as M
     from chessrl_amd.model import ChessModel
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    import ctypes
     import time
     from chessrl_amd import _lib
     disturber = subprocess.Popen([sys.executable, os.path.join(root, "tools", "trunk_stability_probe.py"),
                                   disturbance, "100000"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     time.sleep(8)                                                    # let it get going (imports, allocation)
-    vp = ctypes.c_void_p
     try:
         for blocks, filters, n in ((1, 64, 256), (1, 64, 2048), (2, 128, 256), (2, 128, 2048), (1, 256, 256), (1, 256, 1024)):
             m = ChessModel(blocks=blocks, filters=filters, seed=5, precision="f16")
@@ -473,12 +464,9 @@ def test_trunk_outputs_do_not_change_while_another_process_uses_the_gpu(disturba
             seen = set()
             for _ in range(40):
                 hp = base.clone()
-                assert _lib.lib().crl_trunk_forward_indexed(
-                    vp(torch.cuda.current_stream().cuda_stream), filters, vp(planes.data_ptr()), vp(m._wtiles3.data_ptr()),
-                    vp(m._wbias.data_ptr()), n, blocks, vp(m._head_w.data_ptr()), vp(m._head_b.data_ptr()),
-                    vp(hp.data_ptr()), vp(lst.data_ptr()),
-                    vp(m._trunk_workspace(n).data_ptr() if m._trunk_workspace(n) is not None else None),
-                    m._trunk_workspace(n).numel() if m._trunk_workspace(n) is not None else 0) == 0
+                ws = m._trunk_workspace(n)
+                _lib.trunk_forward_indexed(filters, planes, m._wtiles3, m._wbias, n, blocks, m._head_w, m._head_b, hp, lst,
+                                           ws, ws.numel() if ws is not None else 0)
                 torch.cuda.synchronize()
                 seen.add(hashlib.md5(hp.cpu().numpy().tobytes()).hexdigest())
             assert len(seen) == 1, (blocks, filters, n, "indexed", len(seen))

@@ -16,7 +16,6 @@ percentile, "f16x3" (every block input and conv1 output carried to 2^-22) at 1e-
 Every comparison runs on ALL boards of the batch: every slot of a workgroup (board index mod NB) and the first
 and last workgroup are among them.
 """
-import ctypes
 
 import numpy as np
 import pytest
@@ -96,20 +95,11 @@ def _expected_name(kern, bits):
 
 
 def _kernel_name(filters, n, flags):
-    buf = ctypes.create_string_buffer(256)
-    assert _lib().lib().crl_trunk_kernel_name(filters, n, flags, buf, 256) == 0
-    return buf.value.decode()
+    return _lib().trunk_kernel_name(filters, n, flags)
 
 
-class _SmallBatch(object):
-    def __init__(self, on):
-        self.on = on
-
-    def __enter__(self):
-        _lib().lib().crl_trunk_set_small_batch(self.on)
-
-    def __exit__(self, *exc):
-        _lib().lib().crl_trunk_set_small_batch(1)
+def _SmallBatch(on):
+    return _lib().trunk_set_small_batch(on)
 
 
 def _bits_from_planes(planes):
@@ -173,13 +163,8 @@ def _run(model, mode, planes, n_blocks, image=None, bias=None):
     out = torch.full((n, 8, 8, f), float("nan"), dtype=torch.float32, device=DEV)
     heads = torch.full((n, 192), float("nan"), dtype=torch.float32, device=DEV)
     ws = model._trunk_workspace(n) if split else None
-    vp = ctypes.c_void_p
-    rc = L.lib().crl_trunk_forward_x(
-        vp(torch.cuda.current_stream().cuda_stream), f, flags, vp(planes.data_ptr()), vp(image.data_ptr()),
-        vp(bias.data_ptr()), vp(out.data_ptr()), n, n_blocks, vp(model._head_w.data_ptr()),
-        vp(model._head_b.data_ptr()), vp(heads.data_ptr()), vp(ws.data_ptr() if ws is not None else None),
-        ws.numel() if ws is not None else 0)
-    assert rc == 0
+    L.trunk_forward_x(f, flags, planes, image, bias, out, n, n_blocks, model._head_w, model._head_b, heads, ws,
+                      ws.numel() if ws is not None else 0)
     torch.cuda.synchronize()
     assert torch.isfinite(out).all() and torch.isfinite(heads).all()
     return out, heads

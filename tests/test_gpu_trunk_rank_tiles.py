@@ -41,15 +41,11 @@ def _both_kernels(model, planes, k):
     n = planes.shape[0]
     flags = L.TRUNK_BITPLANES if planes.dtype == torch.int64 else 0
     bits = 1 if planes.dtype == torch.int64 else 0
-    try:
-        L.lib().crl_trunk_set_small_batch(0)
+    with L.trunk_set_small_batch(0):
         assert ta._kernel_name(FILTERS, n, flags) == ta._x16_name(*NB4, bits=bits)
         x4, h4 = ta._run(model, "f16", planes, k)
-        L.lib().crl_trunk_set_small_batch(1)
-        assert ta._kernel_name(FILTERS, n, flags) == ta._x16_name(*NB2, bits=bits)
-        x2, h2 = ta._run(model, "f16", planes, k)
-    finally:
-        L.lib().crl_trunk_set_small_batch(1)
+    assert ta._kernel_name(FILTERS, n, flags) == ta._x16_name(*NB2, bits=bits)           # (the default, restored)
+    x2, h2 = ta._run(model, "f16", planes, k)
     return x4, h4, x2, h2
 
 

@@ -1,5 +1,5 @@
 """CPU: oracle/heads_reference.py checking itself, and the host-side packing of the dense heads
-(ChessModel._pack_split / _pack_dense) against the layout chessrl_amd/csrc/heads.hpp documents.
+(chessrl_amd.packing: pack_split / pack_dense) against the layout chessrl_amd/csrc/heads.hpp documents.
 
 The GPU comparisons (tests/test_gpu_heads_arith.py) rest on what is established here: that "split" is the fp32 layers'
 arithmetic to ~2^-22 of a logit's condition, that each of its three products matters (a dropped one is >= 100x worse),
@@ -87,11 +87,11 @@ def test_modes_and_drops_are_checked():
 
 @pytest.mark.parametrize("tiles,ksteps", [(128, 4), (16, 2)])
 def test_unpack_split_inverts_pack_split_for_every_element(tiles, ksteps):
-    from chessrl_amd.model import ChessModel
+    from chessrl_amd import packing
     rng = np.random.default_rng(tiles)
     x = torch.from_numpy((rng.normal(0, 1, (tiles * 16, ksteps * 32)) * 10.0 ** rng.integers(-6, 3, (tiles * 16, 1)))
                          .astype(np.float32))
-    image = ChessModel._pack_split(x, tiles, ksteps)
+    image = packing.pack_split(x, tiles, ksteps)
     assert image.dtype == torch.float16 and image.numel() == 2 * x.numel()
     hi, lo = hr.unpack_split(image, tiles, ksteps)
     ehi = x.half()
@@ -107,10 +107,10 @@ def test_unpack_split_inverts_pack_split_for_every_element(tiles, ksteps):
 
 
 def test_pack_dense_places_everything_where_the_kernels_read_it(sets):
-    from chessrl_amd.model import ChessModel
+    from chessrl_amd import packing
     w, _ = sets["flat"]
     P = hr.prepare(w)
-    pol_wp, pol_bias, val_w1p, val_b1, val_w2 = object.__new__(ChessModel)._pack_dense(w)
+    pol_wp, pol_bias, val_w1p, val_b1, val_w2 = packing.pack_dense(w)
     hi, lo = hr.unpack_split(pol_wp, 128, 4)                            # [2048 labels][128 inputs]
     assert torch.equal(hi[:1968].double(), P.policy.whi.t()) and torch.equal(lo[:1968].double(), P.policy.wlo.t())
     assert not hi[1968:].any() and not lo[1968:].any()                  # the pad labels: zero weights ...

@@ -278,13 +278,13 @@ def test_bench_gpus_2_starts_two_ranks_and_checks_the_world(tmp_path):
 
 
 def test_dense_head_weight_packing_is_the_fragment_order_the_kernel_reads():
-    """ChessModel._pack_split -> [tile][k-step][hi|lo][lane = 16 q + r][8 halves] with the lane
+    """packing.pack_split -> [tile][k-step][hi|lo][lane = 16 q + r][8 halves] with the lane
     holding x[16 tile + r][32 s + 8 q + e] (csrc/heads.hpp), and hi + lo == x to 2^-22."""
     import torch
-    from chessrl_amd.model import ChessModel
+    from chessrl_amd import packing
     g = torch.Generator().manual_seed(0)
     x = torch.randn((48, 64), generator=g) * 0.3                  # 3 tiles of 16 units, 2 k-steps
-    packed = ChessModel._pack_split(x, 3, 2).reshape(3, 2, 2, 64, 8).float()
+    packed = packing.pack_split(x, 3, 2).reshape(3, 2, 2, 64, 8).float()
     for t in range(3):
         for s in range(2):
             for lane in (0, 5, 16, 37, 63):
@@ -296,28 +296,25 @@ def test_dense_head_weight_packing_is_the_fragment_order_the_kernel_reads():
 
 
 def test_trunk_weight_image_is_the_plane_order_the_header_documents():
-    """ChessModel._pack_fused (CPU tensors, no GPU): the fp16 image handed to crl_trunk_forward is
+    """packing.pack_weights (CPU tensors, no GPU): the fp16 image handed to crl_trunk_forward is
     [conv][tap][in-ch/32][F rows][4 chunks][8 in] with row r holding output channel
     (r & ~31) + 8*((r & 15) >> 2) + 4*((r >> 4) & 1) + (r & 3) and input channels 8c..8c+7 at chunk
     position c ^ ((-(r >> 2)) & 3) (include/chessrl_hip.h) -- checked element by element against the
     BatchNorm-folded kernels, stem (128 input planes incl. the zero pad) and residual convs."""
     import torch
-    from chessrl_amd import model as M
+    from chessrl_amd import packing as M
     from oracle import tower_oracle
     F_, blocks = 64, 1
     w = tower_oracle.init_weights(blocks, F_, seed=3, randomize_bn=True)
-    m = M.ChessModel.__new__(M.ChessModel)
-    m.filters, m.blocks, m.device = F_, blocks, torch.device("cpu")
-    m.precision_requested = "auto"                                   # packs both images
-    m._pack_fused(w)
-    img = m._wtiles.float().numpy()
-    assert m._wtiles.dtype == torch.float16
+    wtiles, wtiles3 = M.pack_weights(w, blocks, F_, want_f16=True, want_x3=True)[:2]    # both images, as "auto" packs
+    img = wtiles.float().numpy()
+    assert wtiles.dtype == torch.float16
     convs = [("stem", None), ("block0.conv1", "block0.bn1"), ("block0.conv2", "block0.bn2")]
     assert img.size == 9 * 128 * F_ + 2 * 9 * F_ * F_
     rng = np.random.default_rng(0)
     off = 0
     for conv, bn in convs:
-        k, _ = M._fold(w, conv, bn)                                  # [O][I][ky][kx] fp32
+        k, _ = M.fold(w, conv, bn)                                   # [O][I][ky][kx] fp32
         k = k.half().float().numpy()
         cin = 128 if conv == "stem" else F_
         planes = img[off:off + 9 * cin * F_].reshape(9, cin // 32, F_, 4, 8)
@@ -332,11 +329,11 @@ def test_trunk_weight_image_is_the_plane_order_the_header_documents():
     assert sorted({(r & ~31) + 8 * ((r & 15) >> 2) + 4 * ((r >> 4) & 1) + (r & 3) for r in range(F_)}) == list(range(F_))
     # the split-precision image (CRL_TRUNK_SPLIT): per tap the planes of Whi, then of Wlo = fp16(W - Whi),
     # each in the same plane order; hi + lo carries W to ~2^-22
-    img3 = m._wtiles3.float().numpy()
+    img3 = wtiles3.float().numpy()
     assert img3.size == 2 * (9 * 128 * F_ + 2 * 9 * F_ * F_)
     off = 0
     for conv, bn in convs:
-        k, _ = M._fold(w, conv, bn)
+        k, _ = M.fold(w, conv, bn)
         k = k.numpy()
         hi = k.astype(np.float16).astype(np.float32)
         lo = (k - hi).astype(np.float16).astype(np.float32)
@@ -355,15 +352,13 @@ def test_trunk_weight_image_is_the_plane_order_the_header_documents():
     # [conv][in-ch/32][tap][Whi, Wlo][256 rows][4 chunks][8 in] (include/chessrl_hip.h: crl_trunk_workspace_bytes)
     F_ = 256
     w = tower_oracle.init_weights(1, F_, seed=5, randomize_bn=True)
-    m = M.ChessModel.__new__(M.ChessModel)
-    m.filters, m.blocks, m.device = F_, 1, torch.device("cpu")
-    m.precision_requested = "f16x3"
-    m._pack_fused(w)
-    img3 = m._wtiles3.float().numpy()
+    wtiles, wtiles3 = M.pack_weights(w, 1, F_, want_f16=False, want_x3=True)[:2]        # as "f16x3" packs
+    assert wtiles.numel() == 8                                       # (the placeholder of an image not asked for)
+    img3 = wtiles3.float().numpy()
     assert img3.size == 2 * (9 * 128 * F_ + 2 * 9 * F_ * F_)
     off = 0
     for conv, bn in convs:
-        k = M._fold(w, conv, bn)[0].numpy()
+        k = M.fold(w, conv, bn)[0].numpy()
         hi = k.astype(np.float16).astype(np.float32)
         parts = [hi, (k - hi).astype(np.float16).astype(np.float32)]
         cin = 128 if conv == "stem" else F_

@@ -141,7 +141,7 @@ def test_scalar_loop_of_the_split_product_agrees_with_the_f16x3_reference(net):
 
 
 def test_rounded_modes_start_from_the_hosts_fp32_fold_bit_for_bit(net):
-    """The emulated modes' weights are the host's stored fp32 values (chessrl_amd.model._fold: what _pack_fused
+    """The emulated modes' weights are the host's stored fp32 values (chessrl_amd.packing.fold: what pack_trunk
     rounds to Whi / Wlo and what the kernels add as biases); the float64 fold is within fp32 rounding of them."""
     from chessrl_amd.model import _fold
     w, _, P = net

@@ -1,13 +1,12 @@
 """Scratch (GPU): HIP-event time of crl_heads_forward (policy + value, policy only) per batch size, in
 the one-pass form and as label slices + normalising pass (scratch given), inside a hipGraph."""
-import ctypes, os, sys
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from chessrl_amd import _lib
 from chessrl_amd.model import ChessModel
 m = ChessModel(blocks=2, filters=64, precision="f16")
-vp = ctypes.c_void_p
-_lib.lib().crl_heads_set_sliced_max(1 << 20)            # the form is chosen by the scratch argument here
+_lib.heads_set_sliced_max(1 << 20)                      # the form is chosen by the scratch argument here
 for n in (64, 256, 512, 1024, 2048, 4096, 8192):
     hp = torch.rand((n, 192), device="cuda")
     pol = torch.empty((n, 1968), device="cuda"); val = torch.empty((n,), device="cuda")
@@ -15,15 +14,12 @@ for n in (64, 256, 512, 1024, 2048, 4096, 8192):
     cnt = torch.full((n,), 30, dtype=torch.int32, device="cuda")
     lab = (torch.arange(256, device="cuda")[None, :] * 7 + torch.arange(n, device="cuda")[:, None]).remainder(1968).to(torch.int16)
     def run(with_value, sliced, legal):
-        sc = vp(scratch.data_ptr() if sliced else None)
-        common = (vp(torch.cuda.current_stream().cuda_stream), vp(hp.data_ptr()), n,
-                  vp(m._pol_wp.data_ptr()), vp(m._pol_bias.data_ptr()), vp(m._val_w1p.data_ptr()), vp(m._val_b1.data_ptr()),
-                  vp(m._val_w2.data_ptr()))
+        sc = scratch if sliced else None
+        common = (hp, n, m._pol_wp, m._pol_bias, m._val_w1p, m._val_b1, m._val_w2)
         if legal:
-            _lib.lib().crl_heads_forward_legal(*common, vp(lab.data_ptr()), vp(cnt.data_ptr()), vp(pri.data_ptr()),
-                                               vp(val.data_ptr() if with_value else None), sc)
+            _lib.heads_forward_legal(*common, lab, cnt, pri, val if with_value else None, sc)
         else:
-            _lib.lib().crl_heads_forward(*common, vp(pol.data_ptr()), vp(val.data_ptr() if with_value else None), sc)
+            _lib.heads_forward(*common, pol, val if with_value else None, sc)
     res = {}
     for sliced in (False, True):
         for legal in (True, False):
