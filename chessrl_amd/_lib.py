@@ -39,6 +39,8 @@ PLANES = 128
 NO_MOVE = 0xFFFF
 RESULT_NONE = 2
 ROLLOUT_GAMES, ROLLOUT_LEAVES, ROLLOUT_SKIPPED = 0, 1, 0xFFFF
+OPP_MAX_DEPTH, OPP_CUT, OPP_SKIPPED = 5, 1, 2     # include/chessrl_hip.h: CRL_OPP_*
+OPP_NODE_LIMIT = 200000   # default node limit per slot of Context.opponent_moves (a first choice)
 FLAG_NUMPY_LEGACY = 1
 WAVE_MAX_THREADS = 64     # include/chessrl_hip.h: CRL_WAVE_MAX_THREADS
 POLICY_FULL, POLICY_LEGAL, POLICY_LEGAL_RAW = 0, 1, 2
@@ -61,7 +63,7 @@ SYMBOLS = [
     "crl_end_move_fetch", "crl_advance_fetch",
     "crl_reroot", "crl_reroot_fetch", "crl_search_begin_kept", "crl_copy_game_tree", "crl_fetch_tree",
     "crl_im2col3x3_f32", "crl_col2im3x3_f32", "crl_stamp", "crl_stamp_clock_khz",
-    "crl_rollout_games", "crl_rollout",
+    "crl_rollout_games", "crl_rollout", "crl_opponent_moves",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
 ]
@@ -234,6 +236,7 @@ def lib():
     L.crl_stamp.argtypes = [vp, vp, u32, u32]
     L.crl_rollout_games.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.crl_rollout.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    L.crl_opponent_moves.argtypes = [vp, vp, i32, ctypes.c_int64, vp, vp, vp, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     L.crl_wave_config.argtypes = [vp, i32]
     L.crl_wave_begin.argtypes = [vp, i32]
@@ -666,6 +669,20 @@ class Context(object):
         vp = ctypes.c_void_p
         self._ck(self._L.crl_rollout(self._h, int(root_source), int(repetitions), int(max_moves), vp(dev_keys),
                                      vp(dev_value), vp(dev_results), vp(dev_plies)), "crl_rollout")
+
+    # ---- the built-in opponent (csrc/opponent.hpp; stockfish.py:23-31, gamestockfish.py:27-41) ------
+    def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT):
+        """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it.
+        Returns (moves u16, scores i32, nodes i64, flags u8); with ``push`` the moves are played."""
+        dp = np.ascontiguousarray(depths, dtype=np.int32)
+        assert dp.shape == (self.G,)
+        moves = np.zeros(self.G, np.uint16)
+        scores = np.zeros(self.G, np.int32)
+        nodes = np.zeros(self.G, np.int64)
+        flags = np.zeros(self.G, np.uint8)
+        self._ck(self._L.crl_opponent_moves(self._h, _ptr(dp), 1 if push else 0, int(node_limit), _ptr(moves),
+                                            _ptr(scores), _ptr(nodes), _ptr(flags)), "crl_opponent_moves")
+        return moves, scores, nodes, flags
 
     # ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------
     def wave_config(self, threads):

@@ -3,6 +3,7 @@
 #include "../../include/chessrl_hip.h"
 #include "search.hpp"
 #include "rollout.hpp"
+#include "opponent.hpp"
 #include "search_wave.hpp"
 #include "tower_x16.hpp"
 #include "tower_layer.hpp"
@@ -24,6 +25,8 @@ using namespace crl;
 static_assert(sizeof(crl_board) == sizeof(Board), "crl_board layout");
 static_assert(CRL_MAX_MOVES == MAX_MOVES && CRL_N_LABELS == N_LABELS && CRL_PLANES == PLANES,
               "header constants");
+static_assert(CRL_OPP_MAX_DEPTH == OPP_MAX_DEPTH && CRL_OPP_CUT == OPP_CUT && CRL_OPP_SKIPPED == OPP_SKIPPED,
+              "opponent constants");
 
 static thread_local std::string g_create_error;
 
@@ -758,6 +761,29 @@ int crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, c
                        repetitions, (float *)dev_value_f32);
     HIP_TRY(ctx, hipGetLastError());
     return CRL_OK;
+}
+
+// ---- the built-in opponent (csrc/opponent.hpp): stockfish.py:23-31, gamestockfish.py:27-41 ---------------------
+int crl_opponent_moves(crl_ctx *ctx, const int32_t *depths, int push, int64_t node_limit, uint16_t *moves,
+                       int32_t *scores, int64_t *nodes, uint8_t *flags)
+{
+    if (!ctx || !depths || !moves || node_limit < 1)
+        return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves: bad argument");
+    const size_t G = ctx->W;
+    for (size_t i = 0; i < G; i++)
+        if (depths[i] < 0 || depths[i] > CRL_OPP_MAX_DEPTH)
+            return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves: a depth outside 0 .. CRL_OPP_MAX_DEPTH");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->t_i32b, depths, G * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LAUNCH(ctx, k_opponent_moves, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_limit, ctx->t_u16a,
+           ctx->t_i32c, dnodes, ctx->t_u8);
+    HIP_TRY(ctx, hipMemcpyAsync(moves, ctx->t_u16a, G * sizeof(u16), hipMemcpyDeviceToHost, s));
+    if (scores) HIP_TRY(ctx, hipMemcpyAsync(scores, ctx->t_i32c, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (nodes) HIP_TRY(ctx, hipMemcpyAsync(nodes, dnodes, G * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (flags) HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->t_u8, G, hipMemcpyDeviceToHost, s));
+    return check_dev_error(ctx);
 }
 
 // ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------------------------

@@ -1,0 +1,232 @@
+// opponent.hpp -- the built-in opponent: a fixed-depth alpha-beta player on the device.  It stands where the
+// reference puts its engine (stockfish.py:23-31 Stockfish.best_move, gamestockfish.py:27-41 the reply inside
+// GameStockfish.move); it is NOT that engine and claims no Elo: results read "against the built-in depth-d opponent".
+//
+// One wavefront (one workgroup) searches one window slot (lane = square, as everywhere in search.hpp); the root is
+// d.cur[g].  Integer work only.  This comment is the specification; tests/opponent_util.py restates it.
+//
+// SEARCH.  Negamax with alpha-beta, depth d = depths[slot] plies, fail-soft (a node returns its best score):
+//     the root window is (-INF, +INF), INF = 32000;
+//     a child is searched with (-beta, -alpha) and scores the negation of what it returns;
+//     a move replaces the best only on a STRICTLY greater score; alpha = max(alpha, score);
+//     the remaining moves of a node are cut when alpha >= beta.
+// The returned move is therefore the FIRST root move, in the root's order, that attains the minimax value, and the
+// returned score is that value: plain minimax with a first-maximum rule gives the same pair.
+//
+// NODE VALUE, in this order, for the node at search ply k (root = 0):
+//     1. generate the legal moves.  This is ONE NODE: the node counter counts wave_movegen calls, the root's included;
+//     2. r = position_result(b, n, in_check, 1): no legal move (mate or stalemate), insufficient material, the
+//        fifty-move claim at clock >= 100, the 75-move rule.  The repetition count handed in is 1: repetition is NOT
+//        looked at below the root (nor at it: a slot whose game has a result, fivefold included, is skipped before);
+//     3. r = mate (the side to move is mated): the value is -(30000 - k).  Any other result (a draw): 0;
+//     4. no result and k = d (no depth remains): the static evaluation;
+//     5. otherwise the search of the moves.
+// Horizon nodes are generated too, so depth d sees a mate delivered by ply d; there is no quiescence search.
+//
+// ORDER OF THE MOVES.  At the root: python-chess generation order, as wave_movegen emits it.  Below the root: a stable
+// partition, tactical moves first, generation order inside each class.  A move is tactical if
+//     its destination holds an enemy piece, or
+//     it is an en-passant capture (a pawn that changes file onto an empty square), or
+//     it is a promotion.
+// (The partition is two ballots per 64 moves and prefix popcounts, like the suffix scan of movegen.hpp.)
+//
+// STATIC EVALUATION, int32, from the side to move: one term per lane, one wave reduction.
+//     material           P 100, N 320, B 330, R 500, Q 900, K 0
+//     ring(sq)           min(file, 7 - file, rank, 7 - rank) = 0 .. 3
+//     position bonus     N 10 * ring, B 5 * ring, R 0, Q 2 * ring, K -10 * ring,
+//                        P 5 * ring + 6 * (ranks advanced from its start rank: rank - 1 for white, 6 - rank for black)
+//     score              (sum over white pieces) - (sum over black pieces), negated when black is to move
+//
+// STRUCTURE.  No device recursion: an explicit stack of per-ply frames in LDS.  A frame holds the node's board, its
+// 256-entry u16 move list, the cursor, the count, alpha, beta and the best score: 608 B, d + 1 <= 6 of them = 3.6 KiB
+// (game_push's scratch shares the bytes: the frames are dead when the move is pushed).  The main loop is
+// `while (nodes < limit)` and every turn generates exactly one node; the unwinding inside a turn strictly
+// decreases the ply.  So the loop is bounded by the node limit by construction: a logic error ends as a flagged cut.
+//
+// NODE LIMIT, per slot.  The limit is tested before every node.  When the count has reached it and the search is not
+// finished, the search ends: the slot returns the best root move among those COMPLETELY searched (and its score), or
+// the first legal move (and the score -INF) if none was, with the flag CRL_OPP_CUT.  A search that finishes with its
+// last permitted node is not cut.  Node counts are deterministic, so the cut is.
+//
+// PER SLOT.  depths[slot] = 0 leaves the slot alone (NO_MOVE, score 0, 0 nodes, flag 0); 1 .. CRL_OPP_MAX_DEPTH
+// searches it.  A slot whose game already has a result returns NO_MOVE, score 0, 0 nodes and CRL_OPP_SKIPPED.  With
+// `push`, the chosen move is pushed through game_push: history, record, ply and result change exactly as by
+// crl_push_moves, repetition included.
+#pragma once
+#include "search.hpp"
+
+namespace crl {
+
+constexpr int OPP_MAX_DEPTH = 5;
+constexpr int OPP_INF = 32000;
+constexpr int OPP_MATE = 30000;
+constexpr uint8_t OPP_CUT = 1, OPP_SKIPPED = 2;
+
+struct __attribute__((aligned(16))) OppFrame {
+    Board b;
+    u16 mv[MAX_MOVES];
+    int32_t cur, n, alpha, beta, best, pad[3];
+};
+static_assert(sizeof(OppFrame) == 608, "OppFrame must be 608 bytes");
+
+union OppLds {
+    OppFrame f[OPP_MAX_DEPTH + 1];
+    WaveLds w;                             // game_push, after the search
+};
+
+// a wave-uniform board read from LDS, moved to scalar registers
+__device__ inline Board uni_board(const Board &x)
+{
+    Board b;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+        b.bb[i] = (u64)(u32)uni((int)(u32)x.bb[i]) | ((u64)(u32)uni((int)(u32)(x.bb[i] >> 32)) << 32);
+    b.white = (u64)(u32)uni((int)(u32)x.white) | ((u64)(u32)uni((int)(u32)(x.white >> 32)) << 32);
+    b.state = (u32)uni((int)x.state);
+    b.pad = 0;
+    return b;
+}
+
+__device__ inline int opp_evaluate(const Board &b, int lane)
+{
+    const int pt = piece_at(b, lane);
+    const int f = lane & 7, r = lane >> 3;
+    const int rf = f < 7 - f ? f : 7 - f, rr = r < 7 - r ? r : 7 - r;
+    const int ring = rf < rr ? rf : rr;
+    const bool white = (b.white >> lane) & 1;
+    int v = 0;
+    if (pt == PAWN) v = 100 + 5 * ring + 6 * (white ? r - 1 : 6 - r);
+    else if (pt == KNIGHT) v = 320 + 10 * ring;
+    else if (pt == BISHOP) v = 330 + 5 * ring;
+    else if (pt == ROOK) v = 500;
+    else if (pt == QUEEN) v = 900 + 2 * ring;
+    else if (pt == KING) v = -10 * ring;
+    if (!white) v = -v;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return st_turn(b.state) ? v : -v;
+}
+
+__device__ inline bool opp_tactical(const Board &b, u64 occ, u64 own, u32 mv)
+{
+    const int from = mv & 63, to = (mv >> 6) & 63;
+    const u64 tb = bit(to);
+    if ((mv >> 12) & 7) return true;
+    if (occ & ~own & tb) return true;
+    return (b.bb[PAWN] & bit(from)) && (from & 7) != (to & 7) && !(occ & tb);
+}
+
+// stable partition of mv[0 .. n): tactical moves first.  mv is visible on entry and on return.
+__device__ inline void opp_partition(const Board &b, u16 *mv, int n, int lane)
+{
+    const u64 occ = occupied(b);
+    const u64 own = st_turn(b.state) ? b.white : (occ & ~b.white);
+    const u64 below = bit(lane) - 1;
+    u32 m[4];
+    u64 T[4], V[4];
+    int nt = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int i = c * 64 + lane;
+        const bool valid = i < n;
+        m[c] = valid ? mv[i] : 0u;
+        V[c] = __ballot(valid);
+        T[c] = __ballot(valid && opp_tactical(b, occ, own, m[c]));
+        nt += popc(T[c]);
+    }
+    __syncthreads();                                   // every move read before any is rewritten
+    int bt = 0, bq = nt;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const u64 Q = V[c] & ~T[c];
+        if (V[c] & bit(lane)) {
+            const int pos = (T[c] & bit(lane)) ? bt + popc(T[c] & below) : bq + popc(Q & below);
+            mv[pos] = (u16)m[c];
+        }
+        bt += popc(T[c]);
+        bq += popc(Q);
+    }
+    __syncthreads();
+}
+
+// window-relative rows: depths / moves / scores / nodes_out / flags [count]
+__global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *depths, int push, long long limit,
+                                                       u16 *moves, int32_t *scores, long long *nodes_out,
+                                                       uint8_t *flags)
+{
+    __shared__ OppLds s;
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    int D = uni(depths[r]);
+    if (D > OPP_MAX_DEPTH) D = OPP_MAX_DEPTH;              // (the host refuses such a depth before the launch)
+    const bool skipped = D > 0 && uni(d.game[g].game_result) != RESULT_NONE;
+    if (D <= 0 || skipped) {
+        if (lane == 0) { moves[r] = NO_MOVE; scores[r] = 0; nodes_out[r] = 0; flags[r] = skipped ? OPP_SKIPPED : 0; }
+        return;
+    }
+    const Board root = uni_board(d.cur[g]);
+    Board b = root;
+    int k = 0, a = -OPP_INF, be = OPP_INF, v = 0, root_best = -OPP_INF;
+    u32 best_mv = NO_MOVE, first_mv = NO_MOVE;
+    bool done = false;
+    long long nodes = 0;
+    while (nodes < limit) {
+        // ---- enter the node `b` at ply k, window (a, be)
+        OppFrame &F = s.f[k];
+        const bool horizon = k == D;
+        MoveGenInfo mi = wave_movegen(b, lane, horizon ? nullptr : F.mv);
+        nodes++;
+        const int n = uni(mi.n);
+        const int res = uni(position_result(b, n, mi.in_check, 1));
+        bool have_v = true;
+        if (res != RESULT_NONE) v = res == 0 ? 0 : -(OPP_MATE - k);
+        else if (horizon) v = uni(opp_evaluate(b, lane));
+        else {
+            __syncthreads();                               // F.mv visible
+            if (k > 0) opp_partition(b, F.mv, n, lane);
+            else first_mv = (u32)uni((int)F.mv[0]);
+            if (lane == 0) { F.b = b; F.cur = 0; F.n = n; F.alpha = a; F.beta = be; F.best = -OPP_INF; }
+            __syncthreads();
+            have_v = false;
+        }
+        // ---- hand v up: every turn lowers k, so at most d + 1 of them
+        while (have_v) {
+            if (k == 0) { done = true; break; }
+            k--;
+            OppFrame &P = s.f[k];
+            const int sc = -v, pn = uni(P.n), pb = uni(P.beta);
+            int cur = uni(P.cur), best = uni(P.best), al = uni(P.alpha);
+            if (sc > best) {
+                best = sc;
+                if (k == 0) { best_mv = (u32)uni((int)P.mv[cur]); root_best = sc; }
+            }
+            if (sc > al) al = sc;
+            cur++;
+            __syncthreads();                               // the frame was read
+            if (lane == 0) { P.cur = cur; P.best = best; P.alpha = al; }
+            __syncthreads();
+            if (cur < pn && al < pb) have_v = false;       // frame k has a next move to search
+            else v = best;                                 // exhausted or cut: it returns its best
+        }
+        if (done) break;
+        // ---- descend: the next move of frame k  (k < D: a frame with moves to search is above the horizon)
+        OppFrame &P = s.f[k];
+        const u32 mv = (u32)uni((int)P.mv[uni(P.cur)]);
+        b = apply_move(uni_board(P.b), mv);
+        a = -uni(P.beta);
+        be = -uni(P.alpha);
+        k++;
+    }
+    const u32 mv = done || best_mv != NO_MOVE ? best_mv : first_mv;
+    if (lane == 0) {
+        moves[r] = (u16)mv;
+        scores[r] = done ? v : root_best;
+        nodes_out[r] = nodes;
+        flags[r] = done ? 0 : OPP_CUT;
+    }
+    if (push && mv != NO_MOVE) {
+        __syncthreads();                                   // the frames are dead: s.w takes their bytes
+        game_push(d, g, root, mv, lane, s.w);
+    }
+}
+
+}  // namespace crl

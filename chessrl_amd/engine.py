@@ -29,6 +29,8 @@ calls evaluate G*T rows (row = game * T + thread), and the leaves are backed up
 in thread order.  Waves may end short, so the number of steps of a search is
 data-dependent, between ceil(n/T) and n; a game whose budget is spent idles.
 """
+import gc
+
 import numpy as np
 import torch
 
@@ -481,12 +483,22 @@ class LockstepEngine(object):
         g = torch.cuda.CUDAGraph()
         # thread_local: another thread of this process (rank 0's background trainer) may allocate and launch
         # on its own stream while this thread captures
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._bind_stream()              # kernels must land on the capturing stream
-            for _ in range(k):
-                self._step_body()
-            if self.stamps is not None:
-                self.stamps.stamp(STAMP_GRAPH_END)
+        # No cyclic garbage collection inside the capture: torch.cuda.graph no longer collects before it begins, and a
+        # finalizer that runs in here -- an engine dropped earlier and still held by its last tree
+        # (mctree: tree._engine <-> engine._tree_owner), whose Context.__del__ is crl_destroy -- would synchronise
+        # the device and free memory on the capturing thread.  What is garbage now is collected after the capture.
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._bind_stream()              # kernels must land on the capturing stream
+                for _ in range(k):
+                    self._step_body()
+                if self.stamps is not None:
+                    self.stamps.stamp(STAMP_GRAPH_END)
+        finally:
+            if gc_was_on:
+                gc.enable()
         self._bind_stream()
         self._graphs[(k, self.stamps is not None)] = g
         self._graph_epoch = getattr(self.evaluator, "graph_epoch", 0)

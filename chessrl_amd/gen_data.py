@@ -1,0 +1,116 @@
+"""Supervised data from games of the built-in opponent against itself -- host mirror of the reference's
+``gen_data_stockfish.py``.
+
+/root/reference/src/chessrl/gen_data_stockfish.py:12-52 lets a Stockfish of ``player_depth`` play a
+``GameStockfish`` whose engine has ``game_depth`` and appends the finished game to a ``DatasetGame``.  Here both
+sides are the built-in alpha-beta player (csrc/opponent.hpp; NOT Stockfish), every game is one slot of ONE device
+context and all games advance together: one ``opponent_moves(depths, push=True)`` launch per ply with the per-slot
+depth of the side to move.  That player is deterministic, so every game first plays ``opening_plies`` random plies
+with the in-slot playout call (``Context.rollout_games``, words from ``random.Random(seed)``).
+"""
+import argparse
+import logging
+import random
+from datetime import datetime
+
+import numpy as np
+
+from . import _lib
+from .dataset import DatasetGame
+from .opponent import clamp_depth
+from .records import GameRecord
+
+log = logging.getLogger("chessrl_amd.gen_data")
+WORDS_PER_PLY = 8         # words handed to a slot per opening ply and call (a choice rejects a word with p < 1/2)
+
+
+def draw_games(num_games, depth=1, random_dep=False, seed=0):
+    """Per game, in game order, from ``np.random.RandomState(seed)``: (is_white, game_depth, player_depth) as
+    gen_data_stockfish.py:13-19 draws them -- ``random() <= .5``, then with ``random_dep`` two
+    ``int(normal(depth, 1))`` -- the depths clamped to [1, CRL_OPP_MAX_DEPTH]."""
+    rs = np.random.RandomState(seed)
+    out = []
+    for _ in range(num_games):
+        is_white = True if rs.random_sample() <= .5 else False
+        game_depth = player_depth = depth
+        if random_dep:
+            game_depth = int(rs.normal(depth, 1))
+            player_depth = int(rs.normal(depth, 1))
+        out.append((is_white, clamp_depth(game_depth), clamp_depth(player_depth)))
+    return out
+
+
+def opening_words(rng, num_games, opening_plies):
+    """The next block of opening words: uint32 [num_games][WORDS_PER_PLY * opening_plies], row by row from
+    ``rng.getrandbits(32)``."""
+    n = WORDS_PER_PLY * opening_plies
+    rows = [[rng.getrandbits(32) for _ in range(n)] for _ in range(num_games)]
+    return np.array(rows, dtype=np.uint32).reshape(num_games, n)
+
+
+def side_depths(draws, white_to_move):
+    """Depth of the side to move per game: the player (colour ``is_white``) has ``player_depth``, the other side
+    ``game_depth``."""
+    return np.array([pd if is_white == white_to_move else gd for is_white, gd, pd in draws], dtype=np.int32)
+
+
+def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512):
+    """Plays ``num_games`` games, saves the finished ones to ``save_path`` (appending to what the file holds, as
+    ``DatasetGame.save`` does) and returns the ``DatasetGame`` it saved.  The reference's ``gen_data`` forgets to
+    pass ``depth`` and ``random_dep`` on to ``play_game`` (gen_data_stockfish.py:44-49); here both are honoured.
+    ``workers`` is accepted and ignored; a game still running after ``max_plies`` plies is dropped."""
+    num_games, opening_plies, max_plies = int(num_games), int(opening_plies), int(max_plies)
+    d = DatasetGame()
+    if num_games < 1:
+        d.save(save_path)
+        return d
+    draws = draw_games(num_games, depth, random_dep, seed)
+    rng = random.Random(seed)
+    ctx = _lib.Context(num_games, 1, max_plies=max(max_plies, opening_plies, 2))
+    try:
+        if opening_plies > 0:
+            played = np.zeros(num_games, np.int32)
+            while True:
+                words = opening_words(rng, num_games, opening_plies)
+                played, _, res = ctx.rollout_games(words, np.full(num_games, words.shape[1], np.int32), 1,
+                                                   opening_plies, played=played)
+                if ((played >= opening_plies) | (res[:, 0] != _lib.RESULT_NONE)).all():
+                    break
+        _, plies, results = ctx.records(with_moves=False)
+        for ply in range(opening_plies, max_plies):
+            running = results == _lib.RESULT_NONE
+            if not running.any():
+                break
+            ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True)
+            results = ctx.results()
+        moves, plies, results = ctx.records()
+    finally:
+        ctx.close()
+    date = datetime.now().strftime("%d/%m/%Y %H:%M:%S")
+    for i in range(num_games):
+        if results[i] != _lib.RESULT_NONE:
+            d.append(GameRecord(i, moves[i, :plies[i]], int(results[i]), draws[i][0], date=date))
+    log.info("Saving dataset...")
+    d.save(save_path)
+    return d
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description="Plays some chess games of the built-in opponent against itself and "
+                                            "stores them as a dataset.")
+    p.add_argument("data_path", metavar="datadir", help="Path of .JSON dataset.")
+    p.add_argument("--games", metavar="games", type=int, default=10)
+    p.add_argument("--depth", metavar="depth", type=int, default=1, help="Search depth of the built-in opponent.")
+    p.add_argument("--random_depth", action="store_true", default=False,
+                   help="Use normal distribution of depths with mean --depth.")
+    p.add_argument("--debug", action="store_true", default=False, help="Log debug messages on screen. Default false.")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--opening-plies", type=int, default=4)
+    a = p.parse_args(argv)
+    logging.basicConfig(level=logging.DEBUG if a.debug else logging.INFO)
+    gen_data(a.data_path, num_games=a.games, depth=a.depth, random_dep=a.random_depth,
+             opening_plies=a.opening_plies, seed=a.seed)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,91 @@
+"""``MinimaxPlayer`` / ``GameOpponent`` -- the built-in opponent in the reference's shapes.
+
+The reference measures and bootstraps against an engine: ``Stockfish(Player)``
+(/root/reference/src/chessrl/stockfish.py:11-34) and ``GameStockfish(Game)``, a game that answers
+every move of ours with the engine's (gamestockfish.py:6-61).  No engine binary belongs to this
+package; what stands in its place is the fixed-depth alpha-beta player of ``csrc/opponent.hpp``,
+one wavefront per game on the GPU.  It is NOT Stockfish: no repetition below the root, no
+quiescence, no time control, and no Elo is claimed -- a result reads "against the built-in depth-d
+opponent".  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
+these classes are the one-game drop-in surface over it.
+"""
+import numpy as np
+
+from . import _lib
+from .game import Game, arena, move_to_uci
+from .player import Player
+
+MAX_DEPTH = _lib.OPP_MAX_DEPTH
+NODE_LIMIT = _lib.OPP_NODE_LIMIT
+
+
+def clamp_depth(depth):
+    """A search depth the kernel takes: [1, MAX_DEPTH]."""
+    return max(1, min(MAX_DEPTH, int(depth)))
+
+
+class MinimaxPlayer(Player):
+    """Mirror of ``Stockfish(Player)``: ``best_move(game)`` is the UCI string of the depth-``search_depth``
+    alpha-beta move for a ``chessrl_amd.Game`` (``'00000'`` on a finished game)."""
+
+    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT):
+        super().__init__(color)
+        if not 1 <= int(search_depth) <= MAX_DEPTH:
+            raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
+        if int(node_limit) < 1:
+            raise ValueError("node_limit must be at least 1")
+        self.search_depth = int(search_depth)
+        self.node_limit = int(node_limit)
+        self.last = None                      # (score, nodes, flag) of the last search
+
+    def best_move(self, game):
+        if game._slot is None:
+            raise RuntimeError("Game was freed")
+        ctx = arena().one(game._slot)
+        moves, scores, nodes, flags = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False,
+                                                         node_limit=self.node_limit)
+        self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
+        if int(moves[0]) == _lib.NO_MOVE:
+            return Game.NULL_MOVE
+        return move_to_uci(moves[0])
+
+    def kill(self):
+        """Nothing to end: kept for the drop-in shape (stockfish.py:33-34)."""
+
+
+class GameOpponent(Game):
+    """Mirror of ``GameStockfish``: a game against the built-in opponent.  ``opponent``: a ``MinimaxPlayer``, or
+    None for one of depth ``opponent_depth`` with the colour opposite to ``player_color``."""
+
+    def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2):
+        if opponent is not None and not isinstance(opponent, MinimaxPlayer):
+            raise ValueError("opponent must be a MinimaxPlayer or None")
+        self.opponent = None                  # (a board's move stack is replayed by plain Game.move)
+        super().__init__(board=board, player_color=player_color, date=date)
+        if opponent is None:
+            opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth)
+        self.opponent = opponent
+
+    def move(self, movement):
+        """gamestockfish.py:27-41: if the opponent is white and nothing was played yet, the opponent moves and
+        ``movement`` is ignored; otherwise our move is made and, if it was legal and the game goes on, the
+        opponent replies."""
+        if self.opponent is None:
+            return Game.move(self, movement)
+        if self.opponent.color and len(self) == 0:
+            Game.move(self, self.opponent.best_move(self))
+        else:
+            made = Game.move(self, movement)
+            if made and self.get_result() is None:
+                Game.move(self, self.opponent.best_move(self))
+
+    def get_copy(self):
+        return GameOpponent(opponent=self.opponent, player_color=self.player_color, board=self, date=self.date)
+
+    def tearup(self):
+        self.opponent.kill()
+
+    def free(self):
+        """Unlinks the game from its opponent (gamestockfish.py:54-56) and gives the device slot back."""
+        self.opponent = None
+        Game.free(self)

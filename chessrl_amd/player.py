@@ -2,8 +2,9 @@
 
 Mirrors the role of the reference's abstract player
 (/root/reference/src/chessrl/player.py:1-14): it only records the side the player has
-(``color``: True = white) and refuses to be used directly; ``Agent`` is the one concrete
-player of this package (the Stockfish player of the reference is out of scope).
+(``color``: True = white) and refuses to be used directly; the concrete players of this
+package are ``Agent`` and ``opponent.MinimaxPlayer``, the built-in stand-in where the reference has its Stockfish
+player (Stockfish itself is out of scope).
 """
 
 

@@ -268,6 +268,26 @@ int  crl_rollout_games(crl_ctx *ctx, const uint32_t *words /*G x stride*/, const
 int  crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, const uint64_t *dev_keys,
                  void *dev_value_f32, int8_t *dev_results_i8, uint16_t *dev_plies_u16);
 
+/* ---- the built-in opponent: a fixed-depth alpha-beta player per slot (csrc/opponent.hpp states the search, the
+ * node value, the move order, the static evaluation and the node limit).  It stands where the reference calls its
+ * engine: Stockfish.best_move (stockfish.py:23-31, engine.play(board, Limit(depth))) and the reply inside
+ * GameStockfish.move (gamestockfish.py:27-41).  It is not that engine: no repetition below the root, no quiescence,
+ * no time control, no Elo.  Host arrays, synchronous, window-relative like crl_greedy_moves.
+ * depths[g] (host int32): 0 leaves slot g alone, 1 .. CRL_OPP_MAX_DEPTH searches it to that depth -- the array is
+ * both the mask and the per-game depth.  node_limit >= 1 bounds the nodes (move generations) of every slot: a slot
+ * that reaches it returns the best root move among those completely searched, or its first legal move, and the flag
+ * CRL_OPP_CUT.  A slot whose game already has a result returns CRL_NO_MOVE and CRL_OPP_SKIPPED.  If push != 0 the
+ * chosen move is played: history, record, ply and result change as by crl_push_moves.
+ * moves[g] = the move (CRL_NO_MOVE for depth 0 and skipped slots); scores[g] = its score from the side to move
+ * (mate in k plies = 30000 - k); nodes[g] = nodes generated; flags[g]; the last three may be NULL.
+ * CRL_ERR_ARG: NULL depths or moves, a depth outside 0 .. CRL_OPP_MAX_DEPTH, node_limit < 1.  No state changes on
+ * an error. */
+#define CRL_OPP_MAX_DEPTH 5
+#define CRL_OPP_CUT 1
+#define CRL_OPP_SKIPPED 2
+int  crl_opponent_moves(crl_ctx *ctx, const int32_t *depths /*G*/, int push, int64_t node_limit,
+                        uint16_t *moves /*G*/, int32_t *scores /*G*/, int64_t *nodes /*G*/, uint8_t *flags /*G*/);
+
 /* ---- threads > 1: virtual-loss waves of simulations per game (csrc/search_wave.hpp) --------------------------
  * The reference runs `threads` explore_tree workers on one tree, kept apart by a virtual loss (mctree.py:12,173-176,
  * 226-227,289-293).  The wave schedule is the deterministic one among its legal schedules: per game, up to `threads`

@@ -1,0 +1,66 @@
+#!/usr/bin/env python
+"""Node rate of the built-in opponent (csrc/opponent.hpp): ms per launch, nodes per slot and nodes/s at depths 1, 2, 3.
+
+    python tools/opponent_probe.py [--games 4096] [--opening-plies 6] [--node-limit 200000] [--out profiles/opponent_probe.json]
+
+Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words), so the slots hold
+different positions.  Per depth, in depth order: one warm-up launch, then three timed ones (host wall time around the
+synchronous call, copies included); the median is reported.  Nothing is pushed, so every launch searches the same
+positions.  No threshold: this is a measurement.
+"""
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=4096)
+    ap.add_argument("--opening-plies", type=int, default=6)
+    ap.add_argument("--node-limit", type=int, default=200000)
+    ap.add_argument("--depths", default="1,2,3")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "opponent_probe.json"))
+    args = ap.parse_args()
+    import numpy as np
+    from chessrl_amd import _lib
+    from chessrl_amd.gen_data import opening_words
+    G = args.games
+    ctx = _lib.Context(G, 1, max_plies=64)
+    words = opening_words(random.Random(1), G, args.opening_plies)
+    played, _, _ = ctx.rollout_games(words, np.full(G, words.shape[1], np.int32), 1, args.opening_plies)
+    out = {"games": G, "opening_plies": args.opening_plies, "mean_opening_plies": float(played.mean()),
+           "node_limit": args.node_limit, "running": int((ctx.results() == _lib.RESULT_NONE).sum()), "depths": {}}
+    for depth in (int(x) for x in args.depths.split(",")):
+        row = np.full(G, depth, np.int32)
+        times = []
+        for i in range(4):
+            t0 = time.perf_counter()
+            moves, scores, nodes, flags = ctx.opponent_moves(row, node_limit=args.node_limit)
+            if i:
+                times.append(time.perf_counter() - t0)
+        t = statistics.median(times)
+        searched = flags != _lib.OPP_SKIPPED
+        total = int(nodes.sum())
+        out["depths"][str(depth)] = {
+            "seconds": times, "ms_per_launch": 1e3 * t, "nodes": total, "nodes_per_slot_mean": float(nodes[searched].mean()),
+            "nodes_per_slot_max": int(nodes.max()), "nodes_per_s": total / t, "us_per_node_of_the_longest_slot":
+            1e6 * t / max(int(nodes.max()), 1), "cut_share": float((flags == _lib.OPP_CUT).mean())}
+        print(depth, json.dumps(out["depths"][str(depth)]), flush=True)
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
