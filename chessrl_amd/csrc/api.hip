@@ -114,11 +114,37 @@ static int fail(crl_ctx *ctx, int code, const std::string &msg)
     return code;
 }
 
+// the stream-level entry points (tower, heads, margin, train ops, stamps) have no context to keep a message in
+static int hip_rc(hipError_t e)
+{
+    return e == hipSuccess ? CRL_OK : fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
+}
+
 #define HIP_TRY(ctx, expr)                                                              \
     do {                                                                                \
         hipError_t _e = (expr);                                                         \
         if (_e != hipSuccess)                                                           \
             return fail(ctx, CRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// a step of an entry point that is itself a CRL_* code (the boundary pieces below)
+#define TRY(call)                                                                       \
+    do {                                                                                \
+        int _rc = (call);                                                               \
+        if (_rc != CRL_OK) return _rc;                                                  \
+    } while (0)
+
+// How every context entry point begins: no context or a false argument condition is CRL_ERR_ARG (`ok` may read the
+// context: it is evaluated only when there is one).  ENTER also selects the context's device; setters that never
+// touch the device stop at ARGS.  A refusal with a message of its own follows as its own `if`.
+#define ARGS(ctx, ok)                                                                   \
+    do {                                                                                \
+        if (!(ctx) || !(ok)) return fail(ctx, CRL_ERR_ARG, std::string(__func__) + ": bad argument"); \
+    } while (0)
+#define ENTER(ctx, ok)                                                                  \
+    do {                                                                                \
+        ARGS(ctx, ok);                                                                  \
+        HIP_TRY(ctx, hipSetDevice((ctx)->device));                                      \
     } while (0)
 
 template <typename T>
@@ -144,6 +170,38 @@ static hipError_t dalloc(crl_ctx *ctx, T **p, size_t count, bool zero = true)
     return dalloc_into(ctx->allocs, p, count, zero);
 }
 
+// The copies of the host-facing calls: on the context's stream, counted in elements of the type both ends hold.
+// A staging array read as another type is cast where it is passed.  A NULL host pointer is an output nobody wants.
+template <typename T>
+static hipError_t to_host(crl_ctx *ctx, T *host, const T *dev, size_t count)
+{
+    if (!host) return hipSuccess;
+    return hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+}
+
+template <typename T>
+static hipError_t to_dev(crl_ctx *ctx, T *dev, const T *host, size_t count)
+{
+    return hipMemcpyAsync(dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+}
+
+// The device buffer of one setup-time call (crl_push_sequences, crl_rollout_games): whichever way the call returns,
+// the stream is drained and then the buffer freed.
+struct Scratch {
+    crl_ctx *ctx;
+    unsigned char *p = nullptr;
+    explicit Scratch(crl_ctx *c) : ctx(c) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    hipError_t alloc(size_t bytes) { return hipMalloc((void **)&p, bytes); }
+    ~Scratch()
+    {
+        if (!p) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(p);
+    }
+};
+
 static const char *dev_err_name(int c)
 {
     switch (c) {
@@ -160,17 +218,75 @@ static const char *dev_err_name(int c)
 static int check_dev_error(crl_ctx *ctx)
 {
     int32_t e = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&e, ctx->d.err, sizeof e, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, &e, ctx->d.err, 1));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (e != 0) return fail(ctx, e == DERR_STATE ? CRL_ERR_STATE : CRL_ERR_CAPACITY, dev_err_name(e));
     return CRL_OK;
 }
 
-#define LAUNCH(ctx, kern, ...)                                                          \
+// one wavefront per workgroup on the context's stream: LAUNCH one workgroup per slot of the window, LAUNCH_N `n` of them
+#define LAUNCH_N(ctx, n, kern, ...)                                                     \
     do {                                                                                \
-        hipLaunchKernelGGL(kern, dim3((ctx)->W), dim3(64), 0, (ctx)->stream, __VA_ARGS__); \
+        hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, (ctx)->stream, __VA_ARGS__);     \
         HIP_TRY(ctx, hipGetLastError());                                                \
     } while (0)
+#define LAUNCH(ctx, kern, ...) LAUNCH_N(ctx, (ctx)->W, kern, __VA_ARGS__)
+
+// ---- the pieces of a move boundary, each stated once (the entry points below enqueue them in stream order: a staging
+// array is free for the next piece as soon as its copy is queued) ----------------------------------------------------
+// root statistics: k_root_children and whichever of its seven outputs the caller wants
+static int root_stats(crl_ctx *ctx, int32_t *nchild, int32_t *visits, double *values, float *priors, uint16_t *moves,
+                      uint16_t *replies, int32_t *root_visits)
+{
+    const size_t G = ctx->W, R = G * MAX_MOVES;
+    LAUNCH(ctx, k_root_children, ctx->d, ctx->t_i32b, ctx->t_i32a, ctx->t_f64, ctx->t_f32, ctx->t_moves,
+           ctx->t_moves2, ctx->t_i32c);
+    HIP_TRY(ctx, to_host(ctx, nchild, ctx->t_i32b, G));
+    HIP_TRY(ctx, to_host(ctx, visits, ctx->t_i32a, R));
+    HIP_TRY(ctx, to_host(ctx, values, ctx->t_f64, R));
+    HIP_TRY(ctx, to_host(ctx, priors, ctx->t_f32, R));
+    HIP_TRY(ctx, to_host(ctx, moves, ctx->t_moves, R));
+    HIP_TRY(ctx, to_host(ctx, replies, ctx->t_moves2, R));
+    HIP_TRY(ctx, to_host(ctx, root_visits, ctx->t_i32c, G));
+    return CRL_OK;
+}
+
+// play the chosen children: k_advance, or with `next_sims` k_reroot (Tree(Node): the chosen child keeps its subtree
+// wherever kept nodes + *next_sims fit, and says how much it kept)
+static int play_chosen(crl_ctx *ctx, const int32_t *chosen, const int *next_sims, uint16_t *bm, uint16_t *am,
+                       int32_t *kept_nodes, int32_t *kept_children)
+{
+    const size_t G = ctx->W;
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, chosen, G));
+    if (next_sims)
+        LAUNCH(ctx, k_reroot, ctx->d, (const int32_t *)ctx->t_i32b, *next_sims, ctx->t_u16a, ctx->t_u16b, ctx->t_i32d,
+               ctx->t_i32e);
+    else
+        LAUNCH(ctx, k_advance, ctx->d, (const int32_t *)ctx->t_i32b, ctx->t_u16a, ctx->t_u16b);
+    HIP_TRY(ctx, to_host(ctx, bm, ctx->t_u16a, G));
+    HIP_TRY(ctx, to_host(ctx, am, ctx->t_u16b, G));
+    HIP_TRY(ctx, to_host(ctx, kept_nodes, ctx->t_i32d, G));
+    HIP_TRY(ctx, to_host(ctx, kept_children, ctx->t_i32e, G));
+    return CRL_OK;
+}
+
+// the next roots: who has ended, and how many legal moves the others have
+static int next_roots(crl_ctx *ctx, int8_t *results, int32_t *legal_counts)
+{
+    const size_t G = ctx->W;
+    LAUNCH(ctx, k_game_scalars, ctx->d, ctx->t_i32c, (int8_t *)ctx->t_u8);
+    HIP_TRY(ctx, to_host(ctx, results, (const int8_t *)ctx->t_u8, G));
+    LAUNCH(ctx, k_legal_moves, ctx->d, ctx->t_moves, ctx->t_i32b);
+    HIP_TRY(ctx, to_host(ctx, legal_counts, ctx->t_i32b, G));
+    return CRL_OK;
+}
+
+static int search_begin(crl_ctx *ctx, void *dev_planes_f16, int keep)
+{
+    LAUNCH(ctx, k_search_begin, ctx->d, dev_planes_f16, keep);
+    ctx->search_begun = true;
+    return CRL_OK;
+}
 
 extern "C" {
 
@@ -256,20 +372,21 @@ void crl_destroy(crl_ctx *ctx)
 
 int crl_set_stream(crl_ctx *ctx, void *hip_stream)
 {
-    if (!ctx) return CRL_ERR_ARG;
+    ARGS(ctx, true);
     ctx->stream = (hipStream_t)hip_stream;
     return CRL_OK;
 }
 
 int crl_sync(crl_ctx *ctx)
 {
-    if (!ctx) return CRL_ERR_ARG;
+    ARGS(ctx, true);
     return check_dev_error(ctx);
 }
 
 int crl_set_window(crl_ctx *ctx, int first, int count)
 {
-    if (!ctx || first < 0 || count < 1 || first + count > ctx->d.G)
+    ARGS(ctx, true);
+    if (first < 0 || count < 1 || first + count > ctx->d.G)
         return fail(ctx, CRL_ERR_ARG, "crl_set_window: bad slot range");
     ctx->d.g0 = first;
     ctx->W = count;
@@ -278,16 +395,14 @@ int crl_set_window(crl_ctx *ctx, int first, int count)
 
 int crl_set_plane_format(crl_ctx *ctx, int format)
 {
-    if (!ctx || (format != CRL_PLANES_F16 && format != CRL_PLANES_BITS))
-        return fail(ctx, CRL_ERR_ARG, "crl_set_plane_format: bad argument");
+    ARGS(ctx, format == CRL_PLANES_F16 || format == CRL_PLANES_BITS);
     ctx->d.plane_fmt = format;
     return CRL_OK;
 }
 
 int crl_set_policy_format(crl_ctx *ctx, int format)
 {
-    if (!ctx || (format != CRL_POLICY_FULL && format != CRL_POLICY_LEGAL && format != CRL_POLICY_LEGAL_RAW))
-        return fail(ctx, CRL_ERR_ARG, "crl_set_policy_format: bad argument");
+    ARGS(ctx, format == CRL_POLICY_FULL || format == CRL_POLICY_LEGAL || format == CRL_POLICY_LEGAL_RAW);
     if (format == CRL_POLICY_LEGAL_RAW && (!ctx->d.stats_s1 || !ctx->d.stats_s2))
         return fail(ctx, CRL_ERR_STATE, "crl_set_policy_format: CRL_POLICY_LEGAL_RAW needs crl_set_policy_stats for both evaluations first");
     ctx->d.policy_fmt = format;
@@ -296,16 +411,14 @@ int crl_set_policy_format(crl_ctx *ctx, int format)
 
 int crl_set_policy_stats(crl_ctx *ctx, int which, const void *dev_stats_f32)
 {
-    if (!ctx || (which != 0 && which != 1) || !dev_stats_f32)
-        return fail(ctx, CRL_ERR_ARG, "crl_set_policy_stats: bad argument");
+    ARGS(ctx, (which == 0 || which == 1) && dev_stats_f32);
     (which ? ctx->d.stats_s2 : ctx->d.stats_s1) = (const float2 *)dev_stats_f32;
     return CRL_OK;
 }
 
 int crl_eval_labels(crl_ctx *ctx, int which, const uint16_t **dev_labels, const int32_t **dev_counts)
 {
-    if (!ctx || (which != 0 && which != 1) || !dev_labels || !dev_counts)
-        return fail(ctx, CRL_ERR_ARG, "crl_eval_labels: bad argument");
+    ARGS(ctx, (which == 0 || which == 1) && dev_labels && dev_counts);
     *dev_labels = which ? ctx->d.lab_s2 : ctx->d.lab_s1;
     *dev_counts = which ? ctx->d.lab_n2 : ctx->d.lab_n1;
     return CRL_OK;
@@ -313,27 +426,23 @@ int crl_eval_labels(crl_ctx *ctx, int which, const uint16_t **dev_labels, const 
 
 int crl_copy_game(crl_ctx *ctx, int dst, int src)
 {
-    if (!ctx || dst < 0 || src < 0 || dst >= ctx->d.G || src >= ctx->d.G)
+    ENTER(ctx, true);
+    if (dst < 0 || src < 0 || dst >= ctx->d.G || src >= ctx->d.G)
         return fail(ctx, CRL_ERR_ARG, "crl_copy_game: bad slot");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (dst != src) {
-        hipLaunchKernelGGL(k_copy_game, dim3(1), dim3(64), 0, ctx->stream, ctx->d, dst, src);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    if (dst != src) LAUNCH_N(ctx, 1, k_copy_game, ctx->d, dst, src);
     return CRL_OK;
 }
 
 int crl_copy_game_from(crl_ctx *ctx, int dst, crl_ctx *src_ctx, int src)
 {
-    if (!ctx || !src_ctx || dst < 0 || src < 0 || dst >= ctx->d.G || src >= src_ctx->d.G)
+    ENTER(ctx, true);
+    if (!src_ctx || dst < 0 || src < 0 || dst >= ctx->d.G || src >= src_ctx->d.G)
         return fail(ctx, CRL_ERR_ARG, "crl_copy_game_from: bad slot");
     if (ctx->device != src_ctx->device)
         return fail(ctx, CRL_ERR_ARG, "crl_copy_game_from: both contexts must live on one GPU");
     if (src_ctx == ctx) return crl_copy_game(ctx, dst, src);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (src_ctx->stream != ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(src_ctx->stream));
-    hipLaunchKernelGGL(k_copy_game_across, dim3(1), dim3(64), 0, ctx->stream, ctx->d, dst, src_ctx->d, src);
-    HIP_TRY(ctx, hipGetLastError());
+    LAUNCH_N(ctx, 1, k_copy_game_across, ctx->d, dst, src_ctx->d, src);
     return check_dev_error(ctx);
 }
 
@@ -356,11 +465,10 @@ int crl_uci_label_moves(uint16_t *moves_out)
 // ---- Game seam ----------------------------------------------------------------------------
 int crl_reset_games(crl_ctx *ctx, const uint8_t *mask)
 {
-    if (!ctx) return CRL_ERR_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, true);
     const uint8_t *dm = nullptr;
     if (mask) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->t_u8, mask, ctx->W, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, to_dev(ctx, ctx->t_u8, mask, ctx->W));
         dm = ctx->t_u8;
     }
     LAUNCH(ctx, k_set_positions, ctx->d, (const Board *)nullptr, dm, ctx->W, 1);
@@ -370,9 +478,8 @@ int crl_reset_games(crl_ctx *ctx, const uint8_t *mask)
 
 int crl_set_positions(crl_ctx *ctx, const crl_board *boards, int n)
 {
-    if (!ctx || !boards || n < 0 || n > ctx->W) return fail(ctx, CRL_ERR_ARG, "crl_set_positions: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->t_boards, boards, (size_t)n * sizeof(Board), hipMemcpyHostToDevice, ctx->stream));
+    ENTER(ctx, boards && n >= 0 && n <= ctx->W);
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_boards, (const Board *)boards, n));
     LAUNCH(ctx, k_set_positions, ctx->d, (const Board *)ctx->t_boards, (const uint8_t *)nullptr, n, 0);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CRL_OK;
@@ -380,105 +487,83 @@ int crl_set_positions(crl_ctx *ctx, const crl_board *boards, int n)
 
 int crl_get_positions(crl_ctx *ctx, crl_board *boards_out, int n)
 {
-    if (!ctx || !boards_out || n < 0 || n > ctx->W) return fail(ctx, CRL_ERR_ARG, "crl_get_positions: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(boards_out, ctx->d.cur + ctx->d.g0, (size_t)n * sizeof(Board), hipMemcpyDeviceToHost, ctx->stream));
+    ENTER(ctx, boards_out && n >= 0 && n <= ctx->W);
+    HIP_TRY(ctx, to_host(ctx, (Board *)boards_out, ctx->d.cur + ctx->d.g0, n));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CRL_OK;
 }
 
 int crl_legal_moves(crl_ctx *ctx, uint16_t *moves, int32_t *counts)
 {
-    if (!ctx || !counts) return fail(ctx, CRL_ERR_ARG, "crl_legal_moves: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, counts);
     const size_t G = ctx->W;
     LAUNCH(ctx, k_legal_moves, ctx->d, ctx->t_moves, ctx->t_i32b);
-    if (moves)
-        HIP_TRY(ctx, hipMemcpyAsync(moves, ctx->t_moves, G * MAX_MOVES * sizeof(u16), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->t_i32b, G * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, moves, ctx->t_moves, G * MAX_MOVES));
+    HIP_TRY(ctx, to_host(ctx, counts, ctx->t_i32b, G));
     return check_dev_error(ctx);
 }
 
 int crl_push_moves(crl_ctx *ctx, const uint16_t *moves, uint8_t *ok)
 {
-    if (!ctx || !moves || !ok) return fail(ctx, CRL_ERR_ARG, "crl_push_moves: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, moves && ok);
     const size_t G = ctx->W;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->t_u16a, moves, G * sizeof(u16), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_u16a, moves, G));
     LAUNCH(ctx, k_push, ctx->d, (const u16 *)ctx->t_u16a, ctx->t_u8);
-    HIP_TRY(ctx, hipMemcpyAsync(ok, ctx->t_u8, G, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, ok, ctx->t_u8, G));
     return check_dev_error(ctx);
 }
 
 int crl_push_sequences(crl_ctx *ctx, const uint16_t *moves, const int32_t *counts, int stride,
                        int32_t *pushed)
 {
-    if (!ctx || !moves || !counts || !pushed || stride < 1)
-        return fail(ctx, CRL_ERR_ARG, "crl_push_sequences: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t G = ctx->W;
-    u16 *dseq = nullptr;                      // setup-time call: a scratch buffer per call is fine
-    HIP_TRY(ctx, hipMalloc((void **)&dseq, G * (size_t)stride * sizeof(u16)));
-    hipError_t e = hipMemcpyAsync(dseq, moves, G * (size_t)stride * sizeof(u16), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(ctx->t_i32b, counts, G * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_push_seq, dim3((unsigned)G), dim3(64), 0, ctx->stream, ctx->d, (const u16 *)dseq,
-                           (const int32_t *)ctx->t_i32b, stride, ctx->t_i32c);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(pushed, ctx->t_i32c, G * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t es = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(dseq);
-    if (e != hipSuccess) return fail(ctx, CRL_ERR_HIP, hipGetErrorString(e));
-    if (es != hipSuccess) return fail(ctx, CRL_ERR_HIP, hipGetErrorString(es));
+    ENTER(ctx, moves && counts && pushed && stride >= 1);
+    const size_t G = ctx->W, n = G * (size_t)stride;
+    Scratch buf(ctx);
+    HIP_TRY(ctx, buf.alloc(n * sizeof(u16)));
+    u16 *dseq = (u16 *)buf.p;
+    HIP_TRY(ctx, to_dev(ctx, dseq, moves, n));
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, counts, G));
+    LAUNCH(ctx, k_push_seq, ctx->d, (const u16 *)dseq, (const int32_t *)ctx->t_i32b, stride, ctx->t_i32c);
+    HIP_TRY(ctx, to_host(ctx, pushed, ctx->t_i32c, G));
     return check_dev_error(ctx);
 }
 
 int crl_results(crl_ctx *ctx, int8_t *result)
 {
-    if (!ctx || !result) return fail(ctx, CRL_ERR_ARG, "crl_results: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, result);
     LAUNCH(ctx, k_game_scalars, ctx->d, ctx->t_i32b, (int8_t *)ctx->t_u8);
-    HIP_TRY(ctx, hipMemcpyAsync(result, ctx->t_u8, ctx->W, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, result, (const int8_t *)ctx->t_u8, ctx->W));
     return check_dev_error(ctx);
 }
 
 int crl_records(crl_ctx *ctx, uint16_t *moves, int32_t *plies, int8_t *result)
 {
-    if (!ctx || !plies) return fail(ctx, CRL_ERR_ARG, "crl_records: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, plies);
     const size_t G = ctx->W;
-    if (moves)
-        HIP_TRY(ctx, hipMemcpyAsync(moves, ctx->d.rec_moves + (size_t)ctx->d.g0 * ctx->d.MAXPLY, G * ctx->d.MAXPLY * sizeof(u16), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, moves, ctx->d.rec_moves + (size_t)ctx->d.g0 * ctx->d.MAXPLY, G * ctx->d.MAXPLY));
     LAUNCH(ctx, k_game_scalars, ctx->d, ctx->t_i32b, (int8_t *)ctx->t_u8);
-    HIP_TRY(ctx, hipMemcpyAsync(plies, ctx->t_i32b, G * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (result)
-        HIP_TRY(ctx, hipMemcpyAsync(result, ctx->t_u8, G, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, plies, ctx->t_i32b, G));
+    HIP_TRY(ctx, to_host(ctx, result, (const int8_t *)ctx->t_u8, G));
     return check_dev_error(ctx);
 }
 
 int crl_encode(crl_ctx *ctx, void *dev_planes_f16)
 {
-    if (!ctx || !dev_planes_f16) return fail(ctx, CRL_ERR_ARG, "crl_encode: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, dev_planes_f16);
     LAUNCH(ctx, k_encode_cur, ctx->d, dev_planes_f16);
     return CRL_OK;
 }
 
 int crl_greedy_moves(crl_ctx *ctx, const void *dev_policy_f32, const uint8_t *mask, int push, uint16_t *moves_out)
 {
-    if (!ctx || !dev_policy_f32) return fail(ctx, CRL_ERR_ARG, "crl_greedy_moves: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, dev_policy_f32);
     const uint8_t *dm = nullptr;
     if (mask) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->t_u8, mask, ctx->W, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, to_dev(ctx, ctx->t_u8, mask, ctx->W));
         dm = ctx->t_u8;
     }
     LAUNCH(ctx, k_greedy, ctx->d, (const float *)dev_policy_f32, dm, push, ctx->t_u16a);
-    if (moves_out)
-        HIP_TRY(ctx, hipMemcpyAsync(moves_out, ctx->t_u16a, (size_t)ctx->W * sizeof(u16), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, moves_out, ctx->t_u16a, ctx->W));
     if (mask || moves_out) return check_dev_error(ctx);
     return CRL_OK;
 }
@@ -486,26 +571,19 @@ int crl_greedy_moves(crl_ctx *ctx, const void *dev_policy_f32, const uint8_t *ma
 // ---- SelfPlayTree seam ----------------------------------------------------------------------
 int crl_search_begin(crl_ctx *ctx, void *dev_planes_f16)
 {
-    if (!ctx || !dev_planes_f16) return fail(ctx, CRL_ERR_ARG, "crl_search_begin: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    LAUNCH(ctx, k_search_begin, ctx->d, dev_planes_f16, 0);
-    ctx->search_begun = true;
-    return CRL_OK;
+    ENTER(ctx, dev_planes_f16);
+    return search_begin(ctx, dev_planes_f16, 0);
 }
 
 int crl_search_begin_kept(crl_ctx *ctx, void *dev_planes_f16)
 {
-    if (!ctx || !dev_planes_f16) return fail(ctx, CRL_ERR_ARG, "crl_search_begin_kept: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    LAUNCH(ctx, k_search_begin, ctx->d, dev_planes_f16, 1);
-    ctx->search_begun = true;
-    return CRL_OK;
+    ENTER(ctx, dev_planes_f16);
+    return search_begin(ctx, dev_planes_f16, 1);
 }
 
 int crl_search_root_priors(crl_ctx *ctx, const void *dev_policy_f32)
 {
-    if (!ctx || !dev_policy_f32) return fail(ctx, CRL_ERR_ARG, "crl_search_root_priors: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, dev_policy_f32);
     LAUNCH(ctx, k_root_priors, ctx->d, (const float *)dev_policy_f32);
     return CRL_OK;
 }
@@ -513,8 +591,7 @@ int crl_search_root_priors(crl_ctx *ctx, const void *dev_policy_f32)
 int crl_sim_select_expand(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32,
                           void *dev_planes_s1_f16)
 {
-    if (!ctx || !dev_planes_s1_f16) return fail(ctx, CRL_ERR_ARG, "crl_sim_select_expand: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, dev_planes_s1_f16);
     LAUNCH(ctx, k_select_expand, ctx->d, (const float *)dev_policy_s2_f32, (const float *)dev_value_s2_f32,
            dev_planes_s1_f16);
     return CRL_OK;
@@ -522,16 +599,14 @@ int crl_sim_select_expand(crl_ctx *ctx, const void *dev_policy_s2_f32, const voi
 
 int crl_sim_reply(crl_ctx *ctx, const void *dev_policy_s1_f32, void *dev_planes_s2_f16)
 {
-    if (!ctx || !dev_policy_s1_f32 || !dev_planes_s2_f16) return fail(ctx, CRL_ERR_ARG, "crl_sim_reply: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, dev_policy_s1_f32 && dev_planes_s2_f16);
     LAUNCH(ctx, k_reply, ctx->d, (const float *)dev_policy_s1_f32, dev_planes_s2_f16);
     return CRL_OK;
 }
 
 int crl_sim_backup(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32)
 {
-    if (!ctx || !dev_policy_s2_f32 || !dev_value_s2_f32) return fail(ctx, CRL_ERR_ARG, "crl_sim_backup: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, dev_policy_s2_f32 && dev_value_s2_f32);
     LAUNCH(ctx, k_backup, ctx->d, (const float *)dev_policy_s2_f32, (const float *)dev_value_s2_f32);
     return CRL_OK;
 }
@@ -539,31 +614,15 @@ int crl_sim_backup(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_
 int crl_root_children(crl_ctx *ctx, int32_t *nchild, int32_t *visits, double *values, float *priors,
                       uint16_t *moves, uint16_t *replies, int32_t *root_visits)
 {
-    if (!ctx) return CRL_ERR_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t G = ctx->W, R = G * MAX_MOVES;
-    LAUNCH(ctx, k_root_children, ctx->d, ctx->t_i32b, ctx->t_i32a, ctx->t_f64, ctx->t_f32, ctx->t_moves,
-           ctx->t_moves2, ctx->t_i32c);
-    hipStream_t s = ctx->stream;
-    if (nchild) HIP_TRY(ctx, hipMemcpyAsync(nchild, ctx->t_i32b, G * 4, hipMemcpyDeviceToHost, s));
-    if (visits) HIP_TRY(ctx, hipMemcpyAsync(visits, ctx->t_i32a, R * 4, hipMemcpyDeviceToHost, s));
-    if (values) HIP_TRY(ctx, hipMemcpyAsync(values, ctx->t_f64, R * 8, hipMemcpyDeviceToHost, s));
-    if (priors) HIP_TRY(ctx, hipMemcpyAsync(priors, ctx->t_f32, R * 4, hipMemcpyDeviceToHost, s));
-    if (moves) HIP_TRY(ctx, hipMemcpyAsync(moves, ctx->t_moves, R * 2, hipMemcpyDeviceToHost, s));
-    if (replies) HIP_TRY(ctx, hipMemcpyAsync(replies, ctx->t_moves2, R * 2, hipMemcpyDeviceToHost, s));
-    if (root_visits) HIP_TRY(ctx, hipMemcpyAsync(root_visits, ctx->t_i32c, G * 4, hipMemcpyDeviceToHost, s));
+    ENTER(ctx, true);
+    TRY(root_stats(ctx, nchild, visits, values, priors, moves, replies, root_visits));
     return check_dev_error(ctx);
 }
 
 int crl_advance(crl_ctx *ctx, const int32_t *chosen, uint16_t *bm, uint16_t *am)
 {
-    if (!ctx || !chosen) return fail(ctx, CRL_ERR_ARG, "crl_advance: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t G = ctx->W;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->t_i32b, chosen, G * 4, hipMemcpyHostToDevice, ctx->stream));
-    LAUNCH(ctx, k_advance, ctx->d, (const int32_t *)ctx->t_i32b, ctx->t_u16a, ctx->t_u16b);
-    if (bm) HIP_TRY(ctx, hipMemcpyAsync(bm, ctx->t_u16a, G * 2, hipMemcpyDeviceToHost, ctx->stream));
-    if (am) HIP_TRY(ctx, hipMemcpyAsync(am, ctx->t_u16b, G * 2, hipMemcpyDeviceToHost, ctx->stream));
+    ENTER(ctx, chosen);
+    TRY(play_chosen(ctx, chosen, nullptr, bm, am, nullptr, nullptr));
     return check_dev_error(ctx);
 }
 
@@ -571,103 +630,58 @@ int crl_advance(crl_ctx *ctx, const int32_t *chosen, uint16_t *bm, uint16_t *am)
 int crl_end_move_fetch(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32, int32_t *nchild,
                        int32_t *visits, int32_t *root_visits, int32_t *plies)
 {
-    if (!ctx || !dev_policy_s2_f32 || !dev_value_s2_f32 || !nchild || !visits || !root_visits || !plies)
-        return fail(ctx, CRL_ERR_ARG, "crl_end_move_fetch: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t G = ctx->W, R = G * MAX_MOVES;
-    hipStream_t s = ctx->stream;
+    ENTER(ctx, dev_policy_s2_f32 && dev_value_s2_f32 && nchild && visits && root_visits && plies);
     LAUNCH(ctx, k_backup, ctx->d, (const float *)dev_policy_s2_f32, (const float *)dev_value_s2_f32);
-    LAUNCH(ctx, k_root_children, ctx->d, ctx->t_i32b, ctx->t_i32a, ctx->t_f64, ctx->t_f32, ctx->t_moves,
-           ctx->t_moves2, ctx->t_i32c);
-    HIP_TRY(ctx, hipMemcpyAsync(nchild, ctx->t_i32b, G * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(visits, ctx->t_i32a, R * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(root_visits, ctx->t_i32c, G * 4, hipMemcpyDeviceToHost, s));
-    // (the copies above are queued behind k_root_children; the staging arrays are free again for the scalars)
+    TRY(root_stats(ctx, nchild, visits, nullptr, nullptr, nullptr, nullptr, root_visits));
+    // (nchild's copy is queued behind k_root_children: t_i32b is free again for the plies)
     LAUNCH(ctx, k_game_scalars, ctx->d, ctx->t_i32b, (int8_t *)ctx->t_u8);
-    HIP_TRY(ctx, hipMemcpyAsync(plies, ctx->t_i32b, G * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, to_host(ctx, plies, ctx->t_i32b, ctx->W));
     return check_dev_error(ctx);
 }
 
 int crl_advance_fetch(crl_ctx *ctx, const int32_t *chosen, uint16_t *bm, uint16_t *am, int8_t *results,
                       int32_t *legal_counts)
 {
-    if (!ctx || !chosen || !results || !legal_counts) return fail(ctx, CRL_ERR_ARG, "crl_advance_fetch: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t G = ctx->W;
-    hipStream_t s = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->t_i32b, chosen, G * 4, hipMemcpyHostToDevice, s));
-    LAUNCH(ctx, k_advance, ctx->d, (const int32_t *)ctx->t_i32b, ctx->t_u16a, ctx->t_u16b);
-    if (bm) HIP_TRY(ctx, hipMemcpyAsync(bm, ctx->t_u16a, G * 2, hipMemcpyDeviceToHost, s));
-    if (am) HIP_TRY(ctx, hipMemcpyAsync(am, ctx->t_u16b, G * 2, hipMemcpyDeviceToHost, s));
-    LAUNCH(ctx, k_game_scalars, ctx->d, ctx->t_i32c, (int8_t *)ctx->t_u8);
-    HIP_TRY(ctx, hipMemcpyAsync(results, ctx->t_u8, G, hipMemcpyDeviceToHost, s));
-    LAUNCH(ctx, k_legal_moves, ctx->d, ctx->t_moves, ctx->t_i32b);
-    HIP_TRY(ctx, hipMemcpyAsync(legal_counts, ctx->t_i32b, G * 4, hipMemcpyDeviceToHost, s));
+    ENTER(ctx, chosen && results && legal_counts);
+    TRY(play_chosen(ctx, chosen, nullptr, bm, am, nullptr, nullptr));
+    TRY(next_roots(ctx, results, legal_counts));
     return check_dev_error(ctx);
 }
 
 // ---- Tree(Node): the chosen child keeps its subtree across the move boundary ---------------------------------
-static int reroot_launch(crl_ctx *ctx, const int32_t *chosen, int next_sims, uint16_t *bm, uint16_t *am,
-                         int32_t *kept_nodes, int32_t *kept_children)
-{
-    const size_t G = ctx->W;
-    hipStream_t s = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->t_i32b, chosen, G * 4, hipMemcpyHostToDevice, s));
-    LAUNCH(ctx, k_reroot, ctx->d, (const int32_t *)ctx->t_i32b, next_sims, ctx->t_u16a, ctx->t_u16b, ctx->t_i32d,
-           ctx->t_i32e);
-    if (bm) HIP_TRY(ctx, hipMemcpyAsync(bm, ctx->t_u16a, G * 2, hipMemcpyDeviceToHost, s));
-    if (am) HIP_TRY(ctx, hipMemcpyAsync(am, ctx->t_u16b, G * 2, hipMemcpyDeviceToHost, s));
-    if (kept_nodes) HIP_TRY(ctx, hipMemcpyAsync(kept_nodes, ctx->t_i32d, G * 4, hipMemcpyDeviceToHost, s));
-    if (kept_children) HIP_TRY(ctx, hipMemcpyAsync(kept_children, ctx->t_i32e, G * 4, hipMemcpyDeviceToHost, s));
-    return CRL_OK;
-}
-
 int crl_reroot(crl_ctx *ctx, const int32_t *chosen, int next_sims, uint16_t *bm, uint16_t *am)
 {
-    if (!ctx || !chosen || next_sims < 0) return fail(ctx, CRL_ERR_ARG, "crl_reroot: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = reroot_launch(ctx, chosen, next_sims, bm, am, nullptr, nullptr);
-    return rc != CRL_OK ? rc : check_dev_error(ctx);
+    ENTER(ctx, chosen && next_sims >= 0);
+    TRY(play_chosen(ctx, chosen, &next_sims, bm, am, nullptr, nullptr));
+    return check_dev_error(ctx);
 }
 
 int crl_reroot_fetch(crl_ctx *ctx, const int32_t *chosen, int next_sims, uint16_t *bm, uint16_t *am, int8_t *results,
                      int32_t *legal_counts, int32_t *kept_nodes, int32_t *kept_children)
 {
-    if (!ctx || !chosen || next_sims < 0 || !results || !legal_counts || !kept_nodes || !kept_children)
-        return fail(ctx, CRL_ERR_ARG, "crl_reroot_fetch: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t G = ctx->W;
-    hipStream_t s = ctx->stream;
-    int rc = reroot_launch(ctx, chosen, next_sims, bm, am, kept_nodes, kept_children);
-    if (rc != CRL_OK) return rc;
-    LAUNCH(ctx, k_game_scalars, ctx->d, ctx->t_i32c, (int8_t *)ctx->t_u8);
-    HIP_TRY(ctx, hipMemcpyAsync(results, ctx->t_u8, G, hipMemcpyDeviceToHost, s));
-    LAUNCH(ctx, k_legal_moves, ctx->d, ctx->t_moves, ctx->t_i32b);
-    HIP_TRY(ctx, hipMemcpyAsync(legal_counts, ctx->t_i32b, G * 4, hipMemcpyDeviceToHost, s));
+    ENTER(ctx, chosen && next_sims >= 0 && results && legal_counts && kept_nodes && kept_children);
+    TRY(play_chosen(ctx, chosen, &next_sims, bm, am, kept_nodes, kept_children));
+    TRY(next_roots(ctx, results, legal_counts));
     return check_dev_error(ctx);
 }
 
 int crl_copy_game_tree(crl_ctx *ctx, int dst, int src)
 {
-    if (!ctx || dst < 0 || src < 0 || dst >= ctx->d.G || src >= ctx->d.G)
+    ENTER(ctx, true);
+    if (dst < 0 || src < 0 || dst >= ctx->d.G || src >= ctx->d.G)
         return fail(ctx, CRL_ERR_ARG, "crl_copy_game_tree: bad slot");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (dst != src) {
-        hipLaunchKernelGGL(k_copy_game, dim3(1), dim3(64), 0, ctx->stream, ctx->d, dst, src);
-        HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_copy_tree, dim3(64), dim3(64), 0, ctx->stream, ctx->d, dst, src);
-        HIP_TRY(ctx, hipGetLastError());
+        LAUNCH_N(ctx, 1, k_copy_game, ctx->d, dst, src);
+        LAUNCH_N(ctx, 64, k_copy_tree, ctx->d, dst, src);
     }
     return CRL_OK;
 }
 
 int crl_fetch_tree(crl_ctx *ctx, int slot, void *nodes, int node_cap, void *edges, int edge_cap, int32_t *info)
 {
-    if (!ctx || slot < 0 || slot >= ctx->d.G || !info || node_cap < 0 || edge_cap < 0)
-        return fail(ctx, CRL_ERR_ARG, "crl_fetch_tree: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, slot >= 0 && slot < ctx->d.G && info && node_cap >= 0 && edge_cap >= 0);
     GameRow row;
-    HIP_TRY(ctx, hipMemcpyAsync(&row, ctx->d.game + slot, sizeof row, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, &row, ctx->d.game + slot, 1));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const bool live = !row.root_dead;
     info[0] = live ? row.n_nodes : 0;
@@ -677,23 +691,20 @@ int crl_fetch_tree(crl_ctx *ctx, int slot, void *nodes, int node_cap, void *edge
     if (info[0] > ctx->d.N || info[1] > ctx->d.ECAP) return fail(ctx, CRL_ERR_STATE, "crl_fetch_tree: tree counters out of range");
     if (nodes && info[0] > 0) {
         if (info[0] > node_cap) return fail(ctx, CRL_ERR_CAPACITY, "crl_fetch_tree: node buffer too small");
-        HIP_TRY(ctx, hipMemcpyAsync(nodes, ctx->d.node + (size_t)slot * ctx->d.N, (size_t)info[0] * sizeof(NodeRow),
-                                    hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, to_host(ctx, (NodeRow *)nodes, ctx->d.node + (size_t)slot * ctx->d.N, info[0]));
     }
     if (edges && info[1] > 0) {
         if (info[1] > edge_cap) return fail(ctx, CRL_ERR_CAPACITY, "crl_fetch_tree: edge buffer too small");
-        HIP_TRY(ctx, hipMemcpyAsync(edges, ctx->d.edge + (size_t)slot * ctx->d.ECAP, (size_t)info[1] * sizeof(Edge),
-                                    hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, to_host(ctx, (Edge *)edges, ctx->d.edge + (size_t)slot * ctx->d.ECAP, info[1]));
     }
     return check_dev_error(ctx);
 }
 
 int crl_counters(crl_ctx *ctx, uint64_t *out6)
 {
-    if (!ctx || !out6) return CRL_ERR_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, out6);
     std::vector<unsigned long long> h((size_t)ctx->d.G * CNT_N);
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->d.counters, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, to_host(ctx, h.data(), ctx->d.counters, h.size()));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < CNT_N; k++) out6[k] = 0;
     for (int g = 0; g < ctx->d.G; g++)
@@ -705,45 +716,32 @@ int crl_counters(crl_ctx *ctx, uint64_t *out6)
 int crl_rollout_games(crl_ctx *ctx, const uint32_t *words, const int32_t *counts, int stride, int chunks,
                       int max_moves, int32_t *played, int32_t *used, int8_t *chunk_results)
 {
-    if (!ctx || !words || !counts || !played || !used || !chunk_results || stride < 1 || chunks < 1 || max_moves < 0 ||
-        (long long)chunks * max_moves > 0x7FFFFFFFll)
-        return fail(ctx, CRL_ERR_ARG, "crl_rollout_games: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t G = ctx->W;
-    const size_t wb = G * (size_t)stride * sizeof(u32), cb = G * (size_t)chunks;
-    unsigned char *buf = nullptr;                 // setup-time call: a scratch buffer per call is fine
-    HIP_TRY(ctx, hipMalloc((void **)&buf, wb + cb));
-    u32 *dwords = (u32 *)buf;
-    int8_t *dres = (int8_t *)(buf + wb);
-    hipStream_t s = ctx->stream;
-    hipError_t e = hipMemcpyAsync(dwords, words, wb, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->t_i32b, counts, G * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->t_i32c, played, G * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_rollout_games, dim3((unsigned)G), dim3(64), 0, s, ctx->d, (const u32 *)dwords,
-                           (const int32_t *)ctx->t_i32b, stride, chunks, max_moves, ctx->t_i32c, ctx->t_i32d, dres);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(played, ctx->t_i32c, G * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(used, ctx->t_i32d, G * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(chunk_results, dres, cb, hipMemcpyDeviceToHost, s);
-    hipError_t es = hipStreamSynchronize(s);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(ctx, CRL_ERR_HIP, hipGetErrorString(e));
-    if (es != hipSuccess) return fail(ctx, CRL_ERR_HIP, hipGetErrorString(es));
+    ENTER(ctx, words && counts && played && used && chunk_results && stride >= 1 && chunks >= 1 && max_moves >= 0 &&
+                   (long long)chunks * max_moves <= 0x7FFFFFFFll);
+    const size_t G = ctx->W, nw = G * (size_t)stride, nr = G * (size_t)chunks;
+    Scratch buf(ctx);                             // the words of every slot, then its chunk results
+    HIP_TRY(ctx, buf.alloc(nw * sizeof(u32) + nr));
+    u32 *dwords = (u32 *)buf.p;
+    int8_t *dres = (int8_t *)(dwords + nw);
+    HIP_TRY(ctx, to_dev(ctx, dwords, words, nw));
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, counts, G));
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_i32c, played, G));
+    LAUNCH(ctx, k_rollout_games, ctx->d, (const u32 *)dwords, (const int32_t *)ctx->t_i32b, stride, chunks, max_moves,
+           ctx->t_i32c, ctx->t_i32d, dres);
+    HIP_TRY(ctx, to_host(ctx, played, ctx->t_i32c, G));
+    HIP_TRY(ctx, to_host(ctx, used, ctx->t_i32d, G));
+    HIP_TRY(ctx, to_host(ctx, chunk_results, dres, nr));
     return check_dev_error(ctx);
 }
 
 int crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, const uint64_t *dev_keys,
                 void *dev_value_f32, int8_t *dev_results_i8, uint16_t *dev_plies_u16)
 {
-    if (!ctx || (root_source != CRL_ROLLOUT_GAMES && root_source != CRL_ROLLOUT_LEAVES) || repetitions < 1 ||
-        max_moves < 0 || max_moves > 65534 || !dev_keys || !dev_value_f32 ||
-        (long long)ctx->W * repetitions > 0x7FFFFFFFll)
-        return fail(ctx, CRL_ERR_ARG, "crl_rollout: bad argument");
+    ENTER(ctx, (root_source == CRL_ROLLOUT_GAMES || root_source == CRL_ROLLOUT_LEAVES) && repetitions >= 1 &&
+                   max_moves >= 0 && max_moves <= 65534 && dev_keys && dev_value_f32 &&
+                   (long long)ctx->W * repetitions <= 0x7FFFFFFFll);
     if (root_source == CRL_ROLLOUT_LEAVES && !ctx->search_begun)
         return fail(ctx, CRL_ERR_STATE, "crl_rollout: CRL_ROLLOUT_LEAVES needs a search (crl_search_begin first)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)ctx->W * repetitions;
     if ((!dev_results_i8 || !dev_plies_u16) && n > ctx->roll_cap) {
         int8_t *r = nullptr;
@@ -754,12 +752,8 @@ int crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, c
     }
     int8_t *res = dev_results_i8 ? dev_results_i8 : ctx->roll_results;
     u16 *pl = dev_plies_u16 ? dev_plies_u16 : ctx->roll_plies;
-    hipLaunchKernelGGL(k_rollout, dim3((unsigned)n), dim3(64), 0, ctx->stream, ctx->d, root_source, repetitions,
-                       max_moves, (const u64 *)dev_keys, res, pl);
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_rollout_mean, dim3((unsigned)ctx->W), dim3(64), 0, ctx->stream, (const int8_t *)res,
-                       repetitions, (float *)dev_value_f32);
-    HIP_TRY(ctx, hipGetLastError());
+    LAUNCH_N(ctx, (unsigned)n, k_rollout, ctx->d, root_source, repetitions, max_moves, (const u64 *)dev_keys, res, pl);
+    LAUNCH(ctx, k_rollout_mean, (const int8_t *)res, repetitions, (float *)dev_value_f32);
     return CRL_OK;
 }
 
@@ -767,30 +761,28 @@ int crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, c
 int crl_opponent_moves(crl_ctx *ctx, const int32_t *depths, int push, int64_t node_limit, uint16_t *moves,
                        int32_t *scores, int64_t *nodes, uint8_t *flags)
 {
-    if (!ctx || !depths || !moves || node_limit < 1)
-        return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves: bad argument");
+    ENTER(ctx, depths && moves && node_limit >= 1);
     const size_t G = ctx->W;
     for (size_t i = 0; i < G; i++)
         if (depths[i] < 0 || depths[i] > CRL_OPP_MAX_DEPTH)
             return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves: a depth outside 0 .. CRL_OPP_MAX_DEPTH");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int64_t) <= sizeof(double), "node counts in t_f64");
     long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->t_i32b, depths, G * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
     LAUNCH(ctx, k_opponent_moves, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_limit, ctx->t_u16a,
            ctx->t_i32c, dnodes, ctx->t_u8);
-    HIP_TRY(ctx, hipMemcpyAsync(moves, ctx->t_u16a, G * sizeof(u16), hipMemcpyDeviceToHost, s));
-    if (scores) HIP_TRY(ctx, hipMemcpyAsync(scores, ctx->t_i32c, G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (nodes) HIP_TRY(ctx, hipMemcpyAsync(nodes, dnodes, G * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (flags) HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->t_u8, G, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, to_host(ctx, moves, ctx->t_u16a, G));
+    HIP_TRY(ctx, to_host(ctx, scores, ctx->t_i32c, G));
+    HIP_TRY(ctx, to_host(ctx, (long long *)nodes, dnodes, G));
+    HIP_TRY(ctx, to_host(ctx, flags, ctx->t_u8, G));
     return check_dev_error(ctx);
 }
 
 // ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------------------------
 int crl_wave_config(crl_ctx *ctx, int threads)
 {
-    if (!ctx || threads < 1 || threads > CRL_WAVE_MAX_THREADS) return fail(ctx, CRL_ERR_ARG, "crl_wave_config: threads must lie in [1, 64]");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ENTER(ctx, true);
+    if (threads < 1 || threads > CRL_WAVE_MAX_THREADS) return fail(ctx, CRL_ERR_ARG, "crl_wave_config: threads must lie in [1, 64]");
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     {   // pending simulations are read from the DEVICE (entry points captured into a hipGraph run on the host only once)
         std::vector<GameRow> rows(ctx->d.G);
@@ -835,78 +827,66 @@ int crl_wave_config(crl_ctx *ctx, int threads)
 
 static int wave_ready(crl_ctx *ctx, const char *what)
 {
-    if (!ctx) return CRL_ERR_ARG;
+    if (!ctx) return fail(ctx, CRL_ERR_ARG, std::string(what) + ": bad argument");
     if (!ctx->d.wave) return fail(ctx, CRL_ERR_STATE, std::string(what) + ": crl_wave_config first");
     if (ctx->d.policy_fmt != CRL_POLICY_FULL)
         return fail(ctx, CRL_ERR_STATE, std::string(what) + ": waves read full policy vectors (CRL_POLICY_FULL) only");
     return CRL_OK;
 }
 
+// how the wave entry points begin: the state refusals come before the argument check
+#define WAVE_ENTER(ctx, ok)                                                             \
+    do {                                                                                \
+        TRY(wave_ready(ctx, __func__));                                                 \
+        ENTER(ctx, ok);                                                                 \
+    } while (0)
+
 int crl_wave_begin(crl_ctx *ctx, int n_sims)
 {
-    int rc = wave_ready(ctx, "crl_wave_begin");
-    if (rc != CRL_OK) return rc;
+    WAVE_ENTER(ctx, true);
     if (n_sims < 1 || n_sims > ctx->d.N - 1) return fail(ctx, CRL_ERR_ARG, "crl_wave_begin: n_sims must lie in [1, max_sims]");
     if (!ctx->search_begun) return fail(ctx, CRL_ERR_STATE, "crl_wave_begin: needs crl_search_begin first");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     LAUNCH(ctx, k_wave_begin, ctx->d, n_sims);
     return CRL_OK;
 }
 
 int crl_wave_select(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32, void *dev_planes_s1)
 {
-    int rc = wave_ready(ctx, "crl_wave_select");
-    if (rc != CRL_OK) return rc;
-    if (!dev_policy_s2_f32 || !dev_value_s2_f32 || !dev_planes_s1) return fail(ctx, CRL_ERR_ARG, "crl_wave_select: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WAVE_ENTER(ctx, dev_policy_s2_f32 && dev_value_s2_f32 && dev_planes_s1);
     LAUNCH(ctx, k_wave_select, ctx->d, (const float *)dev_policy_s2_f32, (const float *)dev_value_s2_f32, dev_planes_s1);
     return CRL_OK;
 }
 
 int crl_wave_reply(crl_ctx *ctx, const void *dev_policy_s1_f32, void *dev_planes_s2)
 {
-    int rc = wave_ready(ctx, "crl_wave_reply");
-    if (rc != CRL_OK) return rc;
-    if (!dev_policy_s1_f32 || !dev_planes_s2) return fail(ctx, CRL_ERR_ARG, "crl_wave_reply: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WAVE_ENTER(ctx, dev_policy_s1_f32 && dev_planes_s2);
     LAUNCH(ctx, k_wave_reply, ctx->d, (const float *)dev_policy_s1_f32, dev_planes_s2);
     return CRL_OK;
 }
 
 int crl_wave_backup(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32)
 {
-    int rc = wave_ready(ctx, "crl_wave_backup");
-    if (rc != CRL_OK) return rc;
-    if (!dev_policy_s2_f32 || !dev_value_s2_f32) return fail(ctx, CRL_ERR_ARG, "crl_wave_backup: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WAVE_ENTER(ctx, dev_policy_s2_f32 && dev_value_s2_f32);
     LAUNCH(ctx, k_wave_backup, ctx->d, (const float *)dev_policy_s2_f32, (const float *)dev_value_s2_f32);
     return CRL_OK;
 }
 
 int crl_wave_remaining(crl_ctx *ctx, int32_t *max_remaining)
 {
-    int rc = wave_ready(ctx, "crl_wave_remaining");
-    if (rc != CRL_OK) return rc;
-    if (!max_remaining) return fail(ctx, CRL_ERR_ARG, "crl_wave_remaining: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_wave_remaining, dim3(1), dim3(64), 0, ctx->stream, ctx->d, ctx->W, ctx->t_i32b);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(max_remaining, ctx->t_i32b, 4, hipMemcpyDeviceToHost, ctx->stream));
+    WAVE_ENTER(ctx, max_remaining);
+    LAUNCH_N(ctx, 1, k_wave_remaining, ctx->d, ctx->W, ctx->t_i32b);
+    HIP_TRY(ctx, to_host(ctx, max_remaining, ctx->t_i32b, 1));
     return check_dev_error(ctx);
 }
 
 int crl_wave_stats(crl_ctx *ctx, int32_t *waves, int32_t *short_waves, int32_t *leaves)
 {
-    int rc = wave_ready(ctx, "crl_wave_stats");
-    if (rc != CRL_OK) return rc;
-    if (!waves || !short_waves || !leaves) return fail(ctx, CRL_ERR_ARG, "crl_wave_stats: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WAVE_ENTER(ctx, waves && short_waves && leaves);
     const int G = ctx->W;
-    hipLaunchKernelGGL(k_wave_stats, dim3(1), dim3(64), 0, ctx->stream, ctx->d, G, ctx->t_i32a);
-    HIP_TRY(ctx, hipGetLastError());
+    LAUNCH_N(ctx, 1, k_wave_stats, ctx->d, G, ctx->t_i32a);
     std::vector<int32_t> h((size_t)G * WST_N);
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->t_i32a, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    rc = check_dev_error(ctx);
+    HIP_TRY(ctx, to_host(ctx, h.data(), ctx->t_i32a, h.size()));
+    const int rc = check_dev_error(ctx);
     for (int g = 0; g < G; g++) {
         waves[g] = h[(size_t)g * WST_N + WST_WAVES];
         short_waves[g] = h[(size_t)g * WST_N + WST_SHORT];
@@ -1009,7 +989,7 @@ static int layer_trunk_launch(hipStream_t st, bool bits, const void *planes, con
     }
     for (conv_t k : { stem, c1, c2, c3 }) {
         hipError_t ea = allow_big_lds((const void *)k, G::LDS_BYTES);
-        if (ea != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(ea));
+        if (ea != hipSuccess) return hip_rc(ea);
     }
     const unsigned char *w = (const unsigned char *)wts;
     const float *b = (const float *)bias;
@@ -1029,9 +1009,7 @@ static int layer_trunk_launch(hipStream_t st, bool bits, const void *planes, con
         conv(last ? c3 : c2, B, A, 2 + 2 * blk, last);
         w += G::conv_bytes(8);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
-    return CRL_OK;
+    return hip_rc(hipGetLastError());
 }
 }  // extern "C++"
 
@@ -1111,16 +1089,14 @@ static int trunk_forward(void *hip_stream, int filters, const void *dev_planes_f
     }
     if (!kern) return fail(nullptr, CRL_ERR_ARG, "crl_trunk_forward: no kernel for this shape");
     hipError_t ea = allow_big_lds((const void *)kern, lds_bytes);
-    if (ea != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(ea));
+    if (ea != hipSuccess) return hip_rc(ea);
     hipLaunchKernelGGL(kern, dim3(n_boards / pk.nb), dim3(512),
                        lds_bytes, (hipStream_t)hip_stream,
                        (const unsigned char *)dev_planes_f16, (const unsigned char *)dev_wtiles_f16,
                        (const float *)dev_bias_f32, (float *)dev_out_f32, n_blocks,
                        (const float *)dev_head_w_f32, (const float *)dev_head_b_f32,
                        (float *)dev_head_out_f32);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
-    return CRL_OK;
+    return hip_rc(hipGetLastError());
 }
 
 int crl_trunk_forward_indexed(void *hip_stream, int filters, const void *dev_bitplanes_u64,
@@ -1148,13 +1124,11 @@ int crl_reply_margin(void *hip_stream, const void *dev_priors_f32, const int32_t
     hipStream_t st = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(crl_heads::k_zero_word, dim3(1), dim3(64), 0, st, (int *)dev_list);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) return hip_rc(e);
     hipLaunchKernelGGL(crl_heads::k_reply_margin, dim3((unsigned)((n_boards + 3) / 4)), dim3(256), 0, st,
                        (const float *)dev_priors_f32, (const int *)dev_counts, n_boards, dev_log_margin_f32,
                        rows_are_logits ? 1 : 0, (int *)dev_list);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
-    return CRL_OK;
+    return hip_rc(hipGetLastError());
 }
 
 int crl_trunk_kernel_name(int filters, int n_boards, int flags, char *buf, int buf_len)
@@ -1255,7 +1229,7 @@ static int heads_forward(void *hip_stream, const void *act, int n_boards, const 
         if (legal) {
             auto kern = crl_heads::k_policy_head<1, true>;
             hipError_t ea = allow_big_lds((const void *)kern, crl_heads::LEGAL_LDS_BYTES);
-            if (ea != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(ea));
+            if (ea != hipSuccess) return hip_rc(ea);
             hipLaunchKernelGGL(kern, dim3(blocks + vblocks), dim3(512), crl_heads::LEGAL_LDS_BYTES, st,
                                (const float *)act, n_boards, (const unsigned char *)pol_wp, (const float *)pol_bias,
                                (float *)pol_out, (const unsigned short *)labels, (const int *)counts, (int)blocks,
@@ -1269,9 +1243,7 @@ static int heads_forward(void *hip_stream, const void *act, int n_boards, const 
                                (float *)val_out);
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
-    return CRL_OK;
+    return hip_rc(hipGetLastError());
 }
 
 int crl_heads_raw_supported(int n_boards) { return n_boards >= 1 && heads_sliced(n_boards) ? 1 : 0; }
@@ -1326,9 +1298,7 @@ static int train_op(void *hip_stream, const void *src, void *dst, int n_boards, 
     else
         hipLaunchKernelGGL(crl_train::k_col2im3x3, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream,
                            (const float4 *)src, (float4 *)dst, total, c4);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
-    return CRL_OK;
+    return hip_rc(hipGetLastError());
 }
 
 // ---- measurement: (id, device wall clock) appended to a ring, capturable into a hipGraph (bench.py) ---------------------
@@ -1344,17 +1314,14 @@ int crl_stamp(void *hip_stream, uint64_t *dev_ring, uint32_t capacity, uint32_t 
 {
     if (!dev_ring || capacity < 1) return fail(nullptr, CRL_ERR_ARG, "crl_stamp: bad argument");
     hipLaunchKernelGGL(k_stamp, dim3(1), dim3(1), 0, (hipStream_t)hip_stream, (unsigned long long *)dev_ring, capacity, id);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
-    return CRL_OK;
+    return hip_rc(hipGetLastError());
 }
 
 int crl_stamp_clock_khz(int device)
 {
     int khz = 0;
     hipError_t e = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device);
-    if (e != hipSuccess) return fail(nullptr, CRL_ERR_HIP, hipGetErrorString(e));
-    return khz;
+    return e == hipSuccess ? khz : hip_rc(e);
 }
 
 int crl_im2col3x3_f32(void *hip_stream, const void *dev_x_f32, void *dev_cols_f32, int n_boards, int channels)

@@ -28,6 +28,8 @@ one among the legal schedules of its virtual-loss thread pool (mctree.py:12,
 calls evaluate G*T rows (row = game * T + thread), and the leaves are backed up
 in thread order.  Waves may end short, so the number of steps of a search is
 data-dependent, between ceil(n/T) and n; a game whose budget is spent idles.
+The step is the same list of phases: the engine picks its kernel triple once
+(crl_sim_* or crl_wave_* select / reply / backup) and the tower calls see more rows.
 """
 import gc
 
@@ -261,8 +263,12 @@ class LockstepEngine(object):
         self.ctx = _lib.Context(n_games, max_nodes - 1, max_plies=max_plies, device=device,
                                 numpy_legacy=(numpy_promotion == "legacy"))
         self.evaluator = evaluator
+        # the kernel triple of a step -- select, reply and the last backup -- chosen once: one leaf per game or a wave
         if threads > 1:
             self.ctx.wave_config(threads)
+            self._select, self._reply, self._backup = self.ctx.wave_select, self.ctx.wave_reply, self.ctx.wave_backup
+        else:
+            self._select, self._reply, self._backup = self.ctx.sim_select_expand, self.ctx.sim_reply, self.ctx.sim_backup
         G = n_games * threads                    # evaluator rows: one per game, or game-major one per (game, thread)
         # An evaluator that runs the fused HIP trunk takes the encoder's compact form -- 128 plane
         # bitboards (1 KiB) per position -- and expands it on chip: the 16-KiB fp16 planes are then
@@ -270,16 +276,18 @@ class LockstepEngine(object):
         if bitplanes is None:
             bitplanes = bool(getattr(evaluator, "accepts_bitplanes", False))
         self.bitplanes = bitplanes
+        # every tensor with one row per evaluator row, by attribute name, at full size (``shrink`` re-slices from here)
+        rows = self._rows = {}
         if bitplanes:
             self.ctx.set_plane_format(True)
-            self.planes_s1 = torch.zeros((G, _lib.PLANES), dtype=torch.int64, device=self.dev)
-            self.planes_s2 = torch.zeros((G, _lib.PLANES), dtype=torch.int64, device=self.dev)
+            rows["planes_s1"] = torch.zeros((G, _lib.PLANES), dtype=torch.int64, device=self.dev)
+            rows["planes_s2"] = torch.zeros((G, _lib.PLANES), dtype=torch.int64, device=self.dev)
         else:
-            self.planes_s1 = torch.zeros((G, 8, 8, _lib.PLANES), dtype=torch.float16, device=self.dev)
-            self.planes_s2 = torch.zeros((G, 8, 8, _lib.PLANES), dtype=torch.float16, device=self.dev)
-        self.pol_s1 = torch.zeros((G, _lib.N_LABELS), dtype=torch.float32, device=self.dev)
-        self.pol_s2 = torch.zeros((G, _lib.N_LABELS), dtype=torch.float32, device=self.dev)
-        self.val_s2 = torch.zeros((G,), dtype=torch.float32, device=self.dev)
+            rows["planes_s1"] = torch.zeros((G, 8, 8, _lib.PLANES), dtype=torch.float16, device=self.dev)
+            rows["planes_s2"] = torch.zeros((G, 8, 8, _lib.PLANES), dtype=torch.float16, device=self.dev)
+        rows["pol_s1"] = torch.zeros((G, _lib.N_LABELS), dtype=torch.float32, device=self.dev)
+        rows["pol_s2"] = torch.zeros((G, _lib.N_LABELS), dtype=torch.float32, device=self.dev)
+        rows["val_s2"] = torch.zeros((G,), dtype=torch.float32, device=self.dev)
         # An evaluator with ``accepts_legal_labels`` (the HIP heads) is told which labels the search
         # will read -- the legal moves of S1 / S2, listed by the kernel that generated them -- and
         # writes only those probabilities: priors [G,256] instead of policy [G,1968] per call
@@ -287,12 +295,11 @@ class LockstepEngine(object):
         if legal_priors is None:
             legal_priors = bool(getattr(evaluator, "accepts_legal_labels", False))
         self.legal_priors = legal_priors
-        self.pri_s1 = self.pri_s2 = None
         self.raw_priors = False
         self._want_raw = raw_priors              # None: wherever the heads support it; False: never
         if legal_priors:
-            self.pri_s1 = torch.zeros((G, _lib.MAX_MOVES), dtype=torch.float32, device=self.dev)
-            self.pri_s2 = torch.zeros((G, _lib.MAX_MOVES), dtype=torch.float32, device=self.dev)
+            rows["pri_s1"] = torch.zeros((G, _lib.MAX_MOVES), dtype=torch.float32, device=self.dev)
+            rows["pri_s2"] = torch.zeros((G, _lib.MAX_MOVES), dtype=torch.float32, device=self.dev)
             self._lab_s1 = self.ctx.eval_labels(0)
             self._lab_s2 = self.ctx.eval_labels(1)
             # small batches: the heads leave logits + the softmax statistics of their label slices and
@@ -303,10 +310,9 @@ class LockstepEngine(object):
             self.ctx.set_policy_stats(0, self.stats_s1.data_ptr())
             self.ctx.set_policy_stats(1, self.stats_s2.data_ptr())
             self._pick_policy_format()
-        else:
-            self.pri_s1, self.pri_s2 = self.pol_s1, self.pol_s2
-        self._full = (self.planes_s1, self.planes_s2, self.pol_s1, self.pol_s2, self.val_s2,
-                      self.pri_s1, self.pri_s2)
+        else:                                    # (always so with threads > 1) the search reads the full policy vectors
+            rows["pri_s1"], rows["pri_s2"] = rows["pol_s1"], rows["pol_s2"]
+        self._take_rows(G)
         # simulate=Rollouts(...): leaves are valued by random playouts (simulation.py:19-34, the alternative
         # mctree.py:272-274 names) instead of the value head -- a fifth phase that overwrites val_s2.  The
         # tower still runs: its priors are needed.  The engine owns the stream keys (set_stream_keys).
@@ -315,6 +321,11 @@ class LockstepEngine(object):
             self.stream_keys = torch.from_numpy(stream_keys(simulate.seed, G).view(np.int64)).to(self.dev)
             self.roll_results = torch.zeros((G, simulate.repetitions), dtype=torch.int8, device=self.dev)
             self.roll_plies = torch.zeros((G, simulate.repetitions), dtype=torch.int16, device=self.dev)
+        # one step: (the stamp in front of a phase when a StampRing is attached, the phase method by name)
+        self._plan = [(STAMP_STEP, "phase_select_expand"), (STAMP_SELECTED, "phase_tower_s1"),
+                      (STAMP_S1_DONE, "phase_reply"), (STAMP_REPLIED, "phase_tower_s2")]
+        if simulate is not None:
+            self._plan.append((STAMP_ROLLOUT, "phase_rollout"))
         self.use_graph = use_graph
         if steps_per_graph is not None:
             if int(steps_per_graph) < 1:
@@ -342,16 +353,20 @@ class LockstepEngine(object):
         self._graph = None
         self.ctx.close()
 
+    def _take_rows(self, n):
+        """self.planes_s1 ... self.pri_s2: the first ``n`` rows of every registered row tensor."""
+        for name, t in self._rows.items():
+            setattr(self, name, t[:n])
+
     def shrink(self, n):
         """Keep only slots [0, n) in the lockstep batch (finite runs: the batch thins out as games
         end; the caller compacts the running games into the first slots with ``ctx.copy_game``).
         Every later launch, tower batch and the re-captured hipGraph cover n games."""
-        if not 0 < n <= self._full[0].shape[0] // self.threads or n % 4:
+        if not 0 < n <= self._rows["val_s2"].shape[0] // self.threads or n % 4:
             raise ValueError("shrink: n must be a multiple of 4 within the engine's capacity")
         self.ctx.set_window(0, n)
         self.G = n
-        (self.planes_s1, self.planes_s2, self.pol_s1, self.pol_s2, self.val_s2,
-         self.pri_s1, self.pri_s2) = (t[:n * self.threads] for t in self._full)
+        self._take_rows(n * self.threads)
         if self.legal_priors:
             self._pick_policy_format()
         self._graph = None
@@ -366,9 +381,14 @@ class LockstepEngine(object):
         if val_out is not None:
             val_out.copy_(val)
 
-    # the four phases of one simulation step (bench.py times them one by one)
+    def _root_rows(self, t):
+        """The rows of ``t`` that belong to the roots: with ``threads`` > 1 the first G of its G*T rows."""
+        return t if self.threads == 1 else t[:self.G]
+
+    # the four phases of one step (bench.py times them one by one); with threads > 1 the same four on G*T rows, the
+    # two kernel phases being the wave kernels
     def phase_select_expand(self):
-        self.ctx.sim_select_expand(self.pri_s2.data_ptr(), self.val_s2.data_ptr(), self.planes_s1.data_ptr())
+        self._select(self.pri_s2.data_ptr(), self.val_s2.data_ptr(), self.planes_s1.data_ptr())
 
     def phase_tower_s1(self):
         if self.legal_priors:
@@ -378,7 +398,7 @@ class LockstepEngine(object):
             self._eval_into(self.planes_s1, self.pol_s1, None)
 
     def phase_reply(self):
-        self.ctx.sim_reply(self.pri_s1.data_ptr(), self.planes_s2.data_ptr())
+        self._reply(self.pri_s1.data_ptr(), self.planes_s2.data_ptr())
 
     def phase_tower_s2(self):
         if self.legal_priors:
@@ -394,13 +414,6 @@ class LockstepEngine(object):
         self.ctx.rollout(_lib.ROLLOUT_LEAVES, sim.repetitions, sim.max_moves, self.stream_keys.data_ptr(),
                          self.val_s2.data_ptr(), self.roll_results.data_ptr(), self.roll_plies.data_ptr())
 
-    # threads > 1: the two kernel phases of a wave step (the tower phases are the same calls on G*T rows)
-    def phase_wave_select(self):
-        self.ctx.wave_select(self.pol_s2.data_ptr(), self.val_s2.data_ptr(), self.planes_s1.data_ptr())
-
-    def phase_wave_reply(self):
-        self.ctx.wave_reply(self.pol_s1.data_ptr(), self.planes_s2.data_ptr())
-
     def set_stream_keys(self, keys):
         """The 64-bit stream key of every slot (default: seed * 2^32 + slot index), copied into the tensor the
         captured step reads: int64 / uint64 tensor or array of n_games entries."""
@@ -413,34 +426,14 @@ class LockstepEngine(object):
         self.stream_keys.copy_(keys.to(self.dev).view(torch.int64).reshape(-1))
 
     def _step_body(self):
+        # with a StampRing attached this is the measurement build of the same step (bench.py): a one-thread stamp
+        # kernel in front of every phase, captured into the graph with them; the evaluator stamps its own trunk
+        # launches (ChessModel.stamp_fn)
         st = self.stamps
-        if self.threads > 1:
-            self.phase_wave_select()
-            self.phase_tower_s1()
-            self.phase_wave_reply()
-            self.phase_tower_s2()
-            return
-        if st is None:
-            self.phase_select_expand()
-            self.phase_tower_s1()
-            self.phase_reply()
-            self.phase_tower_s2()
-            if self.simulate is not None:
-                self.phase_rollout()
-            return
-        # measurement build of the same step (bench.py): one-thread stamp kernels between the phases, captured into
-        # the graph with them; the evaluator stamps its own trunk launches (ChessModel.stamp_fn)
-        st.stamp(STAMP_STEP)
-        self.phase_select_expand()
-        st.stamp(STAMP_SELECTED)
-        self.phase_tower_s1()
-        st.stamp(STAMP_S1_DONE)
-        self.phase_reply()
-        st.stamp(STAMP_REPLIED)
-        self.phase_tower_s2()
-        if self.simulate is not None:
-            st.stamp(STAMP_ROLLOUT)
-            self.phase_rollout()
+        for stamp_id, phase in self._plan:
+            if st is not None:
+                st.stamp(stamp_id)
+            getattr(self, phase)()
 
     def set_stamps(self, ring):
         """Attach (or with None detach) a StampRing: ``run_steps`` then replays the STAMPED build of the step (captured
@@ -561,10 +554,7 @@ class LockstepEngine(object):
             self.ctx.search_begin_kept(self.planes_s2.data_ptr())
         else:
             self.ctx.search_begin(self.planes_s2.data_ptr())
-        if self.threads > 1:                     # the roots are the first G rows of the G*T-row buffers
-            self._eval_into(self.planes_s2[:self.G], self.pol_s2[:self.G], self.val_s2[:self.G])
-        else:
-            self._eval_into(self.planes_s2, self.pol_s2, self.val_s2)
+        self._eval_into(self._root_rows(self.planes_s2), self._root_rows(self.pol_s2), self._root_rows(self.val_s2))
         self.ctx.search_root_priors(self.pol_s2.data_ptr())
 
     def search(self, n_sims, keep_root=False):
@@ -577,7 +567,7 @@ class LockstepEngine(object):
             self.run_waves(n_sims)
             return
         self.run_steps(n_sims)
-        self.ctx.sim_backup(self.pri_s2.data_ptr(), self.val_s2.data_ptr())
+        self._backup(self.pri_s2.data_ptr(), self.val_s2.data_ptr())
 
     def run_waves(self, n_sims, while_enqueued=None):
         """After ``search_begin``: exactly ``n_sims`` simulations for every live game in waves of up to ``threads``,
@@ -601,7 +591,7 @@ class LockstepEngine(object):
             more = -(-left // T)
             self.run_steps(more)
             steps += more
-        self.ctx.wave_backup(self.pol_s2.data_ptr(), self.val_s2.data_ptr())
+        self._backup(self.pri_s2.data_ptr(), self.val_s2.data_ptr())
         self.wave_steps = steps
         return steps
 
@@ -630,10 +620,7 @@ class LockstepEngine(object):
         """agent.best_move(game, real_game=True) for the masked slots (+ gam.move(...))."""
         self._bind_stream()
         self.ctx.encode(self.planes_s1.data_ptr())
-        if self.threads > 1:
-            self._eval_into(self.planes_s1[:self.G], self.pol_s1[:self.G], None)
-        else:
-            self._eval_into(self.planes_s1, self.pol_s1, None)
+        self._eval_into(self._root_rows(self.planes_s1), self._root_rows(self.pol_s1), None)
         return self.ctx.greedy_moves(self.pol_s1.data_ptr(), mask=mask, push=push)
 
     def load_games(self, games):

@@ -26,6 +26,32 @@ def test_library_exports_every_symbol_declared_in_the_header():
         assert hasattr(L, name), name
 
 
+# the symbols that take no context: crl_create makes one, the others are stateless or work on a stream the caller names
+NO_CONTEXT = {"crl_create", "crl_uci_label_moves", "crl_abi_version", "crl_source_hash", "crl_trunk_forward",
+              "crl_trunk_forward_bitplanes", "crl_trunk_forward_x", "crl_trunk_forward_indexed", "crl_trunk_set_small_batch",
+              "crl_trunk_kernel_name", "crl_trunk_workspace_bytes", "crl_heads_forward", "crl_heads_forward_legal",
+              "crl_heads_forward_legal_raw", "crl_heads_raw_supported", "crl_heads_set_sliced_max", "crl_reply_margin",
+              "crl_im2col3x3_f32", "crl_col2im3x3_f32", "crl_stamp", "crl_stamp_clock_khz"}
+
+
+def test_every_context_entry_point_refuses_a_null_context():
+    """Every function the header declares with ``crl_ctx *ctx`` first returns CRL_ERR_ARG for a NULL context (all
+    other arguments zero / NULL) before it touches HIP: no GPU needed.  crl_destroy returns nothing and
+    crl_last_error a string; both take NULL by contract."""
+    import ctypes
+    from chessrl_amd import _lib
+    text = open(os.path.join(ROOT, "include", "chessrl_hip.h")).read()
+    err_arg = int(re.search(r"\bCRL_ERR_ARG\s*=\s*(-?\d+)", text).group(1))
+    found = set(re.findall(r"\b(crl_[a-z_0-9]+)\s*\(\s*crl_ctx\s*\*\s*ctx\b", text))
+    assert found == set(_lib.SYMBOLS) - NO_CONTEXT
+    L = _lib.lib()
+    for name in sorted(found - {"crl_destroy", "crl_last_error"}):
+        fn = getattr(L, name)
+        args = [t() for t in fn.argtypes]            # every ctypes type constructs as zero / NULL
+        assert fn.argtypes[0] is ctypes.c_void_p and args[0].value is None, name
+        assert fn(*args) == err_arg, name
+
+
 def test_library_identity_and_refusal_of_a_stale_library(monkeypatch):
     """The library carries the sha256 of the sources it was built from and an ABI version; a library built
     from other sources that cannot be rebuilt is refused, and so is one of another ABI version (a ctypes
