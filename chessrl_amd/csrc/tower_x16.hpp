@@ -306,7 +306,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
 #pragma unroll
     for (int a = 0; a < PT; a++)
 #pragma unroll
-        for (int b = 0; b < CT; b++) res[a][b] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < CT; b++) res[a][b] = f32x4v{-0.f, -0.f, -0.f, -0.f};   // x + -0 == x bit for bit: the stem's add
 
     constexpr int HP = PT / 2;                          // position blocks per half sub-step
 
@@ -650,10 +650,16 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();                   // all reads of the activation buffer done
         __builtin_amdgcn_sched_barrier(0);
-        // three wave-uniform shapes (branches, not selects: every VALU instruction competes with the
-        // partner wave's MFMAs for issue slots): stem = linear (no BN, no activation,
-        // model.py:33-34); conv1 = ReLU, skip stream untouched; conv2 = + skip, ReLU, new skip
-        const int kind = conv == 0 ? 0 : ((conv & 1) ? 1 : 2);
+        // two wave-uniform shapes (branches, not selects: every VALU instruction competes with the
+        // partner wave's MFMAs for issue slots): conv1 = ReLU, skip stream untouched; conv2 = + skip, ReLU, new
+        // skip.  The stem (linear: no BN, no activation, model.py:33-34) runs as a conv2 whose skip stream is
+        // still -0 and whose floor is -inf: max(acc + -0, -inf) is acc bit for bit, the sign of a zero and fp32
+        // denormals (kept in this build) included; only a NaN accumulator would come out as -inf.
+        // Two shapes, not three, because of the registers: with a branch of its own for the stem hipcc joins the
+        // loop-carried res and the retired acc through chains of phi copies -- 192 v_mov_b32 per wave in a conv1
+        // hand-over, 64 in a conv2's, MFMA pipe idle.  tests/test_trunk_handover_cpu.py holds the ISA to none.
+        const bool conv1 = (conv & 1) != 0;
+        const float floor = conv == 0 ? -__builtin_inff() : 0.f;
         // channel blocks 2g, 2g+1 of a position block: 8 consecutive channels per lane, one 16-byte write
         auto store_pair = [&](int pt, int g, const half4 &lo, const half4 &hi) {
             *reinterpret_cast<__attribute__((address_space(3))) half8 *>(
@@ -676,31 +682,34 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             *reinterpret_cast<__attribute__((address_space(3))) half8 *>(dst + G::LO_OFF) = lo8;
         };
         if constexpr (SPLIT) {
+            // the branch encloses the loops (taken per element it leaves phi copies of res behind each one), and
+            // the two sides end in unequal asm comments: hipcc otherwise merges their last tile's stores into one
+            // tail and copies res into the tail's registers
+            auto write_layer = [&](auto value) {
 #pragma unroll
-            for (int g = 0; g < CT / 2; g++)
+                for (int g = 0; g < CT / 2; g++)
 #pragma unroll
-                for (int pt = 0; pt < PT; pt++) {
-                    f32x4v o[2];
+                    for (int pt = 0; pt < PT; pt++) store_split(pt, g, value(pt, 2 * g), value(pt, 2 * g + 1));
+            };
+            if (conv1) {                                // conv1: ReLU
+                write_layer([&](int pt, int ct) {
+                    f32x4v o;
 #pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const int ct = 2 * g + h;
-                        if (kind == 0) {                // stem: linear, starts the skip stream
-                            o[h] = acc[pt][ct];
-                            res[pt][ct] = o[h];
-                        } else if (kind == 1) {         // conv1: ReLU
+                    for (int j = 0; j < 4; j++) o[j] = fmaxf(acc[pt][ct][j], 0.f);
+                    return o;
+                });
+                asm volatile("; conv1 written");
+            } else {                                    // conv2: + skip, ReLU, new skip; stem: + -0, floor -inf
+                write_layer([&](int pt, int ct) {
+                    const f32x4v sum = acc[pt][ct] + res[pt][ct];
 #pragma unroll
-                            for (int j = 0; j < 4; j++) o[h][j] = fmaxf(acc[pt][ct][j], 0.f);
-                        } else {                        // conv2: + skip, ReLU, new skip
-                            const f32x4v sum = acc[pt][ct] + res[pt][ct];
-#pragma unroll
-                            for (int j = 0; j < 4; j++) o[h][j] = fmaxf(sum[j], 0.f);
-                            res[pt][ct] = o[h];
-                        }
-                    }
-                    store_split(pt, g, o[0], o[1]);
-                }
+                    for (int j = 0; j < 4; j++) res[pt][ct][j] = fmaxf(sum[j], floor);
+                    return res[pt][ct];
+                });
+                asm volatile("; conv2 written");
+            }
         } else
-        if (kind == 1) {                                // conv1 of a block: ReLU, skip stream untouched
+        if (conv1) {                                    // conv1 of a block: ReLU, skip stream untouched
 #pragma unroll
             for (int g = 0; g < CT / 2; g++)
 #pragma unroll
@@ -714,7 +723,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     }
                     store_pair(pt, g, o16[0], o16[1]);
                 }
-        } else if (kind == 2) {                         // conv2: + skip, ReLU, new skip
+        } else {                                        // conv2: + skip, ReLU, new skip; stem: + -0, floor -inf
 #pragma unroll
             for (int g = 0; g < CT / 2; g++)
 #pragma unroll
@@ -726,26 +735,11 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                         const f32x4v sum = acc[pt][ct] + res[pt][ct];      // packed fp32 adds
 #pragma unroll
                         for (int j = 0; j < 4; j++) {
-                            const float v = fmaxf(sum[j], 0.f);
+                            const float v = fmaxf(sum[j], floor);
                             res[pt][ct][j] = v;
                             o16[h][j] = (_Float16)v;
                         }
                     }
-                    store_pair(pt, g, o16[0], o16[1]);
-                }
-        } else {                                        // stem: linear
-#pragma unroll
-            for (int g = 0; g < CT / 2; g++)
-#pragma unroll
-                for (int pt = 0; pt < PT; pt++) {
-                    half4 o16[2];
-#pragma unroll
-                    for (int h = 0; h < 2; h++)
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            res[pt][2 * g + h][j] = acc[pt][2 * g + h][j];
-                            o16[h][j] = (_Float16)acc[pt][2 * g + h][j];
-                        }
                     store_pair(pt, g, o16[0], o16[1]);
                 }
         }
