@@ -27,6 +27,9 @@ def test_full_games_with_refill_match_oracle():
                          total_games=5, max_plies=2048)
     recs = sorted(run.run(), key=lambda r: r.game_id)
     assert [r.game_id for r in recs] == [0, 1, 2, 3, 4]
+    # whole games are what crosses the wrap of the 256-entry history ring with a search on top (the oracle's games are
+    # 487, 266, 365, 422 and 57 plies long): other seeds must keep doing so
+    assert max(len(r.moves) for r in recs) > 2 * 256 - 64
     for r in recs:
         g = oracle_game(net, r.game_id, seed, sims, True)
         h = g.get_history()
