@@ -63,7 +63,7 @@ SYMBOLS = [
     "crl_end_move_fetch", "crl_advance_fetch",
     "crl_reroot", "crl_reroot_fetch", "crl_search_begin_kept", "crl_copy_game_tree", "crl_fetch_tree",
     "crl_im2col3x3_f32", "crl_col2im3x3_f32", "crl_stamp", "crl_stamp_clock_khz",
-    "crl_rollout_games", "crl_rollout", "crl_opponent_moves",
+    "crl_rollout_games", "crl_rollout", "crl_opponent_moves", "crl_sim_reply_opponent",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
 ]
@@ -237,6 +237,7 @@ def lib():
     L.crl_rollout_games.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.crl_rollout.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.crl_opponent_moves.argtypes = [vp, vp, i32, ctypes.c_int64, vp, vp, vp, vp]
+    L.crl_sim_reply_opponent.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     L.crl_wave_config.argtypes = [vp, i32]
     L.crl_wave_begin.argtypes = [vp, i32]
@@ -557,6 +558,13 @@ class Context(object):
     def sim_reply(self, dev_policy_s1, dev_planes_s2):
         self._ck(self._L.crl_sim_reply(self._h, ctypes.c_void_p(dev_policy_s1),
                                        ctypes.c_void_p(dev_planes_s2)), "crl_sim_reply")
+
+    def sim_reply_opponent(self, dev_depths, node_limit, dev_planes_s2, dev_nodes, dev_cuts):
+        """``sim_reply`` with the built-in opponent's move as the reply: device pointers to int32 [count] depths, the
+        planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies."""
+        self._ck(self._L.crl_sim_reply_opponent(
+            self._h, ctypes.c_void_p(dev_depths), int(node_limit), ctypes.c_void_p(dev_planes_s2),
+            ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts)), "crl_sim_reply_opponent")
 
     def sim_backup(self, dev_policy_s2, dev_value_s2):
         self._ck(self._L.crl_sim_backup(self._h, ctypes.c_void_p(dev_policy_s2),

@@ -66,23 +66,38 @@ class Agent(Player):
         return policy
 
     # ---- moves -------------------------------------------------------------------------------
-    def best_move(self, game, real_game=False, max_iters=900, ai_move=True, verbose=False):
+    def best_move(self, game, real_game=False, max_iters=900, ai_move=True, verbose=False, reply=None):
+        """``reply``: None, or a ``chessrl_amd.opponent.MinimaxPlayer`` -- the search then runs against the built-in
+        opponent (the replies in the tree are its moves) with one worker per tree."""
         best_move = "00000"
         if real_game:
             policy = self.predict_policy(game)
             best_move = game.get_legal_moves()[int(np.argmax(policy))]
         elif game.get_result() is None:
             from . import mctree
-            tree = mctree.SelfPlayTree(game, threads=self.num_threads, virtual_loss=self.virtual_loss)
+            if reply is not None:
+                tree = mctree.SelfPlayTree(game, threads=self.num_threads, reply=reply)
+            else:
+                tree = mctree.SelfPlayTree(game, threads=self.num_threads, virtual_loss=self.virtual_loss)
             best_move = tree.search_move(self, max_iters=max_iters, verbose=verbose, ai_move=ai_move)
         return best_move
 
-    def engine_for(self, max_iters, simulate=None, threads=1):
+    def engine_for(self, max_iters, simulate=None, threads=1, reply=None):
         """One single-game LockstepEngine per (simulation budget, threads) (and leaf evaluator: ``simulate``, a
         ``simulation.Rollouts`` or None for the value head), reused across moves; its node pool holds
         max(max_iters + 1, tree_nodes) nodes -- max_iters + 1 with ``threads`` > 1, where every search starts from
-        a fresh tree."""
+        a fresh tree.  ``reply``: a ``MinimaxPlayer`` -- the engine that searches against the built-in opponent, one
+        per (max_iters, search depth, node limit); what it cannot be combined with is refused by the engine."""
         from .engine import LockstepEngine
+        if reply is not None:
+            from .opponent import MinimaxPlayer
+            if not isinstance(reply, MinimaxPlayer):
+                raise TypeError("reply must be None or a chessrl_amd.opponent.MinimaxPlayer")
+            key = ("reply", max_iters, reply.search_depth, reply.node_limit)
+            if threads > 1 or simulate is not None or key not in self._engines:      # (the first two: refused there)
+                self._engines[key] = LockstepEngine(self.model, n_games=1, max_sims=max_iters, simulate=simulate,
+                                                    threads=threads, numpy_promotion=self.numpy_promotion, reply=reply)
+            return self._engines[key]
         key = (max_iters, threads) if simulate is None else (max_iters, threads, simulate)
         if key not in self._engines:
             if threads > 1:

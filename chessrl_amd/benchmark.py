@@ -6,7 +6,13 @@ built-in depth-d alpha-beta player (csrc/opponent.hpp): NOT Stockfish, no Elo --
 built-in depth-d opponent".  All games sit in ONE device context and advance together: on the agent's plies one
 tower call for the slots where the agent is to move and ``greedy_moves(policy, mask, push=True)``
 (agentdistributed.py:56-58), on the opponent's plies one ``opponent_moves(depths, push=True)`` launch.
-MCTS on the agent's side is out of scope: the lockstep search engine advances two plies per search.
+
+``benchmark(..., sims=N)`` (``--sims N``) measures the SEARCHING agent: one ``LockstepEngine(reply=MinimaxPlayer)``
+whose trees hold the built-in opponent's replies (csrc/opponent.hpp ``k_reply_opponent``).  The engine's two-ply step
+fits exactly: the reply stored for our move is the move the opponent plays from that board, so ``advance`` pushes (our
+move, the opponent's real reply) and every game is a real game against the opponent.  Games in which the agent is
+black first get the opponent's opening move (gamestockfish.py:31-33); then per move ``search(N)``, ``root_children``,
+``choose_children(noise=False)``, ``advance``.  ``sims=0`` is the greedy benchmark above.
 """
 import argparse
 import os
@@ -37,28 +43,13 @@ def _load_model(model_dir):
     return ChessModel(weights=path if os.path.exists(path) else None)
 
 
-def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=None, max_plies=512, model=None):
-    """Plays ``games`` games against the built-in depth-``opponent_depth`` opponent and returns
-    ``dict(played=, won=, drawn=, games=)``: the reference's tallies and the per-game UCI move lists.  ``workers`` is
-    accepted and ignored (the games run in lockstep on one GPU); ``model`` takes a ready evaluator (planes ->
-    (policy, value) on the GPU) instead of the newest weights of ``model_dir``.  A game still running after
-    ``max_plies`` plies counts as played, neither won nor drawn."""
+def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white):
+    """(moves, plies, results) of the games with ``Agent.best_move(real_game=True)`` on the agent's plies."""
     import torch
-    if not 1 <= int(opponent_depth) <= _lib.OPP_MAX_DEPTH:
-        raise ValueError("opponent_depth must lie in [1, %d]" % _lib.OPP_MAX_DEPTH)
-    games, max_plies = int(games), int(max_plies)
-    colors = game_colors(games, seed)
-    if games < 1:
-        return dict(tally([], []), games=[])
-    if model is None:
-        model = _load_model(model_dir)
-    dev = getattr(model, "device", None) or torch.device("cuda", 0)
-    dev = torch.device(dev)
     ctx = _lib.Context(games, 1, max_plies=max(max_plies, 2), device=dev.index or 0)
     try:
         planes = torch.zeros((games, 8, 8, _lib.PLANES), dtype=torch.float16, device=dev)
         ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        agent_white = np.array(colors, dtype=bool)
         results = ctx.results()
         for ply in range(max_plies):
             running = results == _lib.RESULT_NONE
@@ -74,15 +65,73 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
             if opp_turn.any():
                 ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True)
             results = ctx.results()
-        moves, plies, results = ctx.records()
+        return ctx.records()
     finally:
         ctx.close()
+
+
+def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims):
+    """(moves, plies, results) of the games with ``sims`` simulations per move against the opponent's replies.  A game
+    is searched while it runs and has fewer than ``max_plies`` plies; a move adds two plies (one if it ends the game),
+    so a game may end one ply past ``max_plies``."""
+    from .engine import LockstepEngine, choose_children
+    from .opponent import MinimaxPlayer
+    eng = LockstepEngine(model, games, sims, device=dev.index or 0, max_plies=max_plies + 2,
+                         reply=MinimaxPlayer(False, search_depth=opponent_depth))
+    try:
+        ctx = eng.ctx
+        if not agent_white.all():                            # gamestockfish.py:31-33: the opponent opens as white
+            ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True)
+        while True:
+            _, plies, results = ctx.records(with_moves=False)
+            live = (results == _lib.RESULT_NONE) & (plies < max_plies)
+            if not live.any():
+                break
+            eng.search(sims)
+            rc = eng.root_children()
+            chosen = choose_children(rc["visits"], rc["nchild"], rc["root_visits"], plies, noise=False)
+            chosen[~live] = -1
+            eng.advance(chosen)
+        return ctx.records()
+    finally:
+        eng.close()
+
+
+def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=None, max_plies=512, model=None,
+              sims=0):
+    """Plays ``games`` games against the built-in depth-``opponent_depth`` opponent and returns
+    ``dict(played=, won=, drawn=, games=)``: the reference's tallies and the per-game UCI move lists.  ``workers`` is
+    accepted and ignored (the games run in lockstep on one GPU); ``model`` takes a ready evaluator (planes ->
+    (policy, value) on the GPU) instead of the newest weights of ``model_dir``.  A game still running after
+    ``max_plies`` plies counts as played, neither won nor drawn.  ``sims`` > 0: the agent's move is the choice of an
+    MCTS of ``sims`` simulations against the opponent's replies instead of its greedy move (module docstring)."""
+    if not 1 <= int(opponent_depth) <= _lib.OPP_MAX_DEPTH:
+        raise ValueError("opponent_depth must lie in [1, %d]" % _lib.OPP_MAX_DEPTH)
+    sims = int(sims)
+    if sims < 0:
+        raise ValueError("sims must be 0 (the greedy agent) or the number of simulations per move")
+    import torch
+    games, max_plies = int(games), int(max_plies)
+    colors = game_colors(games, seed)
+    if games < 1:
+        return dict(tally([], []), games=[])
+    if model is None:
+        model = _load_model(model_dir)
+    dev = getattr(model, "device", None) or torch.device("cuda", 0)
+    dev = torch.device(dev)
+    agent_white = np.array(colors, dtype=bool)
+    if sims > 0:
+        moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims)
+    else:
+        moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white)
     res = [None if r == _lib.RESULT_NONE else int(r) for r in results]
     out = tally(colors, res)
     out["games"] = [[move_to_uci(m) for m in moves[i, :plies[i]]] for i in range(games)]
     if log:
         print("##################### SUMMARY ###################")
         print("Against the built-in depth-%d opponent (not Stockfish, no Elo)" % opponent_depth)
+        if sims > 0:
+            print("agent: MCTS, %d simulations per move" % sims)
         print("Games played: %d" % out["played"])
         print("Games won: %d" % out["won"])
         print("Games drawn: %d" % out["drawn"])
@@ -98,8 +147,11 @@ def main(argv=None):
     p.add_argument("--depth", type=int, default=2, help="search depth of the built-in opponent (1-5)")
     p.add_argument("--seed", type=int, default=None, help="seed of the colour draw")
     p.add_argument("--max-plies", type=int, default=512)
+    p.add_argument("--sims", type=int, default=0,
+                   help="simulations per move of the agent's search against the opponent's replies (0: the greedy agent)")
     a = p.parse_args(argv)
-    benchmark(a.model_dir, games=a.games, opponent_depth=a.depth, seed=a.seed, max_plies=a.max_plies, log=True)
+    benchmark(a.model_dir, games=a.games, opponent_depth=a.depth, seed=a.seed, max_plies=a.max_plies, log=True,
+              sims=a.sims)
 
 
 if __name__ == "__main__":

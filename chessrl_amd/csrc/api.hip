@@ -778,6 +778,18 @@ int crl_opponent_moves(crl_ctx *ctx, const int32_t *depths, int push, int64_t no
     return check_dev_error(ctx);
 }
 
+// the reply of a search step from the built-in opponent (mctree.py:244-246 with gamestockfish.py:27-41 as the mover):
+// device pointers only, so the call captures into the step's hipGraph like crl_sim_reply
+int crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t node_limit, void *dev_planes_s2,
+                           uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32)
+{
+    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && node_limit >= 1);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "node accumulators");
+    LAUNCH(ctx, k_reply_opponent, ctx->d, dev_depths_i32, (long long)node_limit, dev_planes_s2,
+           (unsigned long long *)dev_nodes_u64, dev_cuts_u32);
+    return CRL_OK;
+}
+
 // ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------------------------
 int crl_wave_config(crl_ctx *ctx, int threads)
 {

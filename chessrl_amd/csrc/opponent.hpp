@@ -149,21 +149,14 @@ __device__ inline void opp_partition(const Board &b, u16 *mv, int n, int lane)
     __syncthreads();
 }
 
-// window-relative rows: depths / moves / scores / nodes_out / flags [count]
-__global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *depths, int push, long long limit,
-                                                       u16 *moves, int32_t *scores, long long *nodes_out,
-                                                       uint8_t *flags)
+// The search of the header comment, stated once for both kernels: from `root` to depth D (1 .. OPP_MAX_DEPTH, checked by
+// the caller) under the node limit, in the frames f[0 .. D].  mv: the move (NO_MOVE only for a root without a legal
+// move or with a result, which no caller hands in); score, nodes; done = false is the cut.  Every value is
+// wave-uniform.  The frames are dead on return, but not yet fenced: a barrier comes before their bytes are reused.
+struct OppResult { u32 mv; int score; long long nodes; bool done; };
+
+__device__ inline OppResult opp_search(const Board &root, int D, long long limit, OppFrame *f, int lane)
 {
-    __shared__ OppLds s;
-    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
-    int D = uni(depths[r]);
-    if (D > OPP_MAX_DEPTH) D = OPP_MAX_DEPTH;              // (the host refuses such a depth before the launch)
-    const bool skipped = D > 0 && uni(d.game[g].game_result) != RESULT_NONE;
-    if (D <= 0 || skipped) {
-        if (lane == 0) { moves[r] = NO_MOVE; scores[r] = 0; nodes_out[r] = 0; flags[r] = skipped ? OPP_SKIPPED : 0; }
-        return;
-    }
-    const Board root = uni_board(d.cur[g]);
     Board b = root;
     int k = 0, a = -OPP_INF, be = OPP_INF, v = 0, root_best = -OPP_INF;
     u32 best_mv = NO_MOVE, first_mv = NO_MOVE;
@@ -171,7 +164,7 @@ __global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *dep
     long long nodes = 0;
     while (nodes < limit) {
         // ---- enter the node `b` at ply k, window (a, be)
-        OppFrame &F = s.f[k];
+        OppFrame &F = f[k];
         const bool horizon = k == D;
         MoveGenInfo mi = wave_movegen(b, lane, horizon ? nullptr : F.mv);
         nodes++;
@@ -192,7 +185,7 @@ __global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *dep
         while (have_v) {
             if (k == 0) { done = true; break; }
             k--;
-            OppFrame &P = s.f[k];
+            OppFrame &P = f[k];
             const int sc = -v, pn = uni(P.n), pb = uni(P.beta);
             int cur = uni(P.cur), best = uni(P.best), al = uni(P.alpha);
             if (sc > best) {
@@ -209,24 +202,74 @@ __global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *dep
         }
         if (done) break;
         // ---- descend: the next move of frame k  (k < D: a frame with moves to search is above the horizon)
-        OppFrame &P = s.f[k];
+        OppFrame &P = f[k];
         const u32 mv = (u32)uni((int)P.mv[uni(P.cur)]);
         b = apply_move(uni_board(P.b), mv);
         a = -uni(P.beta);
         be = -uni(P.alpha);
         k++;
     }
-    const u32 mv = done || best_mv != NO_MOVE ? best_mv : first_mv;
+    OppResult o;
+    o.mv = done || best_mv != NO_MOVE ? best_mv : first_mv;
+    o.score = done ? v : root_best;
+    o.nodes = nodes;
+    o.done = done;
+    return o;
+}
+
+// window-relative rows: depths / moves / scores / nodes_out / flags [count]
+__global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *depths, int push, long long limit,
+                                                       u16 *moves, int32_t *scores, long long *nodes_out,
+                                                       uint8_t *flags)
+{
+    __shared__ OppLds s;
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    int D = uni(depths[r]);
+    if (D > OPP_MAX_DEPTH) D = OPP_MAX_DEPTH;              // (the host refuses such a depth before the launch)
+    const bool skipped = D > 0 && uni(d.game[g].game_result) != RESULT_NONE;
+    if (D <= 0 || skipped) {
+        if (lane == 0) { moves[r] = NO_MOVE; scores[r] = 0; nodes_out[r] = 0; flags[r] = skipped ? OPP_SKIPPED : 0; }
+        return;
+    }
+    const Board root = uni_board(d.cur[g]);
+    const OppResult o = opp_search(root, D, limit, s.f, lane);
     if (lane == 0) {
-        moves[r] = (u16)mv;
-        scores[r] = done ? v : root_best;
-        nodes_out[r] = nodes;
-        flags[r] = done ? 0 : OPP_CUT;
+        moves[r] = (u16)o.mv;
+        scores[r] = o.score;
+        nodes_out[r] = o.nodes;
+        flags[r] = o.done ? 0 : OPP_CUT;
     }
-    if (push && mv != NO_MOVE) {
+    if (push && o.mv != NO_MOVE) {
         __syncthreads();                                   // the frames are dead: s.w takes their bytes
-        game_push(d, g, root, mv, lane, s.w);
+        game_push(d, g, root, o.mv, lane, s.w);
     }
+}
+
+// expand, the opponent's half (mctree.py:244-246) with the built-in opponent as the mover (gamestockfish.py:27-41):
+// the reply stored for S1 is the move k_opponent_moves plays from S1 -- it reads the board alone, so the tree holds the
+// real opponent's reply.  Rows as k_reply: one whose pending leaf is not LEAF_NEW_REPLY only clears lab_n2.  The root
+// order of the search is wave_movegen's (s1_moves is not read).  A cut reply is a move like any other.  nodes_acc /
+// cuts_acc [count], window-relative: this wave owns its row, so lane 0 adds with a plain load and store.
+__global__ __launch_bounds__(64) void k_reply_opponent(Dev d, const int32_t *depths, long long limit, void *planes2,
+                                                       unsigned long long *nodes_acc, uint32_t *cuts_acc)
+{
+    __shared__ OppLds s;
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    if (lane == 0) d.lab_n2[r] = 0;                     // no policy(S2) wanted unless a new node gets priors
+    if (d.game[g].root_dead || d.game[g].leaf_kind != LEAF_NEW_REPLY) return;
+    const int D = uni(depths[r]);
+    if (D < 1 || D > OPP_MAX_DEPTH) { dev_error(d, DERR_STATE); return; }   // (the host never sends one)
+    const int c = uni(d.game[g].leaf_node);
+    const Board s1 = uni_board(d.node[(size_t)g * d.N + c].s1);
+    const OppResult o = opp_search(s1, D, limit, s.f, lane);
+    if (o.mv == NO_MOVE) { dev_error(d, DERR_STATE); return; }              // S1 is running: it has a legal move
+    if (lane == 0) {
+        nodes_acc[r] += (unsigned long long)o.nodes;
+        if (!o.done) cuts_acc[r] += 1u;
+    }
+    __syncthreads();                                       // the frames are dead: s.w takes their bytes
+    reply_tail(d, g, r, lane, s.w, c, uni(d.game[g].path_len), uni(d.game[g].ply), s1, o.mv,
+               uni(d.game[g].edge_top), d.policy_fmt, &d.game[g].leaf_kind, planes2);
 }
 
 }  // namespace crl

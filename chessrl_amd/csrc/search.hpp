@@ -722,18 +722,15 @@ __device__ inline NewLeaf expand_child(const Dev &d, int g, int row, int lane, W
     return lf;
 }
 
-// expand, the opponent's half (mctree.py:244-250) and Node() of the new state (mctree.py:28-37): node c, reached by a
-// path of `level` edges, whose S1 has the n1 legal moves mv1, gets the reply agent.best_move(S1, real_game=True) picks
-// from row `row` of pol1, its S2, an edge run from slot edge0 on and the planes of S2 in row `row` of planes2.
+// expand, the opponent's half (mctree.py:244-250) and Node() of the new state (mctree.py:28-37), in two pieces: the
+// choice of the reply (reply_child below: the net's greedy move; k_reply_opponent of opponent.hpp: the built-in
+// opponent's) and everything after it, reply_tail: node c, reached by a path of `level` edges, whose state after our
+// move is s1, gets `reply`, its S2, an edge run from slot edge0 on and the planes of S2 in row `row` of planes2.
 // Returns the length of the run, -1 when the edge pool is exhausted (nothing was written).
-__device__ inline int reply_child(const Dev &d, int g, int row, int lane, WaveLds &s, int c, int level, int ply,
-                                  const u16 *mv1, int n1, int edge0, const float *pol1, int fmt, const float2 *stats,
-                                  uint8_t *kind, void *planes2)
+__device__ inline int reply_tail(const Dev &d, int g, int row, int lane, WaveLds &s, int c, int level, int ply,
+                                 const Board &s1, u32 reply, int edge0, int fmt, uint8_t *kind, void *planes2)
 {
     const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
-    Board s1 = d.node[nb + c].s1;
-    const int bi = argmax_policy(d, row, mv1, n1, pol1, lane, fmt, stats);   // legal[argmax(policy masked to legal)]
-    const u32 reply = mv1[bi];
     Board s2 = apply_move(s1, reply);
     PosEval e = eval_position(d, g, s2, 2 * level, ply, ply, lane, s);
     if (edge0 + e.n > d.ECAP) { dev_error(d, DERR_EDGE_POOL); return -1; }
@@ -753,6 +750,16 @@ __device__ inline int reply_child(const Dev &d, int g, int row, int lane, WaveLd
     __syncthreads();
     encode_position(d, g, e.b, 2 * level, ply, ply, lane, s, planes2, row);
     return e.n;
+}
+
+// the net's reply: agent.best_move(S1, real_game=True) picks it from row `row` of pol1 among the n1 legal moves mv1
+__device__ inline int reply_child(const Dev &d, int g, int row, int lane, WaveLds &s, int c, int level, int ply,
+                                  const u16 *mv1, int n1, int edge0, const float *pol1, int fmt, const float2 *stats,
+                                  uint8_t *kind, void *planes2)
+{
+    Board s1 = d.node[(size_t)g * d.N + c].s1;
+    const int bi = argmax_policy(d, row, mv1, n1, pol1, lane, fmt, stats);   // legal[argmax(policy masked to legal)]
+    return reply_tail(d, g, row, lane, s, c, level, ply, s1, mv1[bi], edge0, fmt, kind, planes2);
 }
 
 __global__ __launch_bounds__(64, 4) void k_select_expand(Dev d, const float *pol2, const float *val2,

@@ -10,6 +10,16 @@ One *step* = one ``explore_tree`` for every game:
     crl_sim_reply           greedy reply, S2, Node(S2), encode S2
     evaluator(planes S2)    tower forward #2  -> policy(S2), value(S2)
 
+``LockstepEngine(..., reply=MinimaxPlayer(...))`` searches against the built-in opponent (csrc/opponent.hpp) instead:
+the reply stored in a node is that opponent's move from S1 -- a function of the board alone, so it is the move the
+real opponent plays there and ``advance`` plays a real game against it.  Such a step is three phases,
+
+    crl_sim_select_expand   as above
+    crl_sim_reply_opponent  alpha-beta from S1, S2, Node(S2), encode S2
+    evaluator(planes S2)    the only tower forward
+
+and S1 is never evaluated.
+
 All four are enqueued on one HIP stream with no host synchronisation and are
 captured once into a hipGraph (torch.cuda.CUDAGraph) that is replayed S times
 per move.  Tensors never leave HBM: the encoder kernels write the tower's input
@@ -215,17 +225,48 @@ def summarise_stamps(stamps):
                           "min_ms": min(v), "max_ms": max(v)} for k, v in trunk.items()}}
 
 
+# what LockstepEngine(reply=MinimaxPlayer) does not cover, each refused with a ValueError that names it
+REPLY_REFUSED = {
+    "threads": "reply= cannot be combined with threads > 1: the opponent's reply kernel serves one pending leaf per game",
+    "simulate": "reply= cannot be combined with rollouts (simulate=Rollouts): the three-phase step has no playout phase",
+    "max_nodes": "reply= cannot be combined with max_nodes (tree reuse): a search against the opponent starts from a "
+                 "fresh tree",
+    "reroot": "reply= cannot be combined with reroot: a search against the opponent starts from a fresh tree",
+    "keep_root": "reply= cannot be combined with keep_root=True: a search against the opponent starts from a fresh tree",
+    "set_stamps": "reply= cannot be combined with set_stamps: the stamped step is the four-phase step",
+    "node": "reply= cannot continue a Node: a search against the opponent starts from a fresh tree (construct the "
+            "tree from the Game)",
+}
+
+
 class LockstepEngine(object):
     """G games x one search tree each on one GPU.
 
     evaluator(planes[G,8,8,128] fp16 cuda) -> (policy[G,1968] f32, value[G] f32) cuda tensors; an
     evaluator with ``accepts_bitplanes`` is given int64 [G,128] plane bitboards instead.
+
+    ``reply``: None -- the reply stored in a node is the net's greedy move -- or a ``chessrl_amd.opponent.MinimaxPlayer``:
+    the built-in opponent's move, searched with the player's ``search_depth`` and ``node_limit`` (its colour is
+    ignored: the side to move after our move replies).
     """
 
     def __init__(self, evaluator, n_games, max_sims, device=0, max_plies=4096,
                  numpy_promotion="auto", use_graph=True, bitplanes=None, legal_priors=None, raw_priors=None,
-                 steps_per_graph=None, max_nodes=None, simulate=None, threads=1):
+                 steps_per_graph=None, max_nodes=None, simulate=None, threads=1, reply=None):
         numpy_promotion = resolve_numpy_promotion(numpy_promotion)
+        # reply=MinimaxPlayer: the replies in the tree are the built-in opponent's.  What that step does not cover is
+        # refused by name before anything touches the device.
+        if reply is not None:
+            from .opponent import MinimaxPlayer
+            if not isinstance(reply, MinimaxPlayer):
+                raise TypeError("reply must be None or a chessrl_amd.opponent.MinimaxPlayer")
+            if int(threads) > 1:
+                raise ValueError(REPLY_REFUSED["threads"])
+            if simulate is not None:
+                raise ValueError(REPLY_REFUSED["simulate"])
+            if max_nodes is not None and max_nodes != max_sims + 1:
+                raise ValueError(REPLY_REFUSED["max_nodes"])
+        self.reply = reply
         if simulate is not None and not isinstance(simulate, Rollouts):
             raise TypeError("simulate must be None or a chessrl_amd.simulation.Rollouts")
         # threads > 1: virtual-loss waves.  What the wave kernels do not cover is refused by name, never ignored.
@@ -324,6 +365,15 @@ class LockstepEngine(object):
         # one step: (the stamp in front of a phase when a StampRing is attached, the phase method by name)
         self._plan = [(STAMP_STEP, "phase_select_expand"), (STAMP_SELECTED, "phase_tower_s1"),
                       (STAMP_S1_DONE, "phase_reply"), (STAMP_REPLIED, "phase_tower_s2")]
+        if reply is not None:
+            # no tower call on S1: the opponent's search reads the board.  The engine owns the per-slot depths and
+            # the two accumulators the captured step reads and writes.
+            self._plan = [(STAMP_STEP, "phase_select_expand"), (STAMP_S1_DONE, "phase_reply_opponent"),
+                          (STAMP_REPLIED, "phase_tower_s2")]
+            rows["reply_depths"] = torch.full((G,), reply.search_depth, dtype=torch.int32, device=self.dev)
+            rows["reply_nodes"] = torch.zeros((G,), dtype=torch.int64, device=self.dev)
+            rows["reply_cuts"] = torch.zeros((G,), dtype=torch.int32, device=self.dev)
+            self._take_rows(G)
         if simulate is not None:
             self._plan.append((STAMP_ROLLOUT, "phase_rollout"))
         self.use_graph = use_graph
@@ -400,6 +450,11 @@ class LockstepEngine(object):
     def phase_reply(self):
         self._reply(self.pri_s1.data_ptr(), self.planes_s2.data_ptr())
 
+    def phase_reply_opponent(self):
+        """Only with ``reply``: the built-in opponent's move from S1 becomes the node's reply."""
+        self.ctx.sim_reply_opponent(self.reply_depths.data_ptr(), self.reply.node_limit, self.planes_s2.data_ptr(),
+                                    self.reply_nodes.data_ptr(), self.reply_cuts.data_ptr())
+
     def phase_tower_s2(self):
         if self.legal_priors:
             self.evaluator.forward_legal_into(self.planes_s2, self._lab_s2[0], self._lab_s2[1], self.pri_s2, self.val_s2,
@@ -425,6 +480,25 @@ class LockstepEngine(object):
             raise ValueError("set_stream_keys: one key per slot (%d)" % self.stream_keys.numel())
         self.stream_keys.copy_(keys.to(self.dev).view(torch.int64).reshape(-1))
 
+    def set_reply_depths(self, depths):
+        """The opponent's search depth of every slot (default: the player's ``search_depth``), copied into the tensor
+        the captured step reads: n_games values in 1 .. 5."""
+        if self.reply is None:
+            raise ValueError("set_reply_depths: the engine was created without reply")
+        d = np.ascontiguousarray(depths, dtype=np.int32).reshape(-1)
+        if d.size != self.reply_depths.numel():
+            raise ValueError("set_reply_depths: one depth per slot (%d)" % self.reply_depths.numel())
+        if d.size and (d.min() < 1 or d.max() > _lib.OPP_MAX_DEPTH):
+            raise ValueError("set_reply_depths: depths must lie in [1, %d]" % _lib.OPP_MAX_DEPTH)
+        self.reply_depths.copy_(torch.from_numpy(d).to(self.dev))
+
+    def reply_stats(self):
+        """(nodes int64 [G], cuts int32 [G]) as numpy: what the opponent's replies of the current search cost per
+        slot -- nodes searched and replies ended by the node limit (synchronises)."""
+        if self.reply is None:
+            raise ValueError("reply_stats: the engine was created without reply")
+        return self.reply_nodes.cpu().numpy(), self.reply_cuts.cpu().numpy()
+
     def _step_body(self):
         # with a StampRing attached this is the measurement build of the same step (bench.py): a one-thread stamp
         # kernel in front of every phase, captured into the graph with them; the evaluator stamps its own trunk
@@ -442,6 +516,8 @@ class LockstepEngine(object):
         with: another ring drops them."""
         if ring is not None and self.threads > 1:
             raise ValueError("threads > 1 cannot be combined with set_stamps: the stamped step is the one-leaf step")
+        if ring is not None and self.reply is not None:
+            raise ValueError(REPLY_REFUSED["set_stamps"])
         if ring is not None and ring is not self._stamped_ring:
             self._graphs = {k: g for k, g in self._graphs.items() if not k[1]}
             self._stamped_ring = ring
@@ -547,6 +623,8 @@ class LockstepEngine(object):
     def search_begin(self, keep_root=False):
         """Tree.__init__ for every slot + the root's policy (priors of its children).  ``keep_root``: slots whose
         root ``reroot`` kept go on with that tree (Tree(Node), mctree.py:98-111); the others start a fresh one."""
+        if keep_root and self.reply is not None:
+            raise ValueError(REPLY_REFUSED["keep_root"])
         self._bind_stream()
         if keep_root and self.threads > 1:
             raise ValueError("threads > 1 cannot be combined with keep_root=True: a wave search starts from a fresh tree")
@@ -556,6 +634,9 @@ class LockstepEngine(object):
             self.ctx.search_begin(self.planes_s2.data_ptr())
         self._eval_into(self._root_rows(self.planes_s2), self._root_rows(self.pol_s2), self._root_rows(self.val_s2))
         self.ctx.search_root_priors(self.pol_s2.data_ptr())
+        if self.reply is not None:
+            self.reply_nodes.zero_()
+            self.reply_cuts.zero_()
 
     def search(self, n_sims, keep_root=False):
         """search_begin + n_sims lockstep simulations + the last backprop.  A kept tree that would not fit n_sims
@@ -604,6 +685,8 @@ class LockstepEngine(object):
     def reroot(self, chosen, next_sims):
         """``advance`` that keeps the chosen child's subtree in every slot where kept nodes + ``next_sims`` fit
         ``max_nodes``; ``search(next_sims, keep_root=True)`` then continues on it."""
+        if self.reply is not None:
+            raise ValueError(REPLY_REFUSED["reroot"])
         if self.threads > 1:
             raise ValueError("threads > 1 cannot be combined with reroot: a wave search starts from a fresh tree")
         if next_sims > self.max_sims:

@@ -28,6 +28,11 @@ the search runs T workers per tree in the wave schedule (csrc/search_wave.hpp) -
 legal schedules of the reference's virtual-loss thread pool (mctree.py:12,173-176,226-227,289-293).  It is opt-in
 because ``Agent`` passes ``threads=6`` today and honouring it would change what every caller gets.  A wave search
 starts from a fresh tree: continuing a ``Node`` with ``virtual_loss=True`` raises.
+
+``SelfPlayTree(game, reply=MinimaxPlayer(...))`` searches against the built-in opponent (``chessrl_amd/opponent.py``):
+the reply stored in every new node, and shown as ``Node.reply``, is that opponent's move from the position after our
+move instead of the net's greedy move.  One worker, the value head, a fresh tree: combining it with ``virtual_loss``
+waves or rollouts, or continuing a ``Node`` of such a tree, raises ``ValueError``.
 """
 import numpy as np
 
@@ -101,6 +106,9 @@ class Tree(object):
         if eng is None or getattr(eng, "_tree_owner", None) is not src:
             raise RuntimeError("the device tree of this Node is gone: its engine has searched another tree since "
                                "(a Node can be continued only while its tree is the last one searched there)")
+        if getattr(eng, "reply", None) is not None:
+            from .engine import REPLY_REFUSED
+            raise ValueError(REPLY_REFUSED["node"])
         if getattr(eng, "threads", 1) > 1:
             raise ValueError("this Node comes from a search with virtual_loss=True and threads > 1: a wave engine starts "
                              "every search from a fresh tree and cannot continue a Node (construct the tree from the Game)")
@@ -122,10 +130,26 @@ class Tree(object):
 
 class SelfPlayTree(Tree):
 
-    def __init__(self, root, threads=6, simulate=None, virtual_loss=False):
+    def __init__(self, root, threads=6, simulate=None, virtual_loss=False, reply=None):
         """``simulate``: None -- leaves are valued by ``agent.predict_outcome`` (the value head) -- or a
         ``chessrl_amd.simulation.Rollouts``: by random playouts, the alternative mctree.py:272-274 names.
-        ``virtual_loss``: the search uses ``threads`` workers per tree (the wave schedule)."""
+        ``virtual_loss``: the search uses ``threads`` workers per tree (the wave schedule).
+        ``reply``: None -- the opponent's reply in a node is the net's greedy move -- or a
+        ``chessrl_amd.opponent.MinimaxPlayer``: the built-in opponent's move ("the simulations against stockfish");
+        ``Node.reply`` is then that move.  Such a search uses one worker, values leaves by the value head and starts
+        from a fresh tree: the combinations are refused as ``LockstepEngine(reply=...)`` refuses them."""
+        if reply is not None:
+            from .engine import REPLY_REFUSED
+            from .opponent import MinimaxPlayer
+            if not isinstance(reply, MinimaxPlayer):
+                raise TypeError("reply must be None or a chessrl_amd.opponent.MinimaxPlayer")
+            if virtual_loss and int(threads) > 1:
+                raise ValueError(REPLY_REFUSED["threads"])
+            if simulate is not None:
+                raise ValueError(REPLY_REFUSED["simulate"])
+            if isinstance(root, Node) and root._tree is not None:
+                raise ValueError(REPLY_REFUSED["node"])
+        self.reply = reply
         if virtual_loss:
             if not 1 <= int(threads) <= _lib.WAVE_MAX_THREADS:
                 raise ValueError("threads must lie in [1, %d]" % _lib.WAVE_MAX_THREADS)
@@ -147,7 +171,9 @@ class SelfPlayTree(Tree):
             eng = self._continue_on_device(max_iters)
             eng.search(max_iters, keep_root=True)
         else:
-            if self.virtual_loss and self.num_threads > 1:
+            if self.reply is not None:
+                eng = agent.engine_for(max_iters, reply=self.reply)
+            elif self.virtual_loss and self.num_threads > 1:
                 eng = agent.engine_for(max_iters, threads=int(self.num_threads))
             else:
                 eng = agent.engine_for(max_iters, self.simulate) if self.simulate is not None else agent.engine_for(max_iters)

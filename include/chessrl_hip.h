@@ -287,6 +287,19 @@ int  crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, 
 #define CRL_OPP_SKIPPED 2
 int  crl_opponent_moves(crl_ctx *ctx, const int32_t *depths /*G*/, int push, int64_t node_limit,
                         uint16_t *moves /*G*/, int32_t *scores /*G*/, int64_t *nodes /*G*/, uint8_t *flags /*G*/);
+/* crl_sim_reply with the built-in opponent as the mover: the second half of expand (mctree.py:244-246), where the
+ * reply to S1 comes from a game that answers every move of ours with its engine (gamestockfish.py:27-41) instead of
+ * from policy(S1).  The search above runs from the pending node's S1 to depth dev_depths_i32[row] under node_limit;
+ * its move -- a function of the board alone, hence the move crl_opponent_moves plays from S1 -- is stored as the
+ * node's reply, then S2, Node(S2) and the planes of S2 exactly as by crl_sim_reply (labels of S2 in the legal-label
+ * policy formats included).  A cut reply (node limit) is still a move and is stored like any other.  No tower call
+ * on S1 is needed in such a step.  All pointers are DEVICE pointers, rows window-relative, so the call captures
+ * into a hipGraph: dev_depths_i32 int32 [count]; dev_nodes_u64 / dev_cuts_u32 [count] accumulate the nodes searched
+ * and the number of cut replies per row (the caller clears them).  Rows without a pending reply read no depth.
+ * CRL_ERR_ARG: a NULL pointer, node_limit < 1.  A depth outside 1 .. CRL_OPP_MAX_DEPTH on a row that needs a reply
+ * is a device error (reported as CRL_ERR_STATE by the next synchronising call). */
+int  crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t node_limit, void *dev_planes_s2,
+                            uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32);
 
 /* ---- threads > 1: virtual-loss waves of simulations per game (csrc/search_wave.hpp) --------------------------
  * The reference runs `threads` explore_tree workers on one tree, kept apart by a virtual loss (mctree.py:12,173-176,
