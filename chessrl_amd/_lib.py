@@ -40,6 +40,7 @@ NO_MOVE = 0xFFFF
 RESULT_NONE = 2
 ROLLOUT_GAMES, ROLLOUT_LEAVES, ROLLOUT_SKIPPED = 0, 1, 0xFFFF
 OPP_MAX_DEPTH, OPP_CUT, OPP_SKIPPED = 5, 1, 2     # include/chessrl_hip.h: CRL_OPP_*
+OPP_MAX_QUIESCENCE = 6    # include/chessrl_hip.h: CRL_OPP_MAX_QUIESCENCE
 OPP_NODE_LIMIT = 200000   # default node limit per slot of Context.opponent_moves (a first choice)
 FLAG_NUMPY_LEGACY = 1
 WAVE_MAX_THREADS = 64     # include/chessrl_hip.h: CRL_WAVE_MAX_THREADS
@@ -64,6 +65,7 @@ SYMBOLS = [
     "crl_reroot", "crl_reroot_fetch", "crl_search_begin_kept", "crl_copy_game_tree", "crl_fetch_tree",
     "crl_im2col3x3_f32", "crl_col2im3x3_f32", "crl_stamp", "crl_stamp_clock_khz",
     "crl_rollout_games", "crl_rollout", "crl_opponent_moves", "crl_sim_reply_opponent",
+    "crl_opponent_moves_q", "crl_sim_reply_opponent_q",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
 ]
@@ -238,6 +240,8 @@ def lib():
     L.crl_rollout.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.crl_opponent_moves.argtypes = [vp, vp, i32, ctypes.c_int64, vp, vp, vp, vp]
     L.crl_sim_reply_opponent.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
+    L.crl_opponent_moves_q.argtypes = [vp, vp, i32, i32, ctypes.c_int64, vp, vp, vp, vp]
+    L.crl_sim_reply_opponent_q.argtypes = [vp, vp, i32, ctypes.c_int64, vp, vp, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     L.crl_wave_config.argtypes = [vp, i32]
     L.crl_wave_begin.argtypes = [vp, i32]
@@ -559,12 +563,13 @@ class Context(object):
         self._ck(self._L.crl_sim_reply(self._h, ctypes.c_void_p(dev_policy_s1),
                                        ctypes.c_void_p(dev_planes_s2)), "crl_sim_reply")
 
-    def sim_reply_opponent(self, dev_depths, node_limit, dev_planes_s2, dev_nodes, dev_cuts):
+    def sim_reply_opponent(self, dev_depths, node_limit, dev_planes_s2, dev_nodes, dev_cuts, quiescence=0):
         """``sim_reply`` with the built-in opponent's move as the reply: device pointers to int32 [count] depths, the
-        planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies."""
-        self._ck(self._L.crl_sim_reply_opponent(
-            self._h, ctypes.c_void_p(dev_depths), int(node_limit), ctypes.c_void_p(dev_planes_s2),
-            ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts)), "crl_sim_reply_opponent")
+        planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies; ``quiescence`` plies (0 ..
+        OPP_MAX_QUIESCENCE) past the depth."""
+        self._ck(self._L.crl_sim_reply_opponent_q(
+            self._h, ctypes.c_void_p(dev_depths), int(quiescence), int(node_limit), ctypes.c_void_p(dev_planes_s2),
+            ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts)), "crl_sim_reply_opponent_q")
 
     def sim_backup(self, dev_policy_s2, dev_value_s2):
         self._ck(self._L.crl_sim_backup(self._h, ctypes.c_void_p(dev_policy_s2),
@@ -679,8 +684,9 @@ class Context(object):
                                      vp(dev_value), vp(dev_results), vp(dev_plies)), "crl_rollout")
 
     # ---- the built-in opponent (csrc/opponent.hpp; stockfish.py:23-31, gamestockfish.py:27-41) ------
-    def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT):
-        """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it.
+    def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT, quiescence=0):
+        """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it,
+        with ``quiescence`` plies (0 .. OPP_MAX_QUIESCENCE, one value per call) of quiescence search past the depth.
         Returns (moves u16, scores i32, nodes i64, flags u8); with ``push`` the moves are played."""
         dp = np.ascontiguousarray(depths, dtype=np.int32)
         assert dp.shape == (self.G,)
@@ -688,8 +694,9 @@ class Context(object):
         scores = np.zeros(self.G, np.int32)
         nodes = np.zeros(self.G, np.int64)
         flags = np.zeros(self.G, np.uint8)
-        self._ck(self._L.crl_opponent_moves(self._h, _ptr(dp), 1 if push else 0, int(node_limit), _ptr(moves),
-                                            _ptr(scores), _ptr(nodes), _ptr(flags)), "crl_opponent_moves")
+        self._ck(self._L.crl_opponent_moves_q(self._h, _ptr(dp), int(quiescence), 1 if push else 0, int(node_limit),
+                                              _ptr(moves), _ptr(scores), _ptr(nodes), _ptr(flags)),
+                 "crl_opponent_moves_q")
         return moves, scores, nodes, flags
 
     # ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------

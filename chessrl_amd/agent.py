@@ -87,13 +87,13 @@ class Agent(Player):
         ``simulation.Rollouts`` or None for the value head), reused across moves; its node pool holds
         max(max_iters + 1, tree_nodes) nodes -- max_iters + 1 with ``threads`` > 1, where every search starts from
         a fresh tree.  ``reply``: a ``MinimaxPlayer`` -- the engine that searches against the built-in opponent, one
-        per (max_iters, search depth, node limit); what it cannot be combined with is refused by the engine."""
+        per (max_iters, search depth, node limit, quiescence); what it cannot be combined with is refused by the engine."""
         from .engine import LockstepEngine
         if reply is not None:
             from .opponent import MinimaxPlayer
             if not isinstance(reply, MinimaxPlayer):
                 raise TypeError("reply must be None or a chessrl_amd.opponent.MinimaxPlayer")
-            key = ("reply", max_iters, reply.search_depth, reply.node_limit)
+            key = ("reply", max_iters, reply.search_depth, reply.node_limit, reply.quiescence)
             if threads > 1 or simulate is not None or key not in self._engines:      # (the first two: refused there)
                 self._engines[key] = LockstepEngine(self.model, n_games=1, max_sims=max_iters, simulate=simulate,
                                                     threads=threads, numpy_promotion=self.numpy_promotion, reply=reply)

@@ -43,7 +43,7 @@ def _load_model(model_dir):
     return ChessModel(weights=path if os.path.exists(path) else None)
 
 
-def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white):
+def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence=0):
     """(moves, plies, results) of the games with ``Agent.best_move(real_game=True)`` on the agent's plies."""
     import torch
     ctx = _lib.Context(games, 1, max_plies=max(max_plies, 2), device=dev.index or 0)
@@ -63,25 +63,25 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white):
                 policy = model(planes)[0].float().contiguous()
                 ctx.greedy_moves(policy.data_ptr(), mask=agent_turn, push=True, want_moves=False)
             if opp_turn.any():
-                ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True)
+                ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True, quiescence=quiescence)
             results = ctx.results()
         return ctx.records()
     finally:
         ctx.close()
 
 
-def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims):
+def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, quiescence=0):
     """(moves, plies, results) of the games with ``sims`` simulations per move against the opponent's replies.  A game
     is searched while it runs and has fewer than ``max_plies`` plies; a move adds two plies (one if it ends the game),
     so a game may end one ply past ``max_plies``."""
     from .engine import LockstepEngine, choose_children
     from .opponent import MinimaxPlayer
     eng = LockstepEngine(model, games, sims, device=dev.index or 0, max_plies=max_plies + 2,
-                         reply=MinimaxPlayer(False, search_depth=opponent_depth))
+                         reply=MinimaxPlayer(False, search_depth=opponent_depth, quiescence=quiescence))
     try:
         ctx = eng.ctx
         if not agent_white.all():                            # gamestockfish.py:31-33: the opponent opens as white
-            ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True)
+            ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True, quiescence=quiescence)
         while True:
             _, plies, results = ctx.records(with_moves=False)
             live = (results == _lib.RESULT_NONE) & (plies < max_plies)
@@ -98,8 +98,9 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
 
 
 def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=None, max_plies=512, model=None,
-              sims=0):
-    """Plays ``games`` games against the built-in depth-``opponent_depth`` opponent and returns
+              sims=0, opponent_quiescence=0):
+    """Plays ``games`` games against the built-in depth-``opponent_depth`` opponent (with ``opponent_quiescence``
+    plies of quiescence search, 0 by default) and returns
     ``dict(played=, won=, drawn=, games=)``: the reference's tallies and the per-game UCI move lists.  ``workers`` is
     accepted and ignored (the games run in lockstep on one GPU); ``model`` takes a ready evaluator (planes ->
     (policy, value) on the GPU) instead of the newest weights of ``model_dir``.  A game still running after
@@ -107,6 +108,9 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     MCTS of ``sims`` simulations against the opponent's replies instead of its greedy move (module docstring)."""
     if not 1 <= int(opponent_depth) <= _lib.OPP_MAX_DEPTH:
         raise ValueError("opponent_depth must lie in [1, %d]" % _lib.OPP_MAX_DEPTH)
+    quiescence = int(opponent_quiescence)
+    if not 0 <= quiescence <= _lib.OPP_MAX_QUIESCENCE:
+        raise ValueError("opponent_quiescence must lie in [0, %d]" % _lib.OPP_MAX_QUIESCENCE)
     sims = int(sims)
     if sims < 0:
         raise ValueError("sims must be 0 (the greedy agent) or the number of simulations per move")
@@ -121,15 +125,17 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     dev = torch.device(dev)
     agent_white = np.array(colors, dtype=bool)
     if sims > 0:
-        moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims)
+        moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims,
+                                             quiescence)
     else:
-        moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white)
+        moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence)
     res = [None if r == _lib.RESULT_NONE else int(r) for r in results]
     out = tally(colors, res)
     out["games"] = [[move_to_uci(m) for m in moves[i, :plies[i]]] for i in range(games)]
     if log:
         print("##################### SUMMARY ###################")
-        print("Against the built-in depth-%d opponent (not Stockfish, no Elo)" % opponent_depth)
+        print("Against the built-in depth-%d opponent%s (not Stockfish, no Elo)"
+              % (opponent_depth, ", quiescence %d" % quiescence if quiescence else ""))
         if sims > 0:
             print("agent: MCTS, %d simulations per move" % sims)
         print("Games played: %d" % out["played"])
@@ -145,13 +151,15 @@ def main(argv=None):
     p.add_argument("model_dir", help="directory of the model-<v>.npz / .h5 weight files")
     p.add_argument("--games", type=int, default=10)
     p.add_argument("--depth", type=int, default=2, help="search depth of the built-in opponent (1-5)")
+    p.add_argument("--quiescence", type=int, default=0,
+                   help="quiescence plies of the built-in opponent past its depth (0-6; 0: none)")
     p.add_argument("--seed", type=int, default=None, help="seed of the colour draw")
     p.add_argument("--max-plies", type=int, default=512)
     p.add_argument("--sims", type=int, default=0,
                    help="simulations per move of the agent's search against the opponent's replies (0: the greedy agent)")
     a = p.parse_args(argv)
     benchmark(a.model_dir, games=a.games, opponent_depth=a.depth, seed=a.seed, max_plies=a.max_plies, log=True,
-              sims=a.sims)
+              sims=a.sims, opponent_quiescence=a.quiescence)
 
 
 if __name__ == "__main__":

@@ -27,6 +27,7 @@ static_assert(CRL_MAX_MOVES == MAX_MOVES && CRL_N_LABELS == N_LABELS && CRL_PLAN
               "header constants");
 static_assert(CRL_OPP_MAX_DEPTH == OPP_MAX_DEPTH && CRL_OPP_CUT == OPP_CUT && CRL_OPP_SKIPPED == OPP_SKIPPED,
               "opponent constants");
+static_assert(CRL_OPP_MAX_QUIESCENCE == OPP_MAX_QUIESCENCE, "opponent quiescence limit");
 
 static thread_local std::string g_create_error;
 
@@ -758,10 +759,13 @@ int crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, c
 }
 
 // ---- the built-in opponent (csrc/opponent.hpp): stockfish.py:23-31, gamestockfish.py:27-41 ---------------------
-int crl_opponent_moves(crl_ctx *ctx, const int32_t *depths, int push, int64_t node_limit, uint16_t *moves,
-                       int32_t *scores, int64_t *nodes, uint8_t *flags)
+// (quiescence = 0 launches the kernel of the search without it: the same code and LDS as before there was one)
+int crl_opponent_moves_q(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_limit,
+                         uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags)
 {
     ENTER(ctx, depths && moves && node_limit >= 1);
+    if (quiescence < 0 || quiescence > CRL_OPP_MAX_QUIESCENCE)
+        return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves: a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
     const size_t G = ctx->W;
     for (size_t i = 0; i < G; i++)
         if (depths[i] < 0 || depths[i] > CRL_OPP_MAX_DEPTH)
@@ -769,8 +773,12 @@ int crl_opponent_moves(crl_ctx *ctx, const int32_t *depths, int push, int64_t no
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int64_t) <= sizeof(double), "node counts in t_f64");
     long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
     HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
-    LAUNCH(ctx, k_opponent_moves, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_limit, ctx->t_u16a,
-           ctx->t_i32c, dnodes, ctx->t_u8);
+    if (quiescence > 0)
+        LAUNCH(ctx, k_opponent_moves_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_limit,
+               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8);
+    else
+        LAUNCH(ctx, k_opponent_moves, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_limit, ctx->t_u16a,
+               ctx->t_i32c, dnodes, ctx->t_u8);
     HIP_TRY(ctx, to_host(ctx, moves, ctx->t_u16a, G));
     HIP_TRY(ctx, to_host(ctx, scores, ctx->t_i32c, G));
     HIP_TRY(ctx, to_host(ctx, (long long *)nodes, dnodes, G));
@@ -778,16 +786,33 @@ int crl_opponent_moves(crl_ctx *ctx, const int32_t *depths, int push, int64_t no
     return check_dev_error(ctx);
 }
 
+int crl_opponent_moves(crl_ctx *ctx, const int32_t *depths, int push, int64_t node_limit, uint16_t *moves,
+                       int32_t *scores, int64_t *nodes, uint8_t *flags)
+{
+    return crl_opponent_moves_q(ctx, depths, 0, push, node_limit, moves, scores, nodes, flags);
+}
+
 // the reply of a search step from the built-in opponent (mctree.py:244-246 with gamestockfish.py:27-41 as the mover):
 // device pointers only, so the call captures into the step's hipGraph like crl_sim_reply
+int crl_sim_reply_opponent_q(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_limit,
+                             void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32)
+{
+    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && node_limit >= 1 &&
+                   quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "node accumulators");
+    if (quiescence > 0)
+        LAUNCH(ctx, k_reply_opponent_q, ctx->d, dev_depths_i32, quiescence, (long long)node_limit, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32);
+    else
+        LAUNCH(ctx, k_reply_opponent, ctx->d, dev_depths_i32, (long long)node_limit, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32);
+    return CRL_OK;
+}
+
 int crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t node_limit, void *dev_planes_s2,
                            uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32)
 {
-    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && node_limit >= 1);
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "node accumulators");
-    LAUNCH(ctx, k_reply_opponent, ctx->d, dev_depths_i32, (long long)node_limit, dev_planes_s2,
-           (unsigned long long *)dev_nodes_u64, dev_cuts_u32);
-    return CRL_OK;
+    return crl_sim_reply_opponent_q(ctx, dev_depths_i32, 0, node_limit, dev_planes_s2, dev_nodes_u64, dev_cuts_u32);
 }
 
 // ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------------------------

@@ -21,7 +21,24 @@
 //     3. r = mate (the side to move is mated): the value is -(30000 - k).  Any other result (a draw): 0;
 //     4. no result and k = d (no depth remains): the static evaluation;
 //     5. otherwise the search of the moves.
-// Horizon nodes are generated too, so depth d sees a mate delivered by ply d; there is no quiescence search.
+// Horizon nodes are generated too, so depth d sees a mate delivered by ply d.
+//
+// QUIESCENCE.  Q = quiescence plies of the call, 0 .. CRL_OPP_MAX_QUIESCENCE (6), the same for every slot.  Q = 0 is
+// the search above and nothing else.  For Q > 0 the node at ply k >= d is a quiescence node, j = k - d; nodes at k < d
+// are unchanged.  Steps 1-3 hold for it as they stand (its moves are generated: one node, counted and tested against
+// the node limit like any other; a result is -(30000 - k) or 0).  Without a result:
+//     4a. j = Q (no quiescence ply remains): the static evaluation, in check or not;
+//     4b. the side to move is in check: ALL legal moves are searched in the below-root order; no stand-pat, best
+//         starts at -INF;
+//     4c. otherwise stand = the static evaluation and best = stand.  If stand >= beta the node returns stand and
+//         searches nothing; otherwise alpha = max(alpha, stand) and only the TACTICAL moves (the predicate below) are
+//         searched, in a stable partition by victim: queen, rook, bishop, knight, pawn (en passant counts as pawn),
+//         then the promotions that capture nothing; generation order inside a class; a capturing promotion sorts by
+//         its victim.  Without a tactical move the value is stand.
+// Children, the strictly-greater rule, alpha and the cut are those of SEARCH.  The root (k = 0 < d) is never a
+// quiescence node, so the root rule holds.  The evaluation is bounded by material, so a score that is not a mate stays
+// inside (-30000 + k, 30000 - k).  Not done: delta or exchange pruning, checks other than the evasions of 4b.
+// (tests/quiescence_util.py restates this section.)
 //
 // ORDER OF THE MOVES.  At the root: python-chess generation order, as wave_movegen emits it.  Below the root: a stable
 // partition, tactical moves first, generation order inside each class.  A move is tactical if
@@ -42,6 +59,10 @@
 // (game_push's scratch shares the bytes: the frames are dead when the move is pushed).  The main loop is
 // `while (nodes < limit)` and every turn generates exactly one node; the unwinding inside a turn strictly
 // decreases the ply.  So the loop is bounded by the node limit by construction: a logic error ends as a flagged cut.
+// With Q > 0 a node that searches moves lies at ply <= d + Q - 1: 5 + 6 = 11 frames, 6.5 KiB, in kernels of their own
+// (k_opponent_moves_q, k_reply_opponent_q; one search body, a template parameter apart), so a Q = 0 launch runs the
+// code and keeps the LDS it had.  A quiescence node that stands pat at or above beta, or lies at j = Q, is generated
+// without a list and takes no frame; whether it is in check is read from the board before its moves are generated.
 //
 // NODE LIMIT, per slot.  The limit is tested before every node.  When the count has reached it and the search is not
 // finished, the search ends: the slot returns the best root move among those COMPLETELY searched (and its score), or
@@ -58,6 +79,7 @@
 namespace crl {
 
 constexpr int OPP_MAX_DEPTH = 5;
+constexpr int OPP_MAX_QUIESCENCE = 6;
 constexpr int OPP_INF = 32000;
 constexpr int OPP_MATE = 30000;
 constexpr uint8_t OPP_CUT = 1, OPP_SKIPPED = 2;
@@ -69,8 +91,9 @@ struct __attribute__((aligned(16))) OppFrame {
 };
 static_assert(sizeof(OppFrame) == 608, "OppFrame must be 608 bytes");
 
+template <bool QS>                         // QS: a search with quiescence plies
 union OppLds {
-    OppFrame f[OPP_MAX_DEPTH + 1];
+    OppFrame f[QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1];
     WaveLds w;                             // game_push, after the search
 };
 
@@ -149,13 +172,81 @@ __device__ inline void opp_partition(const Board &b, u16 *mv, int n, int lane)
     __syncthreads();
 }
 
+// whether the side to move is in check (what wave_movegen reports as in_check), wave-uniform
+__device__ inline bool opp_in_check(const Board &b)
+{
+    const bool white = st_turn(b.state);
+    const u64 occ = occupied(b);
+    const u64 kbb = b.bb[KING] & (white ? b.white : (occ & ~b.white));
+    return kbb && attackers_to(b, msb(kbb), occ, !white) != 0;
+}
+
+// the class of a move in a quiescence node that stands pat: 0 .. 4 = its victim Q R B N P (en passant: P), 5 = a
+// promotion that captures nothing, 6 = not tactical
+__device__ inline int opp_victim_class(const Board &b, u64 occ, u64 own, u32 mv)
+{
+    const int to = (mv >> 6) & 63;
+    if (occ & ~own & bit(to)) {
+        const int pt = piece_at(b, to);
+        return pt >= QUEEN ? 0 : QUEEN - pt;               // (a legal move never takes a king)
+    }
+    if (!opp_tactical(b, occ, own, mv)) return 6;
+    return ((mv >> 12) & 7) ? 5 : 4;
+}
+
+// stable partition of mv[0 .. n) by opp_victim_class, the scheme of opp_partition with seven ballots per 64 moves.
+// Returns the number of tactical moves: they are mv[0 .. that).  mv is visible on entry and on return.
+__device__ inline int opp_partition_victim(const Board &b, u16 *mv, int n, int lane)
+{
+    constexpr int NC = 7;
+    const u64 occ = occupied(b);
+    const u64 own = st_turn(b.state) ? b.white : (occ & ~b.white);
+    const u64 below = bit(lane) - 1;
+    u32 m[4];
+    int cl[4], tot[NC];
+    u64 C[4][NC];
+#pragma unroll
+    for (int q = 0; q < NC; q++) tot[q] = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int i = c * 64 + lane;
+        const bool valid = i < n;
+        m[c] = valid ? mv[i] : 0u;
+        cl[c] = valid ? opp_victim_class(b, occ, own, m[c]) : -1;
+#pragma unroll
+        for (int q = 0; q < NC; q++) {
+            C[c][q] = __ballot(cl[c] == q);
+            tot[q] += popc(C[c][q]);
+        }
+    }
+    __syncthreads();                                   // every move read before any is rewritten
+    int base[NC];
+    base[0] = 0;
+#pragma unroll
+    for (int q = 1; q < NC; q++) base[q] = base[q - 1] + tot[q - 1];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        int pos = -1;
+#pragma unroll
+        for (int q = 0; q < NC; q++) {
+            if (cl[c] == q) pos = base[q] + popc(C[c][q] & below);
+            base[q] += popc(C[c][q]);
+        }
+        if (pos >= 0) mv[pos] = (u16)m[c];             // pos < n: the classes partition the n valid moves
+    }
+    __syncthreads();
+    return n - tot[NC - 1];
+}
+
 // The search of the header comment, stated once for both kernels: from `root` to depth D (1 .. OPP_MAX_DEPTH, checked by
-// the caller) under the node limit, in the frames f[0 .. D].  mv: the move (NO_MOVE only for a root without a legal
+// the caller) with Q quiescence plies (QS: 1 .. OPP_MAX_QUIESCENCE, checked by the caller; otherwise not read) under the
+// node limit, in the frames f[0 .. D] or, QS, f[0 .. D + Q - 1].  mv: the move (NO_MOVE only for a root without a legal
 // move or with a result, which no caller hands in); score, nodes; done = false is the cut.  Every value is
 // wave-uniform.  The frames are dead on return, but not yet fenced: a barrier comes before their bytes are reused.
 struct OppResult { u32 mv; int score; long long nodes; bool done; };
 
-__device__ inline OppResult opp_search(const Board &root, int D, long long limit, OppFrame *f, int lane)
+template <bool QS>
+__device__ inline OppResult opp_search(const Board &root, int D, int Q, long long limit, OppFrame *f, int lane)
 {
     Board b = root;
     int k = 0, a = -OPP_INF, be = OPP_INF, v = 0, root_best = -OPP_INF;
@@ -164,24 +255,37 @@ __device__ inline OppResult opp_search(const Board &root, int D, long long limit
     long long nodes = 0;
     while (nodes < limit) {
         // ---- enter the node `b` at ply k, window (a, be)
-        OppFrame &F = f[k];
-        const bool horizon = k == D;
-        MoveGenInfo mi = wave_movegen(b, lane, horizon ? nullptr : F.mv);
+        OppFrame *const F = f + k;                         // (read only where the node searches moves: k < D + Q)
+        const bool quiet = QS && k >= D;                   // a quiescence node, j = k - D
+        int stand = 0;
+        bool chk = false;
+        if (quiet) { stand = uni(opp_evaluate(b, lane)); chk = opp_in_check(b); }
+        // a node that searches no move: the horizon; with quiescence 4a, and the stand-pat at or above beta of 4c
+        const bool horizon = QS ? quiet && (k >= D + Q || (!chk && stand >= be)) : k == D;
+        MoveGenInfo mi = wave_movegen(b, lane, horizon ? nullptr : F->mv);
         nodes++;
         const int n = uni(mi.n);
         const int res = uni(position_result(b, n, mi.in_check, 1));
         bool have_v = true;
         if (res != RESULT_NONE) v = res == 0 ? 0 : -(OPP_MATE - k);
-        else if (horizon) v = uni(opp_evaluate(b, lane));
+        else if (horizon) v = QS ? stand : uni(opp_evaluate(b, lane));
         else {
-            __syncthreads();                               // F.mv visible
-            if (k > 0) opp_partition(b, F.mv, n, lane);
-            else first_mv = (u32)uni((int)F.mv[0]);
-            if (lane == 0) { F.b = b; F.cur = 0; F.n = n; F.alpha = a; F.beta = be; F.best = -OPP_INF; }
-            __syncthreads();
-            have_v = false;
+            __syncthreads();                               // F->mv visible
+            int cnt = n, best0 = -OPP_INF;
+            if (quiet && !chk) {                           // 4c: stand pat, then the tactical moves by victim
+                cnt = opp_partition_victim(b, F->mv, n, lane);
+                best0 = stand;
+                if (stand > a) a = stand;
+            } else if (k > 0) opp_partition(b, F->mv, n, lane);
+            else first_mv = (u32)uni((int)F->mv[0]);
+            if (QS && cnt == 0) v = stand;                 // 4c without a tactical move (cnt = n > 0 everywhere else)
+            else {
+                if (lane == 0) { F->b = b; F->cur = 0; F->n = cnt; F->alpha = a; F->beta = be; F->best = best0; }
+                __syncthreads();
+                have_v = false;
+            }
         }
-        // ---- hand v up: every turn lowers k, so at most d + 1 of them
+        // ---- hand v up: every turn lowers k, so at most d + Q + 1 of them
         while (have_v) {
             if (k == 0) { done = true; break; }
             k--;
@@ -201,7 +305,7 @@ __device__ inline OppResult opp_search(const Board &root, int D, long long limit
             else v = best;                                 // exhausted or cut: it returns its best
         }
         if (done) break;
-        // ---- descend: the next move of frame k  (k < D: a frame with moves to search is above the horizon)
+        // ---- descend: the next move of frame k  (k < D + Q: a frame with moves to search is above the last ply)
         OppFrame &P = f[k];
         const u32 mv = (u32)uni((int)P.mv[uni(P.cur)]);
         b = apply_move(uni_board(P.b), mv);
@@ -217,22 +321,23 @@ __device__ inline OppResult opp_search(const Board &root, int D, long long limit
     return o;
 }
 
-// window-relative rows: depths / moves / scores / nodes_out / flags [count]
-__global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *depths, int push, long long limit,
-                                                       u16 *moves, int32_t *scores, long long *nodes_out,
-                                                       uint8_t *flags)
+// One slot of k_opponent_moves / k_opponent_moves_q.  Window-relative rows: depths / moves / scores / nodes_out /
+// flags [count]
+template <bool QS>
+__device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, int push, long long limit, u16 *moves,
+                                           int32_t *scores, long long *nodes_out, uint8_t *flags, OppLds<QS> &s)
 {
-    __shared__ OppLds s;
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
     int D = uni(depths[r]);
-    if (D > OPP_MAX_DEPTH) D = OPP_MAX_DEPTH;              // (the host refuses such a depth before the launch)
+    if (D > OPP_MAX_DEPTH) D = OPP_MAX_DEPTH;              // (the host refuses such a depth before the launch,
+    if (Q > OPP_MAX_QUIESCENCE) Q = OPP_MAX_QUIESCENCE;    //  and such a Q)
     const bool skipped = D > 0 && uni(d.game[g].game_result) != RESULT_NONE;
     if (D <= 0 || skipped) {
         if (lane == 0) { moves[r] = NO_MOVE; scores[r] = 0; nodes_out[r] = 0; flags[r] = skipped ? OPP_SKIPPED : 0; }
         return;
     }
     const Board root = uni_board(d.cur[g]);
-    const OppResult o = opp_search(root, D, limit, s.f, lane);
+    const OppResult o = opp_search<QS>(root, D, Q, limit, s.f, lane);
     if (lane == 0) {
         moves[r] = (u16)o.mv;
         scores[r] = o.score;
@@ -245,23 +350,43 @@ __global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *dep
     }
 }
 
+__global__ __launch_bounds__(64) void k_opponent_moves(Dev d, const int32_t *depths, int push, long long limit,
+                                                       u16 *moves, int32_t *scores, long long *nodes_out,
+                                                       uint8_t *flags)
+{
+    __shared__ OppLds<false> s;
+    opponent_moves_slot<false>(d, depths, 0, push, limit, moves, scores, nodes_out, flags, s);
+}
+
+// the same with Q = 1 .. OPP_MAX_QUIESCENCE quiescence plies
+__global__ __launch_bounds__(64) void k_opponent_moves_q(Dev d, const int32_t *depths, int Q, int push, long long limit,
+                                                         u16 *moves, int32_t *scores, long long *nodes_out,
+                                                         uint8_t *flags)
+{
+    __shared__ OppLds<true> s;
+    opponent_moves_slot<true>(d, depths, Q, push, limit, moves, scores, nodes_out, flags, s);
+}
+
 // expand, the opponent's half (mctree.py:244-246) with the built-in opponent as the mover (gamestockfish.py:27-41):
 // the reply stored for S1 is the move k_opponent_moves plays from S1 -- it reads the board alone, so the tree holds the
 // real opponent's reply.  Rows as k_reply: one whose pending leaf is not LEAF_NEW_REPLY only clears lab_n2.  The root
 // order of the search is wave_movegen's (s1_moves is not read).  A cut reply is a move like any other.  nodes_acc /
 // cuts_acc [count], window-relative: this wave owns its row, so lane 0 adds with a plain load and store.
-__global__ __launch_bounds__(64) void k_reply_opponent(Dev d, const int32_t *depths, long long limit, void *planes2,
-                                                       unsigned long long *nodes_acc, uint32_t *cuts_acc)
+template <bool QS>
+__device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, long long limit, void *planes2,
+                                          unsigned long long *nodes_acc, uint32_t *cuts_acc, OppLds<QS> &s)
 {
-    __shared__ OppLds s;
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
     if (lane == 0) d.lab_n2[r] = 0;                     // no policy(S2) wanted unless a new node gets priors
     if (d.game[g].root_dead || d.game[g].leaf_kind != LEAF_NEW_REPLY) return;
     const int D = uni(depths[r]);
-    if (D < 1 || D > OPP_MAX_DEPTH) { dev_error(d, DERR_STATE); return; }   // (the host never sends one)
+    if (D < 1 || D > OPP_MAX_DEPTH || (QS && (Q < 1 || Q > OPP_MAX_QUIESCENCE))) {
+        dev_error(d, DERR_STATE);                       // (the host never sends one)
+        return;
+    }
     const int c = uni(d.game[g].leaf_node);
     const Board s1 = uni_board(d.node[(size_t)g * d.N + c].s1);
-    const OppResult o = opp_search(s1, D, limit, s.f, lane);
+    const OppResult o = opp_search<QS>(s1, D, Q, limit, s.f, lane);
     if (o.mv == NO_MOVE) { dev_error(d, DERR_STATE); return; }              // S1 is running: it has a legal move
     if (lane == 0) {
         nodes_acc[r] += (unsigned long long)o.nodes;
@@ -270,6 +395,21 @@ __global__ __launch_bounds__(64) void k_reply_opponent(Dev d, const int32_t *dep
     __syncthreads();                                       // the frames are dead: s.w takes their bytes
     reply_tail(d, g, r, lane, s.w, c, uni(d.game[g].path_len), uni(d.game[g].ply), s1, o.mv,
                uni(d.game[g].edge_top), d.policy_fmt, &d.game[g].leaf_kind, planes2);
+}
+
+__global__ __launch_bounds__(64) void k_reply_opponent(Dev d, const int32_t *depths, long long limit, void *planes2,
+                                                       unsigned long long *nodes_acc, uint32_t *cuts_acc)
+{
+    __shared__ OppLds<false> s;
+    reply_opponent_row<false>(d, depths, 0, limit, planes2, nodes_acc, cuts_acc, s);
+}
+
+__global__ __launch_bounds__(64) void k_reply_opponent_q(Dev d, const int32_t *depths, int Q, long long limit,
+                                                         void *planes2, unsigned long long *nodes_acc,
+                                                         uint32_t *cuts_acc)
+{
+    __shared__ OppLds<true> s;
+    reply_opponent_row<true>(d, depths, Q, limit, planes2, nodes_acc, cuts_acc, s);
 }
 
 }  // namespace crl

@@ -246,7 +246,7 @@ class LockstepEngine(object):
     evaluator with ``accepts_bitplanes`` is given int64 [G,128] plane bitboards instead.
 
     ``reply``: None -- the reply stored in a node is the net's greedy move -- or a ``chessrl_amd.opponent.MinimaxPlayer``:
-    the built-in opponent's move, searched with the player's ``search_depth`` and ``node_limit`` (its colour is
+    the built-in opponent's move, searched with the player's ``search_depth``, ``quiescence`` and ``node_limit`` (its colour is
     ignored: the side to move after our move replies).
     """
 
@@ -453,7 +453,8 @@ class LockstepEngine(object):
     def phase_reply_opponent(self):
         """Only with ``reply``: the built-in opponent's move from S1 becomes the node's reply."""
         self.ctx.sim_reply_opponent(self.reply_depths.data_ptr(), self.reply.node_limit, self.planes_s2.data_ptr(),
-                                    self.reply_nodes.data_ptr(), self.reply_cuts.data_ptr())
+                                    self.reply_nodes.data_ptr(), self.reply_cuts.data_ptr(),
+                                    quiescence=self.reply.quiescence)
 
     def phase_tower_s2(self):
         if self.legal_priors:

@@ -54,11 +54,16 @@ def side_depths(draws, white_to_move):
     return np.array([pd if is_white == white_to_move else gd for is_white, gd, pd in draws], dtype=np.int32)
 
 
-def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512):
+def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512,
+             quiescence=0):
     """Plays ``num_games`` games, saves the finished ones to ``save_path`` (appending to what the file holds, as
     ``DatasetGame.save`` does) and returns the ``DatasetGame`` it saved.  The reference's ``gen_data`` forgets to
     pass ``depth`` and ``random_dep`` on to ``play_game`` (gen_data_stockfish.py:44-49); here both are honoured.
-    ``workers`` is accepted and ignored; a game still running after ``max_plies`` plies is dropped."""
+    ``workers`` is accepted and ignored; a game still running after ``max_plies`` plies is dropped.  ``quiescence``:
+    the quiescence plies of both sides past their depths (0 .. CRL_OPP_MAX_QUIESCENCE; 0: none)."""
+    quiescence = int(quiescence)
+    if not 0 <= quiescence <= _lib.OPP_MAX_QUIESCENCE:
+        raise ValueError("quiescence must lie in [0, %d]" % _lib.OPP_MAX_QUIESCENCE)
     num_games, opening_plies, max_plies = int(num_games), int(opening_plies), int(max_plies)
     d = DatasetGame()
     if num_games < 1:
@@ -81,7 +86,8 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
             running = results == _lib.RESULT_NONE
             if not running.any():
                 break
-            ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True)
+            ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True,
+                               quiescence=quiescence)
             results = ctx.results()
         moves, plies, results = ctx.records()
     finally:
@@ -101,6 +107,8 @@ def main(argv=None):
     p.add_argument("data_path", metavar="datadir", help="Path of .JSON dataset.")
     p.add_argument("--games", metavar="games", type=int, default=10)
     p.add_argument("--depth", metavar="depth", type=int, default=1, help="Search depth of the built-in opponent.")
+    p.add_argument("--quiescence", type=int, default=0,
+                   help="Quiescence plies of the built-in opponent past its depth, both sides (0-6; 0: none).")
     p.add_argument("--random_depth", action="store_true", default=False,
                    help="Use normal distribution of depths with mean --depth.")
     p.add_argument("--debug", action="store_true", default=False, help="Log debug messages on screen. Default false.")
@@ -109,7 +117,7 @@ def main(argv=None):
     a = p.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if a.debug else logging.INFO)
     gen_data(a.data_path, num_games=a.games, depth=a.depth, random_dep=a.random_depth,
-             opening_plies=a.opening_plies, seed=a.seed)
+             opening_plies=a.opening_plies, seed=a.seed, quiescence=a.quiescence)
 
 
 if __name__ == "__main__":

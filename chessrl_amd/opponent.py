@@ -4,9 +4,10 @@ The reference measures and bootstraps against an engine: ``Stockfish(Player)``
 (/root/reference/src/chessrl/stockfish.py:11-34) and ``GameStockfish(Game)``, a game that answers
 every move of ours with the engine's (gamestockfish.py:6-61).  No engine binary belongs to this
 package; what stands in its place is the fixed-depth alpha-beta player of ``csrc/opponent.hpp``,
-one wavefront per game on the GPU.  It is NOT Stockfish: no repetition below the root, no
-quiescence, no time control, and no Elo is claimed -- a result reads "against the built-in depth-d
-opponent".  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
+one wavefront per game on the GPU.  It is NOT Stockfish: no repetition below the root, no time
+control, and no Elo is claimed -- a result reads "against the built-in depth-d opponent".  Past the
+fixed depth it can search ``quiescence`` plies of captures, promotions and check evasions
+(opponent.hpp, QUIESCENCE); 0, the default, is the fixed-depth search alone.  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
 these classes are the one-game drop-in surface over it.
 """
 import numpy as np
@@ -16,6 +17,7 @@ from .game import Game, arena, move_to_uci
 from .player import Player
 
 MAX_DEPTH = _lib.OPP_MAX_DEPTH
+MAX_QUIESCENCE = _lib.OPP_MAX_QUIESCENCE
 NODE_LIMIT = _lib.OPP_NODE_LIMIT
 
 
@@ -26,15 +28,19 @@ def clamp_depth(depth):
 
 class MinimaxPlayer(Player):
     """Mirror of ``Stockfish(Player)``: ``best_move(game)`` is the UCI string of the depth-``search_depth``
-    alpha-beta move for a ``chessrl_amd.Game`` (``'00000'`` on a finished game)."""
+    alpha-beta move for a ``chessrl_amd.Game`` (``'00000'`` on a finished game), with ``quiescence`` plies of
+    quiescence search past that depth."""
 
-    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT):
+    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0):
         super().__init__(color)
         if not 1 <= int(search_depth) <= MAX_DEPTH:
             raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
         if int(node_limit) < 1:
             raise ValueError("node_limit must be at least 1")
+        if not 0 <= int(quiescence) <= MAX_QUIESCENCE:
+            raise ValueError("quiescence must lie in [0, %d]" % MAX_QUIESCENCE)
         self.search_depth = int(search_depth)
+        self.quiescence = int(quiescence)
         self.node_limit = int(node_limit)
         self.last = None                      # (score, nodes, flag) of the last search
 
@@ -43,7 +49,7 @@ class MinimaxPlayer(Player):
             raise RuntimeError("Game was freed")
         ctx = arena().one(game._slot)
         moves, scores, nodes, flags = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False,
-                                                         node_limit=self.node_limit)
+                                                         node_limit=self.node_limit, quiescence=self.quiescence)
         self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
         if int(moves[0]) == _lib.NO_MOVE:
             return Game.NULL_MOVE
@@ -55,15 +61,18 @@ class MinimaxPlayer(Player):
 
 class GameOpponent(Game):
     """Mirror of ``GameStockfish``: a game against the built-in opponent.  ``opponent``: a ``MinimaxPlayer``, or
-    None for one of depth ``opponent_depth`` with the colour opposite to ``player_color``."""
+    None for one of depth ``opponent_depth`` and ``opponent_quiescence`` with the colour opposite to
+    ``player_color``."""
 
-    def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2):
+    def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2,
+                 opponent_quiescence=0):
         if opponent is not None and not isinstance(opponent, MinimaxPlayer):
             raise ValueError("opponent must be a MinimaxPlayer or None")
         self.opponent = None                  # (a board's move stack is replayed by plain Game.move)
         super().__init__(board=board, player_color=player_color, date=date)
         if opponent is None:
-            opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth)
+            opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth,
+                                     quiescence=opponent_quiescence)
         self.opponent = opponent
 
     def move(self, movement):

@@ -271,8 +271,8 @@ int  crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, 
 /* ---- the built-in opponent: a fixed-depth alpha-beta player per slot (csrc/opponent.hpp states the search, the
  * node value, the move order, the static evaluation and the node limit).  It stands where the reference calls its
  * engine: Stockfish.best_move (stockfish.py:23-31, engine.play(board, Limit(depth))) and the reply inside
- * GameStockfish.move (gamestockfish.py:27-41).  It is not that engine: no repetition below the root, no quiescence,
- * no time control, no Elo.  Host arrays, synchronous, window-relative like crl_greedy_moves.
+ * GameStockfish.move (gamestockfish.py:27-41).  It is not that engine: no repetition below the root, quiescence
+ * only through the _q calls below, no time control, no Elo.  Host arrays, synchronous, window-relative like crl_greedy_moves.
  * depths[g] (host int32): 0 leaves slot g alone, 1 .. CRL_OPP_MAX_DEPTH searches it to that depth -- the array is
  * both the mask and the per-game depth.  node_limit >= 1 bounds the nodes (move generations) of every slot: a slot
  * that reaches it returns the best root move among those completely searched, or its first legal move, and the flag
@@ -300,6 +300,17 @@ int  crl_opponent_moves(crl_ctx *ctx, const int32_t *depths /*G*/, int push, int
  * is a device error (reported as CRL_ERR_STATE by the next synchronising call). */
 int  crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t node_limit, void *dev_planes_s2,
                             uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32);
+/* The two calls above with `quiescence` plies of quiescence search past the fixed depth, one value per call:
+ * 0 .. CRL_OPP_MAX_QUIESCENCE (csrc/opponent.hpp, QUIESCENCE: stand-pat, the tactical moves by victim, every evasion
+ * when in check, the static evaluation after the last ply).  quiescence = 0 is the call above: the same moves, scores,
+ * node counts and flags, from the same kernel.  Node counts grow with quiescence; node_limit bounds them as before.
+ * CRL_ERR_ARG: what the call above refuses, or a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE.  No state changes
+ * on an error. */
+#define CRL_OPP_MAX_QUIESCENCE 6
+int  crl_opponent_moves_q(crl_ctx *ctx, const int32_t *depths /*G*/, int quiescence, int push, int64_t node_limit,
+                          uint16_t *moves /*G*/, int32_t *scores /*G*/, int64_t *nodes /*G*/, uint8_t *flags /*G*/);
+int  crl_sim_reply_opponent_q(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_limit,
+                              void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32);
 
 /* ---- threads > 1: virtual-loss waves of simulations per game (csrc/search_wave.hpp) --------------------------
  * The reference runs `threads` explore_tree workers on one tree, kept apart by a virtual loss (mctree.py:12,173-176,

@@ -2,11 +2,13 @@
 """Node rate of the built-in opponent (csrc/opponent.hpp): ms per launch, nodes per slot and nodes/s at depths 1, 2, 3.
 
     python tools/opponent_probe.py [--games 4096] [--opening-plies 6] [--node-limit 200000] [--out profiles/opponent_probe.json]
+    python tools/opponent_probe.py --quiescence 2,4,6 --depths 1,2 --out profiles/opponent_probe_q.json
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words), so the slots hold
 different positions.  Per depth, in depth order: one warm-up launch, then three timed ones (host wall time around the
 synchronous call, copies included); the median is reported.  Nothing is pushed, so every launch searches the same
-positions.  No threshold: this is a measurement.
+positions.  --quiescence Q[,Q..]: the same per quiescence (opponent.hpp QUIESCENCE), keyed "<depth>+q<Q>"; 0, the
+default, is the fixed-depth search and leaves the output as it was.  No threshold: this is a measurement.
 """
 import argparse
 import json
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--opening-plies", type=int, default=6)
     ap.add_argument("--node-limit", type=int, default=200000)
     ap.add_argument("--depths", default="1,2,3")
+    ap.add_argument("--quiescence", default="0")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "opponent_probe.json"))
     args = ap.parse_args()
     import numpy as np
@@ -37,22 +40,25 @@ def main():
     played, _, _ = ctx.rollout_games(words, np.full(G, words.shape[1], np.int32), 1, args.opening_plies)
     out = {"games": G, "opening_plies": args.opening_plies, "mean_opening_plies": float(played.mean()),
            "node_limit": args.node_limit, "running": int((ctx.results() == _lib.RESULT_NONE).sum()), "depths": {}}
-    for depth in (int(x) for x in args.depths.split(",")):
+    cases = [(int(d), int(q)) for q in args.quiescence.split(",") for d in args.depths.split(",")]
+    for depth, quiescence in cases:
         row = np.full(G, depth, np.int32)
+        key = str(depth) if quiescence == 0 else "%d+q%d" % (depth, quiescence)
+        kw = {"quiescence": quiescence} if quiescence else {}
         times = []
         for i in range(4):
             t0 = time.perf_counter()
-            moves, scores, nodes, flags = ctx.opponent_moves(row, node_limit=args.node_limit)
+            moves, scores, nodes, flags = ctx.opponent_moves(row, node_limit=args.node_limit, **kw)
             if i:
                 times.append(time.perf_counter() - t0)
         t = statistics.median(times)
         searched = flags != _lib.OPP_SKIPPED
         total = int(nodes.sum())
-        out["depths"][str(depth)] = {
+        out["depths"][key] = {
             "seconds": times, "ms_per_launch": 1e3 * t, "nodes": total, "nodes_per_slot_mean": float(nodes[searched].mean()),
             "nodes_per_slot_max": int(nodes.max()), "nodes_per_s": total / t, "us_per_node_of_the_longest_slot":
             1e6 * t / max(int(nodes.max()), 1), "cut_share": float((flags == _lib.OPP_CUT).mean())}
-        print(depth, json.dumps(out["depths"][str(depth)]), flush=True)
+        print(key, json.dumps(out["depths"][key]), flush=True)
     ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
