@@ -75,39 +75,27 @@ class Agent(Player):
             best_move = game.get_legal_moves()[int(np.argmax(policy))]
         elif game.get_result() is None:
             from . import mctree
-            if reply is not None:
-                tree = mctree.SelfPlayTree(game, threads=self.num_threads, reply=reply)
-            else:
-                tree = mctree.SelfPlayTree(game, threads=self.num_threads, virtual_loss=self.virtual_loss)
+            tree = mctree.SelfPlayTree(game, threads=self.num_threads, virtual_loss=self.virtual_loss and reply is None,
+                                       reply=reply)
             best_move = tree.search_move(self, max_iters=max_iters, verbose=verbose, ai_move=ai_move)
         return best_move
 
-    def engine_for(self, max_iters, simulate=None, threads=1, reply=None):
-        """One single-game LockstepEngine per (simulation budget, threads) (and leaf evaluator: ``simulate``, a
-        ``simulation.Rollouts`` or None for the value head), reused across moves; its node pool holds
-        max(max_iters + 1, tree_nodes) nodes -- max_iters + 1 with ``threads`` > 1, where every search starts from
-        a fresh tree.  ``reply``: a ``MinimaxPlayer`` -- the engine that searches against the built-in opponent, one
-        per (max_iters, search depth, node limit, quiescence); what it cannot be combined with is refused by the engine."""
+    def engine_for(self, max_iters, simulate=None, threads=1, reply=None, mode=None):
+        """One single-game LockstepEngine per (simulation budget, ``SearchMode.key``), reused across moves: ``threads``
+        workers per tree, leaves valued by ``simulate`` (a ``simulation.Rollouts`` or None for the value head), replies
+        by ``reply`` (a ``MinimaxPlayer`` or None for the net's greedy move) -- or a ``SearchMode`` that says all three.
+        A combination the mode does not cover is refused by it.  The node pool holds max(max_iters + 1, tree_nodes)
+        nodes where the mode covers tree reuse, else max_iters + 1: every search there starts from a fresh tree."""
         from .engine import LockstepEngine
-        if reply is not None:
-            from .opponent import MinimaxPlayer
-            if not isinstance(reply, MinimaxPlayer):
-                raise TypeError("reply must be None or a chessrl_amd.opponent.MinimaxPlayer")
-            key = ("reply", max_iters, reply.search_depth, reply.node_limit, reply.quiescence)
-            if threads > 1 or simulate is not None or key not in self._engines:      # (the first two: refused there)
-                self._engines[key] = LockstepEngine(self.model, n_games=1, max_sims=max_iters, simulate=simulate,
-                                                    threads=threads, numpy_promotion=self.numpy_promotion, reply=reply)
-            return self._engines[key]
-        key = (max_iters, threads) if simulate is None else (max_iters, threads, simulate)
+        from .searchmode import SearchMode
+        if mode is None:
+            mode = SearchMode(threads, simulate, reply)
+        key = (max_iters, mode.key)
         if key not in self._engines:
-            if threads > 1:
-                self._engines[key] = LockstepEngine(self.model, n_games=1, max_sims=max_iters, simulate=simulate,
-                                                    numpy_promotion=self.numpy_promotion, threads=threads)
-            else:
-                nodes = max(max_iters + 1, self.tree_nodes or 0)
-                self._engines[key] = LockstepEngine(
-                    self.model, n_games=1, max_sims=nodes - 1, max_nodes=nodes, numpy_promotion=self.numpy_promotion,
-                    simulate=simulate)
+            nodes = max(max_iters + 1, self.tree_nodes or 0) if mode.covers("tree_reuse") else max_iters + 1
+            self._engines[key] = LockstepEngine(
+                self.model, n_games=1, max_sims=nodes - 1, max_nodes=nodes, numpy_promotion=self.numpy_promotion,
+                simulate=mode.simulate, threads=mode.threads, reply=mode.reply)
         return self._engines[key]
 
     def get_copy(self):

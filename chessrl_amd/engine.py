@@ -47,7 +47,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .simulation import Rollouts, stream_keys
+from .searchmode import REPLY_REFUSED, SearchMode        # (REPLY_REFUSED: importable from here as ever)
+from .simulation import stream_keys
 
 
 def compute_policy(visits, root_visits, nb_moves, noise=True, rng=None):
@@ -225,20 +226,6 @@ def summarise_stamps(stamps):
                           "min_ms": min(v), "max_ms": max(v)} for k, v in trunk.items()}}
 
 
-# what LockstepEngine(reply=MinimaxPlayer) does not cover, each refused with a ValueError that names it
-REPLY_REFUSED = {
-    "threads": "reply= cannot be combined with threads > 1: the opponent's reply kernel serves one pending leaf per game",
-    "simulate": "reply= cannot be combined with rollouts (simulate=Rollouts): the three-phase step has no playout phase",
-    "max_nodes": "reply= cannot be combined with max_nodes (tree reuse): a search against the opponent starts from a "
-                 "fresh tree",
-    "reroot": "reply= cannot be combined with reroot: a search against the opponent starts from a fresh tree",
-    "keep_root": "reply= cannot be combined with keep_root=True: a search against the opponent starts from a fresh tree",
-    "set_stamps": "reply= cannot be combined with set_stamps: the stamped step is the four-phase step",
-    "node": "reply= cannot continue a Node: a search against the opponent starts from a fresh tree (construct the "
-            "tree from the Game)",
-}
-
-
 class LockstepEngine(object):
     """G games x one search tree each on one GPU.
 
@@ -254,40 +241,18 @@ class LockstepEngine(object):
                  numpy_promotion="auto", use_graph=True, bitplanes=None, legal_priors=None, raw_priors=None,
                  steps_per_graph=None, max_nodes=None, simulate=None, threads=1, reply=None):
         numpy_promotion = resolve_numpy_promotion(numpy_promotion)
-        # reply=MinimaxPlayer: the replies in the tree are the built-in opponent's.  What that step does not cover is
-        # refused by name before anything touches the device.
-        if reply is not None:
-            from .opponent import MinimaxPlayer
-            if not isinstance(reply, MinimaxPlayer):
-                raise TypeError("reply must be None or a chessrl_amd.opponent.MinimaxPlayer")
-            if int(threads) > 1:
-                raise ValueError(REPLY_REFUSED["threads"])
-            if simulate is not None:
-                raise ValueError(REPLY_REFUSED["simulate"])
-            if max_nodes is not None and max_nodes != max_sims + 1:
-                raise ValueError(REPLY_REFUSED["max_nodes"])
-        self.reply = reply
-        if simulate is not None and not isinstance(simulate, Rollouts):
-            raise TypeError("simulate must be None or a chessrl_amd.simulation.Rollouts")
-        # threads > 1: virtual-loss waves.  What the wave kernels do not cover is refused by name, never ignored.
-        threads = int(threads)
-        if not 1 <= threads <= _lib.WAVE_MAX_THREADS:
-            raise ValueError("threads must lie in [1, %d]" % _lib.WAVE_MAX_THREADS)
-        if threads > 1:
-            if simulate is not None:
-                raise ValueError("threads > 1 cannot be combined with rollouts (simulate=Rollouts): the playout kernel "
-                                 "values one pending leaf per game")
-            if legal_priors:
-                raise ValueError("threads > 1 cannot be combined with legal_priors=True: the wave kernels read full "
-                                 "policy vectors")
-            if raw_priors:
-                raise ValueError("threads > 1 cannot be combined with raw_priors=True: the wave kernels read full "
-                                 "policy vectors")
-            if max_nodes is not None and max_nodes != max_sims + 1:
-                raise ValueError("threads > 1 cannot be combined with max_nodes (tree reuse): a wave search starts from "
-                                 "a fresh tree")
+        # what kind of step this is, and -- by name, before anything touches the device -- what that kind does not cover
+        mode = SearchMode(threads, simulate, reply)
+        if legal_priors:
+            mode.require("legal_priors", "legal_priors")
+        if raw_priors:
+            mode.require("raw_priors", "raw_priors")
+        if max_nodes is not None and max_nodes != max_sims + 1:
+            mode.require("tree_reuse", "max_nodes")
+        if not mode.covers("legal_priors"):      # the search reads the full policy vectors
             legal_priors, raw_priors = False, False
-        self.threads = threads
+        threads = mode.threads
+        self.threads, self.simulate, self.reply = threads, simulate, reply
         # node budget of every tree (default max_sims + 1: a fresh tree per move never needs more); a larger
         # one leaves room for the subtree ``reroot`` keeps across a move boundary
         if max_nodes is None:
@@ -307,10 +272,8 @@ class LockstepEngine(object):
         # the kernel triple of a step -- select, reply and the last backup -- chosen once: one leaf per game or a wave
         if threads > 1:
             self.ctx.wave_config(threads)
-            self._select, self._reply, self._backup = self.ctx.wave_select, self.ctx.wave_reply, self.ctx.wave_backup
-        else:
-            self._select, self._reply, self._backup = self.ctx.sim_select_expand, self.ctx.sim_reply, self.ctx.sim_backup
-        G = n_games * threads                    # evaluator rows: one per game, or game-major one per (game, thread)
+        self._select, self._reply, self._backup = (getattr(self.ctx, name) for name in mode.kernels)
+        G = n_games * mode.rows_per_game         # evaluator rows: one per game, or game-major one per (game, thread)
         # An evaluator that runs the fused HIP trunk takes the encoder's compact form -- 128 plane
         # bitboards (1 KiB) per position -- and expands it on chip: the 16-KiB fp16 planes are then
         # never written to HBM.  Any other evaluator gets the fp16 NHWC planes.
@@ -353,29 +316,21 @@ class LockstepEngine(object):
             self._pick_policy_format()
         else:                                    # (always so with threads > 1) the search reads the full policy vectors
             rows["pri_s1"], rows["pri_s2"] = rows["pol_s1"], rows["pol_s2"]
+        if reply is not None:
+            # the engine owns the per-slot depths and the two accumulators the captured step reads and writes
+            rows["reply_depths"] = torch.full((G,), reply.search_depth, dtype=torch.int32, device=self.dev)
+            rows["reply_nodes"] = torch.zeros((G,), dtype=torch.int64, device=self.dev)
+            rows["reply_cuts"] = torch.zeros((G,), dtype=torch.int32, device=self.dev)
         self._take_rows(G)
         # simulate=Rollouts(...): leaves are valued by random playouts (simulation.py:19-34, the alternative
         # mctree.py:272-274 names) instead of the value head -- a fifth phase that overwrites val_s2.  The
         # tower still runs: its priors are needed.  The engine owns the stream keys (set_stream_keys).
-        self.simulate = simulate
         if simulate is not None:
             self.stream_keys = torch.from_numpy(stream_keys(simulate.seed, G).view(np.int64)).to(self.dev)
             self.roll_results = torch.zeros((G, simulate.repetitions), dtype=torch.int8, device=self.dev)
             self.roll_plies = torch.zeros((G, simulate.repetitions), dtype=torch.int16, device=self.dev)
         # one step: (the stamp in front of a phase when a StampRing is attached, the phase method by name)
-        self._plan = [(STAMP_STEP, "phase_select_expand"), (STAMP_SELECTED, "phase_tower_s1"),
-                      (STAMP_S1_DONE, "phase_reply"), (STAMP_REPLIED, "phase_tower_s2")]
-        if reply is not None:
-            # no tower call on S1: the opponent's search reads the board.  The engine owns the per-slot depths and
-            # the two accumulators the captured step reads and writes.
-            self._plan = [(STAMP_STEP, "phase_select_expand"), (STAMP_S1_DONE, "phase_reply_opponent"),
-                          (STAMP_REPLIED, "phase_tower_s2")]
-            rows["reply_depths"] = torch.full((G,), reply.search_depth, dtype=torch.int32, device=self.dev)
-            rows["reply_nodes"] = torch.zeros((G,), dtype=torch.int64, device=self.dev)
-            rows["reply_cuts"] = torch.zeros((G,), dtype=torch.int32, device=self.dev)
-            self._take_rows(G)
-        if simulate is not None:
-            self._plan.append((STAMP_ROLLOUT, "phase_rollout"))
+        self._plan = mode.plan
         self.use_graph = use_graph
         if steps_per_graph is not None:
             if int(steps_per_graph) < 1:
@@ -395,6 +350,11 @@ class LockstepEngine(object):
         sup = getattr(self.evaluator, "raw_priors_supported", None)
         self.raw_priors = bool(self._want_raw is not False and sup is not None and sup(self.G))
         self.ctx.set_policy_format(_lib.POLICY_LEGAL_RAW if self.raw_priors else _lib.POLICY_LEGAL)
+
+    @property
+    def mode(self):
+        """The ``SearchMode`` of this engine: what kind of step it runs and what that kind covers."""
+        return SearchMode.of(self)
 
     def _bind_stream(self):
         self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
@@ -515,10 +475,8 @@ class LockstepEngine(object):
         on first use, cached beside the plain graphs: switching between the two costs nothing, so a stamped leg can
         follow a timed window without a capture in between).  Stamped graphs write into the ring they were captured
         with: another ring drops them."""
-        if ring is not None and self.threads > 1:
-            raise ValueError("threads > 1 cannot be combined with set_stamps: the stamped step is the one-leaf step")
-        if ring is not None and self.reply is not None:
-            raise ValueError(REPLY_REFUSED["set_stamps"])
+        if ring is not None:
+            self.mode.require("stamps", "set_stamps")
         if ring is not None and ring is not self._stamped_ring:
             self._graphs = {k: g for k, g in self._graphs.items() if not k[1]}
             self._stamped_ring = ring
@@ -624,11 +582,9 @@ class LockstepEngine(object):
     def search_begin(self, keep_root=False):
         """Tree.__init__ for every slot + the root's policy (priors of its children).  ``keep_root``: slots whose
         root ``reroot`` kept go on with that tree (Tree(Node), mctree.py:98-111); the others start a fresh one."""
-        if keep_root and self.reply is not None:
-            raise ValueError(REPLY_REFUSED["keep_root"])
+        if keep_root:
+            self.mode.require("tree_reuse", "keep_root")
         self._bind_stream()
-        if keep_root and self.threads > 1:
-            raise ValueError("threads > 1 cannot be combined with keep_root=True: a wave search starts from a fresh tree")
         if keep_root:
             self.ctx.search_begin_kept(self.planes_s2.data_ptr())
         else:
@@ -686,10 +642,7 @@ class LockstepEngine(object):
     def reroot(self, chosen, next_sims):
         """``advance`` that keeps the chosen child's subtree in every slot where kept nodes + ``next_sims`` fit
         ``max_nodes``; ``search(next_sims, keep_root=True)`` then continues on it."""
-        if self.reply is not None:
-            raise ValueError(REPLY_REFUSED["reroot"])
-        if self.threads > 1:
-            raise ValueError("threads > 1 cannot be combined with reroot: a wave search starts from a fresh tree")
+        self.mode.require("tree_reuse", "reroot")
         if next_sims > self.max_sims:
             raise ValueError("next_sims exceeds the max_sims this engine was created with")
         self._bind_stream()

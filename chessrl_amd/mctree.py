@@ -38,6 +38,7 @@ import numpy as np
 
 from .engine import compute_policy
 from .game import Game, arena, move_to_uci
+from .searchmode import SearchMode
 from . import _lib
 
 
@@ -106,12 +107,7 @@ class Tree(object):
         if eng is None or getattr(eng, "_tree_owner", None) is not src:
             raise RuntimeError("the device tree of this Node is gone: its engine has searched another tree since "
                                "(a Node can be continued only while its tree is the last one searched there)")
-        if getattr(eng, "reply", None) is not None:
-            from .engine import REPLY_REFUSED
-            raise ValueError(REPLY_REFUSED["node"])
-        if getattr(eng, "threads", 1) > 1:
-            raise ValueError("this Node comes from a search with virtual_loss=True and threads > 1: a wave engine starts "
-                             "every search from a fresh tree and cannot continue a Node (construct the tree from the Game)")
+        SearchMode.of(eng).require("tree_reuse", "node")
         if node.reply is None:
             raise ValueError("search_move on a finished game (attempt to get argmax of an empty sequence)")
         nodes, edges, info = eng.ctx.fetch_tree(0)
@@ -138,26 +134,10 @@ class SelfPlayTree(Tree):
         ``chessrl_amd.opponent.MinimaxPlayer``: the built-in opponent's move ("the simulations against stockfish");
         ``Node.reply`` is then that move.  Such a search uses one worker, values leaves by the value head and starts
         from a fresh tree: the combinations are refused as ``LockstepEngine(reply=...)`` refuses them."""
-        if reply is not None:
-            from .engine import REPLY_REFUSED
-            from .opponent import MinimaxPlayer
-            if not isinstance(reply, MinimaxPlayer):
-                raise TypeError("reply must be None or a chessrl_amd.opponent.MinimaxPlayer")
-            if virtual_loss and int(threads) > 1:
-                raise ValueError(REPLY_REFUSED["threads"])
-            if simulate is not None:
-                raise ValueError(REPLY_REFUSED["simulate"])
-            if isinstance(root, Node) and root._tree is not None:
-                raise ValueError(REPLY_REFUSED["node"])
+        self.mode = SearchMode(threads if virtual_loss else 1, simulate, reply, tree=True)
+        if isinstance(root, Node) and root._tree is not None:
+            self.mode.require("tree_reuse", "tree:node")
         self.reply = reply
-        if virtual_loss:
-            if not 1 <= int(threads) <= _lib.WAVE_MAX_THREADS:
-                raise ValueError("threads must lie in [1, %d]" % _lib.WAVE_MAX_THREADS)
-            if simulate is not None and threads > 1:
-                raise ValueError("virtual_loss=True with threads > 1 cannot be combined with rollouts (simulate=Rollouts)")
-            if isinstance(root, Node) and root._tree is not None and threads > 1:
-                raise ValueError("virtual_loss=True with threads > 1 cannot continue a Node: a wave search starts from "
-                                 "a fresh tree (construct the tree from the Game)")
         super().__init__(root)
         self.num_threads = threads
         self.simulate = simulate
@@ -171,12 +151,7 @@ class SelfPlayTree(Tree):
             eng = self._continue_on_device(max_iters)
             eng.search(max_iters, keep_root=True)
         else:
-            if self.reply is not None:
-                eng = agent.engine_for(max_iters, reply=self.reply)
-            elif self.virtual_loss and self.num_threads > 1:
-                eng = agent.engine_for(max_iters, threads=int(self.num_threads))
-            else:
-                eng = agent.engine_for(max_iters, self.simulate) if self.simulate is not None else agent.engine_for(max_iters)
+            eng = agent.engine_for(max_iters, mode=self.mode)
             eng._tree_owner = None
             eng.ctx.copy_game_from(0, arena().ctx, game._slot)
             eng.search(max_iters)

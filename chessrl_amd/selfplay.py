@@ -25,6 +25,7 @@ import numpy as np
 from . import _lib
 from .engine import LockstepEngine, choose_children, dirichlet_row
 from .records import GameRecord
+from .searchmode import COVERS, SearchMode
 
 log = logging.getLogger("chessrl_amd.selfplay")
 
@@ -86,12 +87,10 @@ class SelfPlayRunner(object):
         # threads > 1: every move is searched by `threads` workers per tree in the wave schedule (virtual loss,
         # csrc/search_wave.hpp): a step evaluates up to `threads` leaves per game, a move takes between
         # ceil(sims / threads) and sims steps.  Every search starts from a fresh tree.
-        threads = int(threads)
-        if not 1 <= threads <= _lib.WAVE_MAX_THREADS:
-            raise ValueError("threads must lie in [1, %d]" % _lib.WAVE_MAX_THREADS)
-        if threads > 1 and reuse_tree:
-            raise ValueError("threads > 1 cannot be combined with reuse_tree=True: a wave search starts from a fresh tree")
-        self.threads = threads
+        mode = SearchMode(threads)
+        if reuse_tree:
+            mode.require("tree_reuse", "reuse_tree")
+        self.threads = threads = mode.threads
         # reuse_tree: the subtree below the move that was played is kept for the next search (Tree(Node),
         # mctree.py:98-111) wherever kept nodes + sims fit tree_nodes; every move still runs `sims` NEW
         # simulations for every game.  Off (the default): a fresh tree per move, today's calls exactly.
@@ -755,7 +754,8 @@ def build_parser():
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.virtual_loss and args.reuse_tree:
+    # --virtual-loss asks for the wave kind whatever --threads says
+    if args.reuse_tree and "tree_reuse" not in COVERS["wave" if args.virtual_loss else "leaf"]:
         parser.error("--virtual-loss cannot be combined with --reuse-tree")
     logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO)
 
