@@ -815,6 +815,49 @@ int crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t 
     return crl_sim_reply_opponent_q(ctx, dev_depths_i32, 0, node_limit, dev_planes_s2, dev_nodes_u64, dev_cuts_u32);
 }
 
+// ITERATIVE DEEPENING under a node budget (csrc/opponent.hpp): kernels of their own, so the calls above launch what
+// they launched
+int crl_opponent_moves_id(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
+                          uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
+{
+    ENTER(ctx, depths && moves && node_budget >= 1);
+    if (quiescence < 0 || quiescence > CRL_OPP_MAX_QUIESCENCE)
+        return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves_id: a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
+    const size_t G = ctx->W;
+    for (size_t i = 0; i < G; i++)
+        if (depths[i] < 0 || depths[i] > CRL_OPP_MAX_DEPTH)
+            return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves_id: a depth outside 0 .. CRL_OPP_MAX_DEPTH");
+    long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
+    if (quiescence > 0)
+        LAUNCH(ctx, k_opponent_moves_id_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
+               (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    else
+        LAUNCH(ctx, k_opponent_moves_id, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_budget,
+               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    HIP_TRY(ctx, to_host(ctx, moves, ctx->t_u16a, G));
+    HIP_TRY(ctx, to_host(ctx, scores, ctx->t_i32c, G));
+    HIP_TRY(ctx, to_host(ctx, (long long *)nodes, dnodes, G));
+    HIP_TRY(ctx, to_host(ctx, flags, ctx->t_u8, G));
+    HIP_TRY(ctx, to_host(ctx, depths_done, ctx->t_i32d, G));
+    return check_dev_error(ctx);
+}
+
+int crl_sim_reply_opponent_id(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                              void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                              uint64_t *dev_depth_sum_u64)
+{
+    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
+                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE);
+    if (quiescence > 0)
+        LAUNCH(ctx, k_reply_opponent_id_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    else
+        LAUNCH(ctx, k_reply_opponent_id, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    return CRL_OK;
+}
+
 // ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------------------------
 int crl_wave_config(crl_ctx *ctx, int threads)
 {

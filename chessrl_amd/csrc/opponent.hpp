@@ -73,6 +73,30 @@
 // searches it.  A slot whose game already has a result returns NO_MOVE, score 0, 0 nodes and CRL_OPP_SKIPPED.  With
 // `push`, the chosen move is pushed through game_push: history, record, ply and result change exactly as by
 // crl_push_moves, repetition included.
+//
+// ITERATIVE DEEPENING (the _id kernels only; every other launch is the text above and nothing else).  Per slot:
+// D = depths[slot], now the MAXIMUM depth, 1 .. CRL_OPP_MAX_DEPTH; B >= 1, the node budget of the call; Q as above.
+//     One node counter runs across all iterations of the slot.  It counts wave_movegen calls as above; the root is
+//     generated again at the start of every iteration and counted each time.  The counter is tested before every node:
+//     when it has reached B and the search is not finished, the search stops.
+//     Iteration i = 1 .. D is SEARCH (and QUIESCENCE) to depth i with ONE difference: at the root the best move of
+//     iteration i - 1 is moved to the front of the list, the other root moves keeping generation order (a stable
+//     move-to-front; iteration 1 uses generation order).  Below the root nothing changes: the tactical-first
+//     partition, the victim partition, the strictly-greater rule, fail-soft, the windows.
+//     An iteration that finishes sets (move, score) to its result and depth_done = i.  Iteration D finishing ends the
+//     search; a search that finishes with its last permitted node is not cut.
+//     If the budget stops iteration i: with at least one root move of iteration i searched completely, (move, score)
+//     is the best completely searched root move of iteration i and its score -- the first such move is the previous
+//     iteration's best, so the partial answer is never worse at depth i than the move already held; otherwise (move,
+//     score) of iteration i - 1 stands, and in iteration 1 that is the first legal move with the score -INF, as under
+//     NODE LIMIT.  depth_done stays i - 1.
+//     CRL_OPP_CUT means depth_done < D.  depths[slot] = 0, finished games (CRL_OPP_SKIPPED; depth_done 0) and `push`
+//     are unchanged.
+// The answer is still a function of the board and the settings alone.  Structure: the same frames (an iteration to depth
+// i uses i + 1 of them, or i + Q) and the same main loop, `while (nodes < B)` with one wave_movegen per turn; starting
+// iteration i + 1 is a change of state inside the turn that finished iteration i (ply 0, the full window, the remembered
+// best move), not a loop of its own, so a logic error still ends as a flagged cut.  The move-to-front is one ballot per
+// 64 moves and a shift by one lane.  (tests/iterdeep_util.py restates this section.)
 #pragma once
 #include "search.hpp"
 
@@ -238,21 +262,54 @@ __device__ inline int opp_partition_victim(const Board &b, u16 *mv, int n, int l
     return n - tot[NC - 1];
 }
 
-// The search of the header comment, stated once for both kernels: from `root` to depth D (1 .. OPP_MAX_DEPTH, checked by
+// ITERATIVE DEEPENING, the root's order: the stable move-to-front of `pm` in mv[0 .. n), where it stands at some p --
+// mv[1 .. p] take mv[0 .. p - 1] (each lane its left neighbour's move, lane 0 the last lane's of the 64 moves before)
+// and mv[0] = pm.  A move that is not in the list, or stands in front already, changes nothing.  mv is visible on entry
+// and on return.
+__device__ inline void opp_move_to_front(u16 *mv, int n, u32 pm, int lane)
+{
+    u32 m[4];
+    int p = -1;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int i = c * 64 + lane;
+        m[c] = i < n ? mv[i] : (u32)NO_MOVE;
+        const u64 hit = __ballot(i < n && m[c] == pm);
+        if (hit && p < 0) p = c * 64 + lsb(hit);
+    }
+    if (p <= 0) return;                                // (wave-uniform: p comes from ballots)
+    __syncthreads();                                   // every move read before any is rewritten
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int i = c * 64 + lane;
+        u32 left = __shfl_up(m[c], 1);
+        const u32 carry = c > 0 ? __shfl(m[c > 0 ? c - 1 : 0], 63) : pm;
+        if (lane == 0) left = carry;
+        if (i <= p) mv[i] = (u16)left;                 // i <= p < n
+    }
+    __syncthreads();
+}
+
+// The search of the header comment, stated once for both kernels: from `root` to depth Dmax (1 .. OPP_MAX_DEPTH, checked by
 // the caller) with Q quiescence plies (QS: 1 .. OPP_MAX_QUIESCENCE, checked by the caller; otherwise not read) under the
-// node limit, in the frames f[0 .. D] or, QS, f[0 .. D + Q - 1].  mv: the move (NO_MOVE only for a root without a legal
+// node limit, in the frames f[0 .. Dmax] or, QS, f[0 .. Dmax + Q - 1].  mv: the move (NO_MOVE only for a root without a legal
 // move or with a result, which no caller hands in); score, nodes; done = false is the cut.  Every value is
 // wave-uniform.  The frames are dead on return, but not yet fenced: a barrier comes before their bytes are reused.
-struct OppResult { u32 mv; int score; long long nodes; bool done; };
+// ID: ITERATIVE DEEPENING of the header comment -- Dmax is the maximum depth and `limit` the node budget; the loop below
+// then searches to D = 1, 2, .. Dmax, and depth_done is the last iteration that finished (done: it was Dmax).  Without
+// ID, D = Dmax throughout, depth_done is not set and every line marked ID folds away.
+struct OppResult { u32 mv; int score; long long nodes; bool done; int depth_done; };
 
-template <bool QS>
-__device__ inline OppResult opp_search(const Board &root, int D, int Q, long long limit, OppFrame *f, int lane)
+template <bool QS, bool ID = false>
+__device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long long limit, OppFrame *f, int lane)
 {
     Board b = root;
     int k = 0, a = -OPP_INF, be = OPP_INF, v = 0, root_best = -OPP_INF;
     u32 best_mv = NO_MOVE, first_mv = NO_MOVE;
     bool done = false;
     long long nodes = 0;
+    int D = ID ? 1 : Dmax, depth_done = 0, held_score = -OPP_INF;      // ID: the iteration; what the last whole one gave
+    u32 held_mv = NO_MOVE;
     while (nodes < limit) {
         // ---- enter the node `b` at ply k, window (a, be)
         OppFrame *const F = f + k;                         // (read only where the node searches moves: k < D + Q)
@@ -277,7 +334,10 @@ __device__ inline OppResult opp_search(const Board &root, int D, int Q, long lon
                 best0 = stand;
                 if (stand > a) a = stand;
             } else if (k > 0) opp_partition(b, F->mv, n, lane);
-            else first_mv = (u32)uni((int)F->mv[0]);
+            else {
+                first_mv = (u32)uni((int)F->mv[0]);
+                if (ID && held_mv != NO_MOVE) opp_move_to_front(F->mv, n, held_mv, lane);
+            }
             if (QS && cnt == 0) v = stand;                 // 4c without a tactical move (cnt = n > 0 everywhere else)
             else {
                 if (lane == 0) { F->b = b; F->cur = 0; F->n = cnt; F->alpha = a; F->beta = be; F->best = best0; }
@@ -286,8 +346,25 @@ __device__ inline OppResult opp_search(const Board &root, int D, int Q, long lon
             }
         }
         // ---- hand v up: every turn lowers k, so at most d + Q + 1 of them
+        bool again = false;                                // ID: this turn finished an iteration below Dmax
         while (have_v) {
-            if (k == 0) { done = true; break; }
+            if (k == 0) {
+                if (ID) {
+                    held_mv = best_mv; held_score = v; depth_done = D;
+                    // the next iteration: ply 0, the full window, no best yet.  (A root that searched a move wrote its
+                    // frame, so the root's board is read back from there; one with a result -- no caller hands one in
+                    // -- searched none and ends here as it does without ID.)
+                    if (D < Dmax && best_mv != NO_MOVE) {
+                        D++;
+                        b = uni_board(f[0].b); a = -OPP_INF; be = OPP_INF;
+                        best_mv = NO_MOVE; root_best = -OPP_INF;
+                        again = true;
+                        break;
+                    }
+                }
+                done = true;
+                break;
+            }
             k--;
             OppFrame &P = f[k];
             const int sc = -v, pn = uni(P.n), pb = uni(P.beta);
@@ -305,6 +382,7 @@ __device__ inline OppResult opp_search(const Board &root, int D, int Q, long lon
             else v = best;                                 // exhausted or cut: it returns its best
         }
         if (done) break;
+        if (ID && again) continue;                         // (the budget is tested before the new root like any node)
         // ---- descend: the next move of frame k  (k < D + Q: a frame with moves to search is above the last ply)
         OppFrame &P = f[k];
         const u32 mv = (u32)uni((int)P.mv[uni(P.cur)]);
@@ -314,18 +392,25 @@ __device__ inline OppResult opp_search(const Board &root, int D, int Q, long lon
         k++;
     }
     OppResult o;
-    o.mv = done || best_mv != NO_MOVE ? best_mv : first_mv;
-    o.score = done ? v : root_best;
+    if (ID && !done && best_mv == NO_MOVE && depth_done > 0) {             // a cut iteration without a whole root move
+        o.mv = held_mv;
+        o.score = held_score;
+    } else {
+        o.mv = done || best_mv != NO_MOVE ? best_mv : first_mv;
+        o.score = done ? v : root_best;
+    }
     o.nodes = nodes;
     o.done = done;
+    o.depth_done = depth_done;
     return o;
 }
 
-// One slot of k_opponent_moves / k_opponent_moves_q.  Window-relative rows: depths / moves / scores / nodes_out /
-// flags [count]
-template <bool QS>
+// One slot of k_opponent_moves / k_opponent_moves_q and, ID, of their _id forms.  Window-relative rows: depths / moves /
+// scores / nodes_out / flags [count] and, ID only, depths_done [count]
+template <bool QS, bool ID = false>
 __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, int push, long long limit, u16 *moves,
-                                           int32_t *scores, long long *nodes_out, uint8_t *flags, OppLds<QS> &s)
+                                           int32_t *scores, long long *nodes_out, uint8_t *flags, OppLds<QS> &s,
+                                           int32_t *depths_done = nullptr)
 {
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
     int D = uni(depths[r]);
@@ -333,16 +418,20 @@ __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, 
     if (Q > OPP_MAX_QUIESCENCE) Q = OPP_MAX_QUIESCENCE;    //  and such a Q)
     const bool skipped = D > 0 && uni(d.game[g].game_result) != RESULT_NONE;
     if (D <= 0 || skipped) {
-        if (lane == 0) { moves[r] = NO_MOVE; scores[r] = 0; nodes_out[r] = 0; flags[r] = skipped ? OPP_SKIPPED : 0; }
+        if (lane == 0) {
+            moves[r] = NO_MOVE; scores[r] = 0; nodes_out[r] = 0; flags[r] = skipped ? OPP_SKIPPED : 0;
+            if (ID) depths_done[r] = 0;
+        }
         return;
     }
     const Board root = uni_board(d.cur[g]);
-    const OppResult o = opp_search<QS>(root, D, Q, limit, s.f, lane);
+    const OppResult o = opp_search<QS, ID>(root, D, Q, limit, s.f, lane);
     if (lane == 0) {
         moves[r] = (u16)o.mv;
         scores[r] = o.score;
         nodes_out[r] = o.nodes;
-        flags[r] = o.done ? 0 : OPP_CUT;
+        flags[r] = o.done ? 0 : OPP_CUT;                   // (ID: done = the iteration to depth D finished)
+        if (ID) depths_done[r] = o.depth_done;
     }
     if (push && o.mv != NO_MOVE) {
         __syncthreads();                                   // the frames are dead: s.w takes their bytes
@@ -367,14 +456,34 @@ __global__ __launch_bounds__(64) void k_opponent_moves_q(Dev d, const int32_t *d
     opponent_moves_slot<true>(d, depths, Q, push, limit, moves, scores, nodes_out, flags, s);
 }
 
+// ITERATIVE DEEPENING under the node budget: depths[] are maximum depths, depths_done [count] the completed ones.  Kernels
+// of their own, so a launch without a budget runs the code it ran.
+__global__ __launch_bounds__(64) void k_opponent_moves_id(Dev d, const int32_t *depths, int push, long long budget,
+                                                          u16 *moves, int32_t *scores, long long *nodes_out,
+                                                          uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<false> s;
+    opponent_moves_slot<false, true>(d, depths, 0, push, budget, moves, scores, nodes_out, flags, s, depths_done);
+}
+
+__global__ __launch_bounds__(64) void k_opponent_moves_id_q(Dev d, const int32_t *depths, int Q, int push,
+                                                            long long budget, u16 *moves, int32_t *scores,
+                                                            long long *nodes_out, uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<true> s;
+    opponent_moves_slot<true, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s, depths_done);
+}
+
 // expand, the opponent's half (mctree.py:244-246) with the built-in opponent as the mover (gamestockfish.py:27-41):
 // the reply stored for S1 is the move k_opponent_moves plays from S1 -- it reads the board alone, so the tree holds the
 // real opponent's reply.  Rows as k_reply: one whose pending leaf is not LEAF_NEW_REPLY only clears lab_n2.  The root
 // order of the search is wave_movegen's (s1_moves is not read).  A cut reply is a move like any other.  nodes_acc /
-// cuts_acc [count], window-relative: this wave owns its row, so lane 0 adds with a plain load and store.
-template <bool QS>
+// cuts_acc [count], window-relative: this wave owns its row, so lane 0 adds with a plain load and store.  ID: the
+// search is ITERATIVE DEEPENING under the budget `limit`, and depth_acc [count] sums the completed depths.
+template <bool QS, bool ID = false>
 __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, long long limit, void *planes2,
-                                          unsigned long long *nodes_acc, uint32_t *cuts_acc, OppLds<QS> &s)
+                                          unsigned long long *nodes_acc, uint32_t *cuts_acc, OppLds<QS> &s,
+                                          unsigned long long *depth_acc = nullptr)
 {
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
     if (lane == 0) d.lab_n2[r] = 0;                     // no policy(S2) wanted unless a new node gets priors
@@ -386,11 +495,12 @@ __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, l
     }
     const int c = uni(d.game[g].leaf_node);
     const Board s1 = uni_board(d.node[(size_t)g * d.N + c].s1);
-    const OppResult o = opp_search<QS>(s1, D, Q, limit, s.f, lane);
+    const OppResult o = opp_search<QS, ID>(s1, D, Q, limit, s.f, lane);
     if (o.mv == NO_MOVE) { dev_error(d, DERR_STATE); return; }              // S1 is running: it has a legal move
     if (lane == 0) {
         nodes_acc[r] += (unsigned long long)o.nodes;
         if (!o.done) cuts_acc[r] += 1u;
+        if (ID) depth_acc[r] += (unsigned long long)o.depth_done;
     }
     __syncthreads();                                       // the frames are dead: s.w takes their bytes
     reply_tail(d, g, r, lane, s.w, c, uni(d.game[g].path_len), uni(d.game[g].ply), s1, o.mv,
@@ -410,6 +520,22 @@ __global__ __launch_bounds__(64) void k_reply_opponent_q(Dev d, const int32_t *d
 {
     __shared__ OppLds<true> s;
     reply_opponent_row<true>(d, depths, Q, limit, planes2, nodes_acc, cuts_acc, s);
+}
+
+__global__ __launch_bounds__(64) void k_reply_opponent_id(Dev d, const int32_t *depths, long long budget, void *planes2,
+                                                          unsigned long long *nodes_acc, uint32_t *cuts_acc,
+                                                          unsigned long long *depth_acc)
+{
+    __shared__ OppLds<false> s;
+    reply_opponent_row<false, true>(d, depths, 0, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
+}
+
+__global__ __launch_bounds__(64) void k_reply_opponent_id_q(Dev d, const int32_t *depths, int Q, long long budget,
+                                                            void *planes2, unsigned long long *nodes_acc,
+                                                            uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<true> s;
+    reply_opponent_row<true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
 }
 
 }  // namespace crl

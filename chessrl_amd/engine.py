@@ -234,7 +234,8 @@ class LockstepEngine(object):
 
     ``reply``: None -- the reply stored in a node is the net's greedy move -- or a ``chessrl_amd.opponent.MinimaxPlayer``:
     the built-in opponent's move, searched with the player's ``search_depth``, ``quiescence`` and ``node_limit`` (its colour is
-    ignored: the side to move after our move replies).
+    ignored: the side to move after our move replies).  A player with a ``node_budget`` replies by iterative deepening
+    under that budget (csrc/opponent.hpp ``k_reply_opponent_id``); one without launches the fixed-depth kernel as before.
     """
 
     def __init__(self, evaluator, n_games, max_sims, device=0, max_plies=4096,
@@ -321,6 +322,8 @@ class LockstepEngine(object):
             rows["reply_depths"] = torch.full((G,), reply.search_depth, dtype=torch.int32, device=self.dev)
             rows["reply_nodes"] = torch.zeros((G,), dtype=torch.int64, device=self.dev)
             rows["reply_cuts"] = torch.zeros((G,), dtype=torch.int32, device=self.dev)
+            if reply.node_budget is not None:    # iterative deepening: the sum of the depths the replies completed
+                rows["reply_depth_sum"] = torch.zeros((G,), dtype=torch.int64, device=self.dev)
         self._take_rows(G)
         # simulate=Rollouts(...): leaves are valued by random playouts (simulation.py:19-34, the alternative
         # mctree.py:272-274 names) instead of the value head -- a fifth phase that overwrites val_s2.  The
@@ -412,9 +415,11 @@ class LockstepEngine(object):
 
     def phase_reply_opponent(self):
         """Only with ``reply``: the built-in opponent's move from S1 becomes the node's reply."""
+        budget = self.reply.node_budget
         self.ctx.sim_reply_opponent(self.reply_depths.data_ptr(), self.reply.node_limit, self.planes_s2.data_ptr(),
                                     self.reply_nodes.data_ptr(), self.reply_cuts.data_ptr(),
-                                    quiescence=self.reply.quiescence)
+                                    quiescence=self.reply.quiescence, node_budget=budget,
+                                    dev_depth_sum=None if budget is None else self.reply_depth_sum.data_ptr())
 
     def phase_tower_s2(self):
         if self.legal_priors:
@@ -455,10 +460,15 @@ class LockstepEngine(object):
 
     def reply_stats(self):
         """(nodes int64 [G], cuts int32 [G]) as numpy: what the opponent's replies of the current search cost per
-        slot -- nodes searched and replies ended by the node limit (synchronises)."""
+        slot -- nodes searched and replies ended by the node limit (synchronises).  A ``reply`` with a ``node_budget``
+        adds a third array, depth sums int64 [G]: the completed depths of the replies, summed (a cut reply is then one
+        that did not complete its maximum depth)."""
         if self.reply is None:
             raise ValueError("reply_stats: the engine was created without reply")
-        return self.reply_nodes.cpu().numpy(), self.reply_cuts.cpu().numpy()
+        out = (self.reply_nodes.cpu().numpy(), self.reply_cuts.cpu().numpy())
+        if self.reply.node_budget is not None:
+            out += (self.reply_depth_sum.cpu().numpy(),)
+        return out
 
     def _step_body(self):
         # with a StampRing attached this is the measurement build of the same step (bench.py): a one-thread stamp
@@ -594,6 +604,8 @@ class LockstepEngine(object):
         if self.reply is not None:
             self.reply_nodes.zero_()
             self.reply_cuts.zero_()
+            if self.reply.node_budget is not None:
+                self.reply_depth_sum.zero_()
 
     def search(self, n_sims, keep_root=False):
         """search_begin + n_sims lockstep simulations + the last backprop.  A kept tree that would not fit n_sims

@@ -55,12 +55,15 @@ def side_depths(draws, white_to_move):
 
 
 def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512,
-             quiescence=0):
+             quiescence=0, node_budget=None):
     """Plays ``num_games`` games, saves the finished ones to ``save_path`` (appending to what the file holds, as
     ``DatasetGame.save`` does) and returns the ``DatasetGame`` it saved.  The reference's ``gen_data`` forgets to
     pass ``depth`` and ``random_dep`` on to ``play_game`` (gen_data_stockfish.py:44-49); here both are honoured.
     ``workers`` is accepted and ignored; a game still running after ``max_plies`` plies is dropped.  ``quiescence``:
-    the quiescence plies of both sides past their depths (0 .. CRL_OPP_MAX_QUIESCENCE; 0: none)."""
+    the quiescence plies of both sides past their depths (0 .. CRL_OPP_MAX_QUIESCENCE; 0: none).  ``node_budget``
+    (None: none): both sides deepen iteratively up to their depths and stop at that many nodes per move."""
+    if node_budget is not None and int(node_budget) < 1:
+        raise ValueError("node_budget must be None or at least 1")
     quiescence = int(quiescence)
     if not 0 <= quiescence <= _lib.OPP_MAX_QUIESCENCE:
         raise ValueError("quiescence must lie in [0, %d]" % _lib.OPP_MAX_QUIESCENCE)
@@ -87,7 +90,7 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
             if not running.any():
                 break
             ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True,
-                               quiescence=quiescence)
+                               quiescence=quiescence, node_budget=node_budget)
             results = ctx.results()
         moves, plies, results = ctx.records()
     finally:
@@ -109,6 +112,8 @@ def main(argv=None):
     p.add_argument("--depth", metavar="depth", type=int, default=1, help="Search depth of the built-in opponent.")
     p.add_argument("--quiescence", type=int, default=0,
                    help="Quiescence plies of the built-in opponent past its depth, both sides (0-6; 0: none).")
+    p.add_argument("--nodes", type=int, default=None,
+                   help="Node budget per move, both sides: iterative deepening up to the depth (default: none).")
     p.add_argument("--random_depth", action="store_true", default=False,
                    help="Use normal distribution of depths with mean --depth.")
     p.add_argument("--debug", action="store_true", default=False, help="Log debug messages on screen. Default false.")
@@ -117,7 +122,8 @@ def main(argv=None):
     a = p.parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if a.debug else logging.INFO)
     gen_data(a.data_path, num_games=a.games, depth=a.depth, random_dep=a.random_depth,
-             opening_plies=a.opening_plies, seed=a.seed, quiescence=a.quiescence)
+             opening_plies=a.opening_plies, seed=a.seed, quiescence=a.quiescence,
+             node_budget=a.nodes)
 
 
 if __name__ == "__main__":

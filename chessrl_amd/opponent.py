@@ -7,7 +7,9 @@ package; what stands in its place is the fixed-depth alpha-beta player of ``csrc
 one wavefront per game on the GPU.  It is NOT Stockfish: no repetition below the root, no time
 control, and no Elo is claimed -- a result reads "against the built-in depth-d opponent".  Past the
 fixed depth it can search ``quiescence`` plies of captures, promotions and check evasions
-(opponent.hpp, QUIESCENCE); 0, the default, is the fixed-depth search alone.  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
+(opponent.hpp, QUIESCENCE); 0, the default, is the fixed-depth search alone.  With ``node_budget`` it deepens
+iteratively up to ``search_depth`` and stops at that many nodes per move (opponent.hpp, ITERATIVE DEEPENING): the
+deterministic counterpart of the reference's ``Limit(time=...)`` (stockfish.py:14-21).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
 these classes are the one-game drop-in surface over it.
 """
 import numpy as np
@@ -29,9 +31,11 @@ def clamp_depth(depth):
 class MinimaxPlayer(Player):
     """Mirror of ``Stockfish(Player)``: ``best_move(game)`` is the UCI string of the depth-``search_depth``
     alpha-beta move for a ``chessrl_amd.Game`` (``'00000'`` on a finished game), with ``quiescence`` plies of
-    quiescence search past that depth."""
+    quiescence search past that depth.  ``node_budget`` (None: no budget, the fixed-depth search): iterative deepening
+    with ``search_depth`` as the maximum depth under ``min(node_budget, node_limit)`` nodes per move; ``last_depth`` is
+    then the depth the last search completed (None without a budget)."""
 
-    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0):
+    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0, node_budget=None):
         super().__init__(color)
         if not 1 <= int(search_depth) <= MAX_DEPTH:
             raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
@@ -41,16 +45,22 @@ class MinimaxPlayer(Player):
             raise ValueError("quiescence must lie in [0, %d]" % MAX_QUIESCENCE)
         self.search_depth = int(search_depth)
         self.quiescence = int(quiescence)
+        if node_budget is not None and int(node_budget) < 1:
+            raise ValueError("node_budget must be None or at least 1")
         self.node_limit = int(node_limit)
+        self.node_budget = None if node_budget is None else int(node_budget)
         self.last = None                      # (score, nodes, flag) of the last search
+        self.last_depth = None                # with a budget: the depth that search completed
 
     def best_move(self, game):
         if game._slot is None:
             raise RuntimeError("Game was freed")
         ctx = arena().one(game._slot)
-        moves, scores, nodes, flags = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False,
-                                                         node_limit=self.node_limit, quiescence=self.quiescence)
+        out = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False, node_limit=self.node_limit,
+                                 quiescence=self.quiescence, node_budget=self.node_budget)
+        moves, scores, nodes, flags = out[:4]
         self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
+        self.last_depth = int(out[4][0]) if self.node_budget is not None else None
         if int(moves[0]) == _lib.NO_MOVE:
             return Game.NULL_MOVE
         return move_to_uci(moves[0])
@@ -61,18 +71,18 @@ class MinimaxPlayer(Player):
 
 class GameOpponent(Game):
     """Mirror of ``GameStockfish``: a game against the built-in opponent.  ``opponent``: a ``MinimaxPlayer``, or
-    None for one of depth ``opponent_depth`` and ``opponent_quiescence`` with the colour opposite to
-    ``player_color``."""
+    None for one of depth ``opponent_depth``, ``opponent_quiescence`` and ``opponent_budget`` (the player's
+    ``node_budget``) with the colour opposite to ``player_color``."""
 
     def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2,
-                 opponent_quiescence=0):
+                 opponent_quiescence=0, opponent_budget=None):
         if opponent is not None and not isinstance(opponent, MinimaxPlayer):
             raise ValueError("opponent must be a MinimaxPlayer or None")
         self.opponent = None                  # (a board's move stack is replayed by plain Game.move)
         super().__init__(board=board, player_color=player_color, date=date)
         if opponent is None:
             opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth,
-                                     quiescence=opponent_quiescence)
+                                     quiescence=opponent_quiescence, node_budget=opponent_budget)
         self.opponent = opponent
 
     def move(self, movement):

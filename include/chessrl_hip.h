@@ -311,6 +311,23 @@ int  crl_opponent_moves_q(crl_ctx *ctx, const int32_t *depths /*G*/, int quiesce
                           uint16_t *moves /*G*/, int32_t *scores /*G*/, int64_t *nodes /*G*/, uint8_t *flags /*G*/);
 int  crl_sim_reply_opponent_q(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_limit,
                               void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32);
+/* The two _q calls with ITERATIVE DEEPENING under a node budget (csrc/opponent.hpp states the rule), the deterministic
+ * counterpart of the reference's Limit(time=...) (stockfish.py:14-21).  depths[g] is now the MAXIMUM depth of slot g:
+ * the slot searches depth 1, 2, ... with one node counter, the best move of an iteration first at the root of the
+ * next, and stops when the counter reaches node_budget >= 1, so no slot costs more than node_budget nodes.  It plays
+ * the result of the deepest iteration it finished, or the best completely searched root move of the iteration the
+ * budget stopped; depths_done[g] (host int32 / dev_depth_sum_u64[row] accumulates it) is the last finished iteration,
+ * and CRL_OPP_CUT means depths_done[g] < depths[g].  Everything else -- depth 0, finished games, push, quiescence,
+ * the node and cut accumulators, the stored reply -- is as in the calls above; depths_done may be NULL.  The calls
+ * above do not change: they launch the kernels they launched.
+ * CRL_ERR_ARG: what the calls above refuse (NULL dev_depth_sum_u64 included), with node_budget in node_limit's place.
+ * No state changes on an error. */
+int  crl_opponent_moves_id(crl_ctx *ctx, const int32_t *depths /*G*/, int quiescence, int push, int64_t node_budget,
+                           uint16_t *moves /*G*/, int32_t *scores /*G*/, int64_t *nodes /*G*/, uint8_t *flags /*G*/,
+                           int32_t *depths_done /*G*/);
+int  crl_sim_reply_opponent_id(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                               uint64_t *dev_depth_sum_u64);
 
 /* ---- threads > 1: virtual-loss waves of simulations per game (csrc/search_wave.hpp) --------------------------
  * The reference runs `threads` explore_tree workers on one tree, kept apart by a virtual loss (mctree.py:12,173-176,

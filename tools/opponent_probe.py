@@ -3,12 +3,16 @@
 
     python tools/opponent_probe.py [--games 4096] [--opening-plies 6] [--node-limit 200000] [--out profiles/opponent_probe.json]
     python tools/opponent_probe.py --quiescence 2,4,6 --depths 1,2 --out profiles/opponent_probe_q.json
+    python tools/opponent_probe.py --budget 150,300,600,1500 --depths 2,3 --max-depth 3
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words), so the slots hold
 different positions.  Per depth, in depth order: one warm-up launch, then three timed ones (host wall time around the
 synchronous call, copies included); the median is reported.  Nothing is pushed, so every launch searches the same
 positions.  --quiescence Q[,Q..]: the same per quiescence (opponent.hpp QUIESCENCE), keyed "<depth>+q<Q>"; 0, the
-default, is the fixed-depth search and leaves the output as it was.  No threshold: this is a measurement.
+default, is the fixed-depth search and leaves the output as it was.  --budget B[,B..]: after the fixed depths, on the
+same games in the same process, iterative deepening up to --max-depth under each node budget (opponent.hpp ITERATIVE
+DEEPENING), keyed "<=<depth>@<B>[+q<Q>]", with the histogram of the completed depths; the output then goes to
+profiles/opponent_probe_id.json unless --out names another file.  No threshold: this is a measurement.
 """
 import argparse
 import json
@@ -29,8 +33,13 @@ def main():
     ap.add_argument("--node-limit", type=int, default=200000)
     ap.add_argument("--depths", default="1,2,3")
     ap.add_argument("--quiescence", default="0")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "opponent_probe.json"))
+    ap.add_argument("--budget", default="", help="node budgets of the iterative-deepening launches (default: none)")
+    ap.add_argument("--max-depth", type=int, default=3, help="maximum depth of the --budget launches")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    budgets = [int(b) for b in args.budget.split(",") if b]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "opponent_probe_id.json" if budgets else "opponent_probe.json")
     import numpy as np
     from chessrl_amd import _lib
     from chessrl_amd.gen_data import opening_words
@@ -40,15 +49,18 @@ def main():
     played, _, _ = ctx.rollout_games(words, np.full(G, words.shape[1], np.int32), 1, args.opening_plies)
     out = {"games": G, "opening_plies": args.opening_plies, "mean_opening_plies": float(played.mean()),
            "node_limit": args.node_limit, "running": int((ctx.results() == _lib.RESULT_NONE).sum()), "depths": {}}
-    cases = [(int(d), int(q)) for q in args.quiescence.split(",") for d in args.depths.split(",")]
-    for depth, quiescence in cases:
+    cases = [(int(d), int(q), None) for q in args.quiescence.split(",") for d in args.depths.split(",")]
+    cases += [(args.max_depth, int(q), b) for q in args.quiescence.split(",") for b in budgets]
+    for depth, quiescence, budget in cases:
         row = np.full(G, depth, np.int32)
-        key = str(depth) if quiescence == 0 else "%d+q%d" % (depth, quiescence)
+        key = (str(depth) if budget is None else "<=%d@%d" % (depth, budget)) + ("+q%d" % quiescence if quiescence else "")
         kw = {"quiescence": quiescence} if quiescence else {}
+        if budget is not None:
+            kw["node_budget"] = budget
         times = []
         for i in range(4):
             t0 = time.perf_counter()
-            moves, scores, nodes, flags = ctx.opponent_moves(row, node_limit=args.node_limit, **kw)
+            moves, scores, nodes, flags = ctx.opponent_moves(row, node_limit=args.node_limit, **kw)[:4]
             if i:
                 times.append(time.perf_counter() - t0)
         t = statistics.median(times)
@@ -58,6 +70,9 @@ def main():
             "seconds": times, "ms_per_launch": 1e3 * t, "nodes": total, "nodes_per_slot_mean": float(nodes[searched].mean()),
             "nodes_per_slot_max": int(nodes.max()), "nodes_per_s": total / t, "us_per_node_of_the_longest_slot":
             1e6 * t / max(int(nodes.max()), 1), "cut_share": float((flags == _lib.OPP_CUT).mean())}
+        if budget is not None:
+            done = ctx.opponent_moves(row, node_limit=args.node_limit, **kw)[4]
+            out["depths"][key]["depth_done_histogram"] = np.bincount(done[searched], minlength=depth + 1).tolist()
         print(key, json.dumps(out["depths"][key]), flush=True)
     ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -5,13 +5,17 @@ tower call + the alpha-beta search), over the same games and weights in one proc
 
     python tools/reply_probe.py [--games 4096] [--opening-plies 6] [--towers 10x128:f16] [--depths 1,2]
                                 [--steps 32] [--windows 3] [--out profiles/reply_probe.json]
+                                [--budget 150,300,600 [--max-depth 3]]
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words: the same games in every
 engine).  All engines live side by side; after ``search_begin`` and 8 warm-up steps each (graphs captured before),
 the timed windows alternate between them: a window is ``run_steps(--steps)`` between two synchronisations, host
 clock; the median window is reported.  The trees grow alike in all engines, so window k compares like with like.
 Then one more step with cleared accumulators gives the nodes per reply (mean / max over the slots that needed one)
-and the cuts; the accumulators over the whole run give the mean per slot and step.  No threshold: a measurement.
+and the cuts; the accumulators over the whole run give the mean per slot and step.  --budget B[,B..] adds one engine
+per node budget, ``reply=MinimaxPlayer(search_depth=--max-depth, node_budget=B)`` (iterative deepening:
+k_reply_opponent_id), with the histogram of the completed depths of the last step's replies; such a run is stored as the
+block "node_budget" of the output file, whose other content stays.  No threshold: a measurement.
 """
 import argparse
 import json
@@ -34,8 +38,11 @@ def main():
     ap.add_argument("--depths", default="1,2")
     ap.add_argument("--steps", type=int, default=32, help="steps per timed window")
     ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--budget", default="", help="node budgets of the iterative-deepening engines (default: none)")
+    ap.add_argument("--max-depth", type=int, default=3, help="maximum depth of the --budget engines")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reply_probe.json"))
     args = ap.parse_args()
+    budgets = [int(b) for b in args.budget.split(",") if b]
     import numpy as np
     import torch
     from chessrl_amd import _lib
@@ -55,6 +62,9 @@ def main():
         engines = {"net reply": LockstepEngine(model, G, sims)}
         for depth in (int(x) for x in args.depths.split(",")):
             engines["depth %d" % depth] = LockstepEngine(model, G, sims, reply=MinimaxPlayer(False, search_depth=depth))
+        for b in budgets:
+            engines["depth <= %d within %d" % (args.max_depth, b)] = LockstepEngine(
+                model, G, sims, reply=MinimaxPlayer(False, search_depth=args.max_depth, node_budget=b))
         for eng in engines.values():
             eng.ctx.rollout_games(words, np.full(G, words.shape[1], np.int32), 1, args.opening_plies)
             eng.search_begin()
@@ -77,21 +87,36 @@ def main():
                        "sims_per_s": G / ms * 1e3}
             if eng.reply is not None:
                 done = WARM + args.windows * steps
-                nodes, cuts = eng.reply_stats()
+                nodes, cuts = eng.reply_stats()[:2]
                 rows[k]["nodes_per_slot_and_step_mean"] = float(nodes.sum()) / (G * done)
                 rows[k]["cuts"] = int(cuts.sum())
                 eng.reply_nodes.zero_()
                 eng.reply_cuts.zero_()
+                budgeted = eng.reply.node_budget is not None
+                if budgeted:
+                    rows[k]["depth_done_per_slot_and_step_mean"] = float(eng.reply_stats()[2].sum()) / (G * done)
+                    eng.reply_depth_sum.zero_()
                 eng.run_steps(1)
                 eng.ctx.sync()
-                nodes, cuts = eng.reply_stats()
+                stats = eng.reply_stats()
+                nodes, cuts = stats[:2]
                 replied = nodes > 0
                 rows[k]["last_step"] = {"replies": int(replied.sum()), "nodes_per_reply_mean": float(nodes[replied].mean()),
                                         "nodes_per_reply_max": int(nodes.max()), "cuts": int(cuts.sum())}
+                if budgeted:                     # one reply per slot in this step: the sum is that reply's depth
+                    rows[k]["last_step"]["depth_done_histogram"] = np.bincount(
+                        stats[2][replied], minlength=eng.reply.search_depth + 1).tolist()
             print(spec, k, json.dumps(rows[k]), flush=True)
             eng.close()
         out["towers"][spec] = {"precision": str(getattr(model, "precision", precision)), "running_games": running,
                                "engines": rows}
+    if budgets:                                  # an added block: what the file holds stays
+        kept = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                kept = json.load(f)
+        kept["node_budget"] = dict(out, budgets=budgets, max_depth=args.max_depth)
+        out = kept
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
