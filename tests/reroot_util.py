@@ -39,8 +39,11 @@ def new_root(game):
 
 
 def grow(root, agent, iters, mode):
-    """``iters`` more explore_tree calls on the tree below ``root`` (mcts_oracle.search's loop body)."""
-    for _ in range(iters):
+    """``iters`` more explore_tree calls on the tree below ``root`` (mcts_oracle.search's loop body).  An agent with
+    a ``sim`` attribute (tests.rollout_util.RolloutAgent) is told the 0-based index of every simulation."""
+    for i in range(iters):
+        if hasattr(agent, "sim"):
+            agent.sim = i
         node = root
         while node.result is None:
             if node.todo:

@@ -155,22 +155,29 @@ def mean_values(results):
 class RolloutAgent(mcts_oracle.OracleAgent):
     """OracleAgent whose predict_outcome is the mean of ``repetitions`` private playouts of the leaf, keyed as the
     device keys them: the slot's stream key, len(leaf game), the 0-based index of the simulation, the
-    repetition.  ``mcts_oracle.search`` does not hand the simulation index to its agent -- simulations that end
-    on a terminal node do not call it at all -- so it is read from the caller's frame (the loop variable ``_``
-    of ``search``); test infrastructure only."""
+    repetition.  A loop that knows the index sets ``sim`` before every simulation (``tests.reroot_util.grow``).
+    ``mcts_oracle.search`` does not hand the simulation index to its agent -- simulations that end on a terminal
+    node do not call it at all -- so while ``sim`` is None it is read from the caller's frame (the loop variable
+    ``_`` of ``search``); test infrastructure only.  ``reasons`` logs how every playout ended (``end_reason`` or
+    "cut"), in the order played."""
 
     def __init__(self, net, key, repetitions, max_moves, **kw):
         super().__init__(net, **kw)
         self.key, self.repetitions, self.max_moves = int(key), int(repetitions), int(max_moves)
         self.n_rollouts = 0
+        self.sim = None
+        self.reasons = []
 
     def predict_outcome(self, game):
-        frame = sys._getframe(1)
-        assert frame.f_code.co_name == "search", frame.f_code.co_name
-        sim = frame.f_locals["_"]
-        res = np.array([[playout(game, self.key, sim, r, self.max_moves)[0] for r in range(self.repetitions)]], np.int8)
+        sim = self.sim
+        if sim is None:
+            frame = sys._getframe(1)
+            assert frame.f_code.co_name == "search", frame.f_code.co_name
+            sim = frame.f_locals["_"]
+        outs = [playout(game, self.key, sim, r, self.max_moves) for r in range(self.repetitions)]
+        self.reasons.extend(o[2] for o in outs)
         self.n_rollouts += 1
-        return float(mean_values(res)[0])
+        return float(mean_values(np.array([[o[0] for o in outs]], np.int8))[0])
 
 
 def random_prefix(n_plies, seed):

@@ -126,14 +126,12 @@ def test_search_matches_oracle(mode, shift, quant, sims, graph):
     eng.close()
 
 
-def test_search_on_long_games_with_high_halfmove_clocks():
-    """Roots 120-260 plies deep: large halfmove clocks, so the tree meets the fifty-move claim
-    (terminal nodes inside the tree) and runs the repetition scan over tree path + game ring."""
-    from chessrl_amd.engine import LockstepEngine
-    G, sims = 10, 120
-    rng = np.random.default_rng(77)
+def long_quiet_games(n, seed=77):
+    """n running games of 120, 134, ... plies that shuffle pieces (non-pawn, non-capturing moves preferred): large
+    halfmove clocks.  Game i does not depend on n."""
+    rng = np.random.default_rng(seed)
     games = []
-    while len(games) < G:                      # shuffle pieces: prefer non-pawn, non-capturing moves
+    while len(games) < n:
         g = OracleGame()
         want = 120 + 14 * len(games)
         while len(g) < want and g.get_result() is None:
@@ -147,6 +145,15 @@ def test_search_on_long_games_with_high_halfmove_clocks():
             g.move(move_to_uci(pool[int(rng.integers(len(pool)))]))
         if g.get_result() is None:
             games.append(g)
+    return games
+
+
+def test_search_on_long_games_with_high_halfmove_clocks():
+    """Roots 120-260 plies deep: large halfmove clocks, so the tree meets the fifty-move claim
+    (terminal nodes inside the tree) and runs the repetition scan over tree path + game ring."""
+    from chessrl_amd.engine import LockstepEngine
+    G, sims = 10, 120
+    games = long_quiet_games(G)
     clocks = [(int(g.board_at(0).state) >> 12) & 255 for g in games]
     assert max(clocks) >= 40
     net = FakeNet(seed=41, prior_shift=31)
