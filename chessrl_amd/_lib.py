@@ -66,6 +66,7 @@ SYMBOLS = [
     "crl_im2col3x3_f32", "crl_col2im3x3_f32", "crl_stamp", "crl_stamp_clock_khz",
     "crl_rollout_games", "crl_rollout", "crl_opponent_moves", "crl_sim_reply_opponent",
     "crl_opponent_moves_q", "crl_sim_reply_opponent_q", "crl_opponent_moves_id", "crl_sim_reply_opponent_id",
+    "crl_opponent_moves_ord", "crl_sim_reply_opponent_ord",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
 ]
@@ -244,6 +245,8 @@ def lib():
     L.crl_sim_reply_opponent_q.argtypes = [vp, vp, i32, ctypes.c_int64, vp, vp, vp]
     L.crl_opponent_moves_id.argtypes = [vp, vp, i32, i32, ctypes.c_int64, vp, vp, vp, vp, vp]
     L.crl_sim_reply_opponent_id.argtypes = [vp, vp, i32, ctypes.c_int64, vp, vp, vp, vp]
+    L.crl_opponent_moves_ord.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, vp, vp, vp, vp, vp]
+    L.crl_sim_reply_opponent_ord.argtypes = [vp, vp, i32, ctypes.c_int64, i32, vp, vp, vp, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     L.crl_wave_config.argtypes = [vp, i32]
     L.crl_wave_begin.argtypes = [vp, i32]
@@ -566,12 +569,21 @@ class Context(object):
                                        ctypes.c_void_p(dev_planes_s2)), "crl_sim_reply")
 
     def sim_reply_opponent(self, dev_depths, node_limit, dev_planes_s2, dev_nodes, dev_cuts, quiescence=0,
-                           node_budget=None, dev_depth_sum=None):
+                           node_budget=None, dev_depth_sum=None, ordering=False):
         """``sim_reply`` with the built-in opponent's move as the reply: device pointers to int32 [count] depths, the
         planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies; ``quiescence`` plies (0 ..
         OPP_MAX_QUIESCENCE) past the depth.  ``node_budget`` (not None): iterative deepening up to the depths under
         ``min(node_budget, node_limit)`` nodes per reply, ``dev_depth_sum`` the int64 [count] accumulator of the
-        completed depths."""
+        completed depths.  ``ordering`` (needs a ``node_budget``): the budgeted search with ORDERING (csrc/opponent.hpp),
+        ``crl_sim_reply_opponent_ord``; False calls the entry it called."""
+        if ordering:
+            if node_budget is None:
+                raise ValueError("ordering needs a node_budget")
+            self._ck(self._L.crl_sim_reply_opponent_ord(
+                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)), 1,
+                ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts),
+                ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_ord")
+            return
         if node_budget is not None:
             self._ck(self._L.crl_sim_reply_opponent_id(
                 self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)),
@@ -695,12 +707,17 @@ class Context(object):
                                      vp(dev_value), vp(dev_results), vp(dev_plies)), "crl_rollout")
 
     # ---- the built-in opponent (csrc/opponent.hpp; stockfish.py:23-31, gamestockfish.py:27-41) ------
-    def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT, quiescence=0, node_budget=None):
+    def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT, quiescence=0, node_budget=None,
+                       ordering=False):
         """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it,
         with ``quiescence`` plies (0 .. OPP_MAX_QUIESCENCE, one value per call) of quiescence search past the depth.
         Returns (moves u16, scores i32, nodes i64, flags u8); with ``push`` the moves are played.  ``node_budget`` (not
         None): iterative deepening, ``depths`` the maximum depths, under ``min(node_budget, node_limit)`` nodes per
-        slot; returns (moves, scores, nodes, flags, depths_done i32)."""
+        slot; returns (moves, scores, nodes, flags, depths_done i32).  ``ordering`` (needs a ``node_budget``): that
+        search with ORDERING (csrc/opponent.hpp: victims first, then the killer moves of the ply), through
+        ``crl_opponent_moves_ord``; False calls the entry it called."""
+        if ordering and node_budget is None:
+            raise ValueError("ordering needs a node_budget")
         dp = np.ascontiguousarray(depths, dtype=np.int32)
         assert dp.shape == (self.G,)
         moves = np.zeros(self.G, np.uint16)
@@ -709,6 +726,12 @@ class Context(object):
         flags = np.zeros(self.G, np.uint8)
         if node_budget is not None:
             done = np.zeros(self.G, np.int32)
+            if ordering:
+                self._ck(self._L.crl_opponent_moves_ord(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
+                                                        min(int(node_budget), int(node_limit)), 1, _ptr(moves),
+                                                        _ptr(scores), _ptr(nodes), _ptr(flags), _ptr(done)),
+                         "crl_opponent_moves_ord")
+                return moves, scores, nodes, flags, done
             self._ck(self._L.crl_opponent_moves_id(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
                                                    min(int(node_budget), int(node_limit)), _ptr(moves), _ptr(scores),
                                                    _ptr(nodes), _ptr(flags), _ptr(done)), "crl_opponent_moves_id")

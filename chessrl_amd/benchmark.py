@@ -43,7 +43,8 @@ def _load_model(model_dir):
     return ChessModel(weights=path if os.path.exists(path) else None)
 
 
-def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence=0, budget=None):
+def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence=0, budget=None,
+                 ordering=False):
     """(moves, plies, results) of the games with ``Agent.best_move(real_game=True)`` on the agent's plies."""
     import torch
     ctx = _lib.Context(games, 1, max_plies=max(max_plies, 2), device=dev.index or 0)
@@ -64,14 +65,15 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quie
                 ctx.greedy_moves(policy.data_ptr(), mask=agent_turn, push=True, want_moves=False)
             if opp_turn.any():
                 ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True, quiescence=quiescence,
-                                   node_budget=budget)
+                                   node_budget=budget, ordering=ordering)
             results = ctx.results()
         return ctx.records()
     finally:
         ctx.close()
 
 
-def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, quiescence=0, budget=None):
+def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, quiescence=0, budget=None,
+                 ordering=False):
     """(moves, plies, results) of the games with ``sims`` simulations per move against the opponent's replies.  A game
     is searched while it runs and has fewer than ``max_plies`` plies; a move adds two plies (one if it ends the game),
     so a game may end one ply past ``max_plies``."""
@@ -79,12 +81,12 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
     from .opponent import MinimaxPlayer
     eng = LockstepEngine(model, games, sims, device=dev.index or 0, max_plies=max_plies + 2,
                          reply=MinimaxPlayer(False, search_depth=opponent_depth, quiescence=quiescence,
-                                             node_budget=budget))
+                                             node_budget=budget, ordering=ordering))
     try:
         ctx = eng.ctx
         if not agent_white.all():                            # gamestockfish.py:31-33: the opponent opens as white
             ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True, quiescence=quiescence,
-                               node_budget=budget)
+                               node_budget=budget, ordering=ordering)
         while True:
             _, plies, results = ctx.records(with_moves=False)
             live = (results == _lib.RESULT_NONE) & (plies < max_plies)
@@ -101,7 +103,7 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
 
 
 def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=None, max_plies=512, model=None,
-              sims=0, opponent_quiescence=0, opponent_budget=None):
+              sims=0, opponent_quiescence=0, opponent_budget=None, opponent_ordering=False):
     """Plays ``games`` games against the built-in depth-``opponent_depth`` opponent (with ``opponent_quiescence``
     plies of quiescence search, 0 by default) and returns
     ``dict(played=, won=, drawn=, games=)``: the reference's tallies and the per-game UCI move lists.  ``workers`` is
@@ -110,7 +112,8 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     ``max_plies`` plies counts as played, neither won nor drawn.  ``sims`` > 0: the agent's move is the choice of an
     MCTS of ``sims`` simulations against the opponent's replies instead of its greedy move (module docstring).
     ``opponent_budget`` (None: none): the opponent deepens iteratively up to ``opponent_depth`` and stops at that many
-    nodes per move (csrc/opponent.hpp, ITERATIVE DEEPENING)."""
+    nodes per move (csrc/opponent.hpp, ITERATIVE DEEPENING); ``opponent_ordering`` (needs ``opponent_budget``): with
+    the move ORDERING of that header."""
     if not 1 <= int(opponent_depth) <= _lib.OPP_MAX_DEPTH:
         raise ValueError("opponent_depth must lie in [1, %d]" % _lib.OPP_MAX_DEPTH)
     quiescence = int(opponent_quiescence)
@@ -119,6 +122,9 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     budget = None if opponent_budget is None else int(opponent_budget)
     if budget is not None and budget < 1:
         raise ValueError("opponent_budget must be None or at least 1")
+    ordering = bool(opponent_ordering)
+    if ordering and budget is None:
+        raise ValueError("opponent_ordering needs an opponent_budget")
     sims = int(sims)
     if sims < 0:
         raise ValueError("sims must be 0 (the greedy agent) or the number of simulations per move")
@@ -134,10 +140,10 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     agent_white = np.array(colors, dtype=bool)
     if sims > 0:
         moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims,
-                                             quiescence, budget)
+                                             quiescence, budget, ordering)
     else:
         moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence,
-                                             budget)
+                                             budget, ordering)
     res = [None if r == _lib.RESULT_NONE else int(r) for r in results]
     out = tally(colors, res)
     out["games"] = [[move_to_uci(m) for m in moves[i, :plies[i]]] for i in range(games)]
@@ -147,8 +153,9 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
             print("Against the built-in depth-%d opponent%s (not Stockfish, no Elo)"
                   % (opponent_depth, ", quiescence %d" % quiescence if quiescence else ""))
         else:
-            print("Against the built-in opponent, depth <= %d within %d nodes per move%s (not Stockfish, no Elo)"
-                  % (opponent_depth, budget, ", quiescence %d" % quiescence if quiescence else ""))
+            print("Against the built-in opponent, depth <= %d within %d nodes per move%s%s (not Stockfish, no Elo)"
+                  % (opponent_depth, budget, ", ordered" if ordering else "",
+                     ", quiescence %d" % quiescence if quiescence else ""))
         if sims > 0:
             print("agent: MCTS, %d simulations per move" % sims)
         print("Games played: %d" % out["played"])
@@ -169,13 +176,15 @@ def main(argv=None):
     p.add_argument("--nodes", type=int, default=None,
                    help="node budget per move of the built-in opponent: iterative deepening up to --depth (default: "
                         "none, the fixed depth)")
+    p.add_argument("--ordering", action="store_true",
+                   help="order the moves of the --nodes search by victim and killer moves (needs --nodes)")
     p.add_argument("--seed", type=int, default=None, help="seed of the colour draw")
     p.add_argument("--max-plies", type=int, default=512)
     p.add_argument("--sims", type=int, default=0,
                    help="simulations per move of the agent's search against the opponent's replies (0: the greedy agent)")
     a = p.parse_args(argv)
     benchmark(a.model_dir, games=a.games, opponent_depth=a.depth, seed=a.seed, max_plies=a.max_plies, log=True,
-              sims=a.sims, opponent_quiescence=a.quiescence, opponent_budget=a.nodes)
+              sims=a.sims, opponent_quiescence=a.quiescence, opponent_budget=a.nodes, opponent_ordering=a.ordering)
 
 
 if __name__ == "__main__":

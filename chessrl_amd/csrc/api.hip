@@ -817,19 +817,27 @@ int crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t 
 
 // ITERATIVE DEEPENING under a node budget (csrc/opponent.hpp): kernels of their own, so the calls above launch what
 // they launched
-int crl_opponent_moves_id(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
-                          uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
+// (ordering = 1: ORDERING of csrc/opponent.hpp, the _ido kernels; 0 launches the _id kernels, whoever calls)
+static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depths, int quiescence, int push,
+                             int64_t node_budget, int ordering, uint16_t *moves, int32_t *scores, int64_t *nodes,
+                             uint8_t *flags, int32_t *depths_done)
 {
-    ENTER(ctx, depths && moves && node_budget >= 1);
+    ENTER(ctx, depths && moves && node_budget >= 1 && (ordering == 0 || ordering == 1));
     if (quiescence < 0 || quiescence > CRL_OPP_MAX_QUIESCENCE)
-        return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves_id: a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
+        return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
     const size_t G = ctx->W;
     for (size_t i = 0; i < G; i++)
         if (depths[i] < 0 || depths[i] > CRL_OPP_MAX_DEPTH)
-            return fail(ctx, CRL_ERR_ARG, "crl_opponent_moves_id: a depth outside 0 .. CRL_OPP_MAX_DEPTH");
+            return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a depth outside 0 .. CRL_OPP_MAX_DEPTH");
     long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
     HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
-    if (quiescence > 0)
+    if (ordering && quiescence > 0)
+        LAUNCH(ctx, k_opponent_moves_ido_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
+               (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    else if (ordering)
+        LAUNCH(ctx, k_opponent_moves_ido, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_budget,
+               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    else if (quiescence > 0)
         LAUNCH(ctx, k_opponent_moves_id_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
                (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
     else
@@ -843,19 +851,49 @@ int crl_opponent_moves_id(crl_ctx *ctx, const int32_t *depths, int quiescence, i
     return check_dev_error(ctx);
 }
 
-int crl_sim_reply_opponent_id(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
-                              void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
-                              uint64_t *dev_depth_sum_u64)
+int crl_opponent_moves_id(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
+                          uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
+{
+    return opponent_moves_id(ctx, "crl_opponent_moves_id", depths, quiescence, push, node_budget, 0, moves, scores,
+                             nodes, flags, depths_done);
+}
+
+int crl_opponent_moves_ord(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
+                           int ordering, uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags,
+                           int32_t *depths_done)
+{
+    return opponent_moves_id(ctx, "crl_opponent_moves_ord", depths, quiescence, push, node_budget, ordering, moves,
+                             scores, nodes, flags, depths_done);
+}
+
+int crl_sim_reply_opponent_ord(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                               uint64_t *dev_depth_sum_u64)
 {
     ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
-                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE);
-    if (quiescence > 0)
+                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
+                   (ordering == 0 || ordering == 1));
+    if (ordering && quiescence > 0)
+        LAUNCH(ctx, k_reply_opponent_ido_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    else if (ordering)
+        LAUNCH(ctx, k_reply_opponent_ido, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    else if (quiescence > 0)
         LAUNCH(ctx, k_reply_opponent_id_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
                (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
     else
         LAUNCH(ctx, k_reply_opponent_id, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
                (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
     return CRL_OK;
+}
+
+int crl_sim_reply_opponent_id(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                              void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                              uint64_t *dev_depth_sum_u64)
+{
+    return crl_sim_reply_opponent_ord(ctx, dev_depths_i32, quiescence, node_budget, 0, dev_planes_s2, dev_nodes_u64,
+                                      dev_cuts_u32, dev_depth_sum_u64);
 }
 
 // ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------------------------

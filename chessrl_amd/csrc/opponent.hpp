@@ -97,6 +97,34 @@
 // iteration i + 1 is a change of state inside the turn that finished iteration i (ply 0, the full window, the remembered
 // best move), not a loop of its own, so a logic error still ends as a flagged cut.  The move-to-front is one ballot per
 // 64 moves and a shift by one lane.  (tests/iterdeep_util.py restates this section.)
+//
+// ORDERING (the _ido kernels only; it requires ITERATIVE DEEPENING, and everything in that section holds, the root's
+// order included: generation order with the previous iteration's best moved to the front).
+//     Move order below the root.  At every node at ply k >= 1 that searches moves the order is a stable partition into
+//     NINE classes, generation order inside each class:
+//         0 .. 5   the victim classes of QUIESCENCE 4c: victim Q, R, B, N, P (en passant counts as P), then the
+//                  promotions that capture nothing;
+//         6        killer A of ply k;      7   killer B of ply k;      8   every other quiet move.
+//     A tactical move is classed by its victim whatever the killers are.  A node that stands pat (4c) searches the
+//     classes 0 .. 5 only, exactly as without ORDERING; a quiescence node in check (4b) and every node at k < D search
+//     all nine.
+//     Killers.  Each ply 1 .. D + Q - 1 has ONE pair of 16-bit moves (A, B).  Both are NO_MOVE when the slot's search
+//     starts; they are kept across the iterations of that search and never shared between slots or between two
+//     searches.  A killer that is not in the node's list has no effect.
+//     Setting a killer.  When a node at ply k >= 1 has searched its move m and then alpha >= beta (the cut of SEARCH,
+//     whether or not a move remained), and m is not tactical in that node's position, and m != A: B = A, then A = m.
+//     A node that stands pat searches tactical moves only, so it never sets a killer; the root never sets one.
+//     Nothing else changes: fail-soft, the strictly-greater rule, the windows, one wave_movegen per turn, the budget
+//     tested before every node, the cut rules, depth_done and CRL_OPP_CUT.
+// Consequence.  With a budget nothing reaches, move, score, flag and depth_done are those of the _id search (each
+// iteration returns the minimax pair of its root order, and the root order does not depend on what lies below it); only
+// `nodes` differs.  Under a budget that cuts, all five may differ.  Both searches stay a function of the board and the
+// settings alone.  Structure: the killers of ply k and the number of tactical moves of the node live in the pad words
+// of frame k (frames exist exactly for the plies that search moves, and a frame is written field by field, never as a
+// whole), so the LDS is what it was; a cursor at or past the stored number is a quiet move, so the turn that hands a
+// value up needs no board to decide whether a cut sets a killer, and lane 0 stores the pair with the frame's own
+// cursor, best and alpha.  The partition is the seven ballots of 4c per 64 moves and two more that find the killers: a
+// killer class holds at most one move.  (tests/ordering_util.py restates this section.)
 #pragma once
 #include "search.hpp"
 
@@ -111,7 +139,10 @@ constexpr uint8_t OPP_CUT = 1, OPP_SKIPPED = 2;
 struct __attribute__((aligned(16))) OppFrame {
     Board b;
     u16 mv[MAX_MOVES];
-    int32_t cur, n, alpha, beta, best, pad[3];
+    int32_t cur, n, alpha, beta, best;
+    int32_t nt;                                // ORDERING: the tactical moves of the node are mv[0 .. nt)
+    uint32_t killers;                          // ORDERING: killer A (low half) and B of this ply
+    int32_t pad;
 };
 static_assert(sizeof(OppFrame) == 608, "OppFrame must be 608 bytes");
 
@@ -220,7 +251,12 @@ __device__ inline int opp_victim_class(const Board &b, u64 occ, u64 own, u32 mv)
 
 // stable partition of mv[0 .. n) by opp_victim_class, the scheme of opp_partition with seven ballots per 64 moves.
 // Returns the number of tactical moves: they are mv[0 .. that).  mv is visible on entry and on return.
-__device__ inline int opp_partition_victim(const Board &b, u16 *mv, int n, int lane)
+// KL: ORDERING -- inside class 6, the quiet moves, killer `ka` comes first, then killer `kb`, then the others in
+// generation order: the nine classes of the header.  A killer is ONE move, so its class needs no ballot row of its own:
+// one ballot per 64 moves finds its rank among the quiet moves, and every other quiet move steps back by the killers
+// that stood behind it.  (A tactical move equal to a killer is no hit.)  Every line marked KL folds away without it.
+template <bool KL = false>
+__device__ inline int opp_partition_victim(const Board &b, u16 *mv, int n, int lane, u32 ka = NO_MOVE, u32 kb = NO_MOVE)
 {
     constexpr int NC = 7;
     const u64 occ = occupied(b);
@@ -229,6 +265,7 @@ __device__ inline int opp_partition_victim(const Board &b, u16 *mv, int n, int l
     u32 m[4];
     int cl[4], tot[NC];
     u64 C[4][NC];
+    int ra = -1, rb = -1;                              // KL: the ranks of the killers among the quiet moves, -1: absent
 #pragma unroll
     for (int q = 0; q < NC; q++) tot[q] = 0;
 #pragma unroll
@@ -240,6 +277,11 @@ __device__ inline int opp_partition_victim(const Board &b, u16 *mv, int n, int l
 #pragma unroll
         for (int q = 0; q < NC; q++) {
             C[c][q] = __ballot(cl[c] == q);
+            if (KL && q == NC - 1) {                   // (tot[6] still counts the quiet moves of the chunks before)
+                const u64 ha = __ballot(cl[c] == q && m[c] == ka), hb = __ballot(cl[c] == q && m[c] == kb);
+                if (ha) ra = tot[q] + popc(C[c][q] & (ha - 1));        // (a legal move stands in the list once)
+                if (hb) rb = tot[q] + popc(C[c][q] & (hb - 1));
+            }
             tot[q] += popc(C[c][q]);
         }
     }
@@ -248,6 +290,7 @@ __device__ inline int opp_partition_victim(const Board &b, u16 *mv, int n, int l
     base[0] = 0;
 #pragma unroll
     for (int q = 1; q < NC; q++) base[q] = base[q - 1] + tot[q - 1];
+    const int quiet0 = base[NC - 1];
 #pragma unroll
     for (int c = 0; c < 4; c++) {
         int pos = -1;
@@ -255,6 +298,10 @@ __device__ inline int opp_partition_victim(const Board &b, u16 *mv, int n, int l
         for (int q = 0; q < NC; q++) {
             if (cl[c] == q) pos = base[q] + popc(C[c][q] & below);
             base[q] += popc(C[c][q]);
+        }
+        if (KL && cl[c] == NC - 1) {                   // a permutation of the quiet ranks: ka, kb, the others in order
+            const int r = pos - quiet0;
+            pos = quiet0 + (r == ra ? 0 : r == rb ? (ra >= 0) : r + (ra > r) + (rb > r));
         }
         if (pos >= 0) mv[pos] = (u16)m[c];             // pos < n: the classes partition the n valid moves
     }
@@ -298,11 +345,19 @@ __device__ inline void opp_move_to_front(u16 *mv, int n, u32 pm, int lane)
 // ID: ITERATIVE DEEPENING of the header comment -- Dmax is the maximum depth and `limit` the node budget; the loop below
 // then searches to D = 1, 2, .. Dmax, and depth_done is the last iteration that finished (done: it was Dmax).  Without
 // ID, D = Dmax throughout, depth_done is not set and every line marked ID folds away.
+// ORD: ORDERING of the header comment, on top of ID; NF is the number of frames behind f (their killers are cleared
+// here).  Every line marked ORD folds away without it.
 struct OppResult { u32 mv; int score; long long nodes; bool done; int depth_done; };
 
-template <bool QS, bool ID = false>
+template <bool QS, bool ID = false, bool ORD = false>
 __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long long limit, OppFrame *f, int lane)
 {
+    static_assert(ID || !ORD, "ORDERING requires ITERATIVE DEEPENING");
+    if (ORD) {                                             // both killers of every ply: NO_MOVE
+        constexpr int NF = QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1;
+        if (lane < NF) f[lane].killers = ((u32)NO_MOVE << 16) | (u32)NO_MOVE;
+        __syncthreads();
+    }
     Board b = root;
     int k = 0, a = -OPP_INF, be = OPP_INF, v = 0, root_best = -OPP_INF;
     u32 best_mv = NO_MOVE, first_mv = NO_MOVE;
@@ -328,19 +383,27 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
         else if (horizon) v = QS ? stand : uni(opp_evaluate(b, lane));
         else {
             __syncthreads();                               // F->mv visible
-            int cnt = n, best0 = -OPP_INF;
+            int cnt = n, best0 = -OPP_INF, nt = 0;         // ORD: nt, the node's tactical moves
             if (quiet && !chk) {                           // 4c: stand pat, then the tactical moves by victim
                 cnt = opp_partition_victim(b, F->mv, n, lane);
                 best0 = stand;
                 if (stand > a) a = stand;
-            } else if (k > 0) opp_partition(b, F->mv, n, lane);
-            else {
+                nt = cnt;                                  // (never below the cursor: no killer from this frame)
+            } else if (k > 0) {
+                if (ORD) {
+                    const u32 kl = (u32)uni((int)F->killers);
+                    nt = opp_partition_victim<true>(b, F->mv, n, lane, kl & 0xFFFFu, kl >> 16);
+                } else opp_partition(b, F->mv, n, lane);
+            } else {
                 first_mv = (u32)uni((int)F->mv[0]);
                 if (ID && held_mv != NO_MOVE) opp_move_to_front(F->mv, n, held_mv, lane);
             }
             if (QS && cnt == 0) v = stand;                 // 4c without a tactical move (cnt = n > 0 everywhere else)
             else {
-                if (lane == 0) { F->b = b; F->cur = 0; F->n = cnt; F->alpha = a; F->beta = be; F->best = best0; }
+                if (lane == 0) {
+                    F->b = b; F->cur = 0; F->n = cnt; F->alpha = a; F->beta = be; F->best = best0;
+                    if (ORD) F->nt = nt;
+                }
                 __syncthreads();
                 have_v = false;
             }
@@ -374,9 +437,20 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
                 if (k == 0) { best_mv = (u32)uni((int)P.mv[cur]); root_best = sc; }
             }
             if (sc > al) al = sc;
+            u32 kl = 0;
+            bool set_killer = false;                       // ORD: a cut below the root by a quiet move other than A
+            if (ORD && k > 0 && al >= pb && cur >= uni(P.nt)) {
+                const u32 m = (u32)uni((int)P.mv[cur]);
+                kl = (u32)uni((int)P.killers);
+                set_killer = m != (kl & 0xFFFFu);
+                kl = (kl << 16) | m;                       // B = A, A = m
+            }
             cur++;
             __syncthreads();                               // the frame was read
-            if (lane == 0) { P.cur = cur; P.best = best; P.alpha = al; }
+            if (lane == 0) {
+                P.cur = cur; P.best = best; P.alpha = al;
+                if (ORD && set_killer) P.killers = kl;
+            }
             __syncthreads();
             if (cur < pn && al < pb) have_v = false;       // frame k has a next move to search
             else v = best;                                 // exhausted or cut: it returns its best
@@ -407,7 +481,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
 
 // One slot of k_opponent_moves / k_opponent_moves_q and, ID, of their _id forms.  Window-relative rows: depths / moves /
 // scores / nodes_out / flags [count] and, ID only, depths_done [count]
-template <bool QS, bool ID = false>
+template <bool QS, bool ID = false, bool ORD = false>
 __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, int push, long long limit, u16 *moves,
                                            int32_t *scores, long long *nodes_out, uint8_t *flags, OppLds<QS> &s,
                                            int32_t *depths_done = nullptr)
@@ -425,7 +499,7 @@ __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, 
         return;
     }
     const Board root = uni_board(d.cur[g]);
-    const OppResult o = opp_search<QS, ID>(root, D, Q, limit, s.f, lane);
+    const OppResult o = opp_search<QS, ID, ORD>(root, D, Q, limit, s.f, lane);
     if (lane == 0) {
         moves[r] = (u16)o.mv;
         scores[r] = o.score;
@@ -435,7 +509,7 @@ __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, 
     }
     if (push && o.mv != NO_MOVE) {
         __syncthreads();                                   // the frames are dead: s.w takes their bytes
-        game_push(d, g, root, o.mv, lane, s.w);
+        game_push(d, g, ORD ? uni_board(d.cur[g]) : root, o.mv, lane, s.w);    // (ORD: not held across the search)
     }
 }
 
@@ -474,13 +548,30 @@ __global__ __launch_bounds__(64) void k_opponent_moves_id_q(Dev d, const int32_t
     opponent_moves_slot<true, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s, depths_done);
 }
 
+// the _id kernels with ORDERING: the same arguments
+__global__ __launch_bounds__(64) void k_opponent_moves_ido(Dev d, const int32_t *depths, int push, long long budget,
+                                                           u16 *moves, int32_t *scores, long long *nodes_out,
+                                                           uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<false> s;
+    opponent_moves_slot<false, true, true>(d, depths, 0, push, budget, moves, scores, nodes_out, flags, s, depths_done);
+}
+
+__global__ __launch_bounds__(64) void k_opponent_moves_ido_q(Dev d, const int32_t *depths, int Q, int push,
+                                                             long long budget, u16 *moves, int32_t *scores,
+                                                             long long *nodes_out, uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<true> s;
+    opponent_moves_slot<true, true, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s, depths_done);
+}
+
 // expand, the opponent's half (mctree.py:244-246) with the built-in opponent as the mover (gamestockfish.py:27-41):
 // the reply stored for S1 is the move k_opponent_moves plays from S1 -- it reads the board alone, so the tree holds the
 // real opponent's reply.  Rows as k_reply: one whose pending leaf is not LEAF_NEW_REPLY only clears lab_n2.  The root
 // order of the search is wave_movegen's (s1_moves is not read).  A cut reply is a move like any other.  nodes_acc /
 // cuts_acc [count], window-relative: this wave owns its row, so lane 0 adds with a plain load and store.  ID: the
 // search is ITERATIVE DEEPENING under the budget `limit`, and depth_acc [count] sums the completed depths.
-template <bool QS, bool ID = false>
+template <bool QS, bool ID = false, bool ORD = false>
 __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, long long limit, void *planes2,
                                           unsigned long long *nodes_acc, uint32_t *cuts_acc, OppLds<QS> &s,
                                           unsigned long long *depth_acc = nullptr)
@@ -495,7 +586,7 @@ __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, l
     }
     const int c = uni(d.game[g].leaf_node);
     const Board s1 = uni_board(d.node[(size_t)g * d.N + c].s1);
-    const OppResult o = opp_search<QS, ID>(s1, D, Q, limit, s.f, lane);
+    const OppResult o = opp_search<QS, ID, ORD>(s1, D, Q, limit, s.f, lane);
     if (o.mv == NO_MOVE) { dev_error(d, DERR_STATE); return; }              // S1 is running: it has a legal move
     if (lane == 0) {
         nodes_acc[r] += (unsigned long long)o.nodes;
@@ -536,6 +627,23 @@ __global__ __launch_bounds__(64) void k_reply_opponent_id_q(Dev d, const int32_t
 {
     __shared__ OppLds<true> s;
     reply_opponent_row<true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
+}
+
+// the _id kernels with ORDERING: the same arguments
+__global__ __launch_bounds__(64) void k_reply_opponent_ido(Dev d, const int32_t *depths, long long budget,
+                                                           void *planes2, unsigned long long *nodes_acc,
+                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<false> s;
+    reply_opponent_row<false, true, true>(d, depths, 0, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
+}
+
+__global__ __launch_bounds__(64) void k_reply_opponent_ido_q(Dev d, const int32_t *depths, int Q, long long budget,
+                                                             void *planes2, unsigned long long *nodes_acc,
+                                                             uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<true> s;
+    reply_opponent_row<true, true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
 }
 
 }  // namespace crl

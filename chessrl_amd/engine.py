@@ -236,6 +236,7 @@ class LockstepEngine(object):
     the built-in opponent's move, searched with the player's ``search_depth``, ``quiescence`` and ``node_limit`` (its colour is
     ignored: the side to move after our move replies).  A player with a ``node_budget`` replies by iterative deepening
     under that budget (csrc/opponent.hpp ``k_reply_opponent_id``); one without launches the fixed-depth kernel as before.
+    A budgeted player with ``ordering`` replies through the ordered kernels (``k_reply_opponent_ido``), eager and captured.
     """
 
     def __init__(self, evaluator, n_games, max_sims, device=0, max_plies=4096,
@@ -419,7 +420,8 @@ class LockstepEngine(object):
         self.ctx.sim_reply_opponent(self.reply_depths.data_ptr(), self.reply.node_limit, self.planes_s2.data_ptr(),
                                     self.reply_nodes.data_ptr(), self.reply_cuts.data_ptr(),
                                     quiescence=self.reply.quiescence, node_budget=budget,
-                                    dev_depth_sum=None if budget is None else self.reply_depth_sum.data_ptr())
+                                    dev_depth_sum=None if budget is None else self.reply_depth_sum.data_ptr(),
+                                    ordering=self.reply.ordering)
 
     def phase_tower_s2(self):
         if self.legal_priors:

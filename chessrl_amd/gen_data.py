@@ -55,13 +55,16 @@ def side_depths(draws, white_to_move):
 
 
 def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512,
-             quiescence=0, node_budget=None):
+             quiescence=0, node_budget=None, ordering=False):
     """Plays ``num_games`` games, saves the finished ones to ``save_path`` (appending to what the file holds, as
     ``DatasetGame.save`` does) and returns the ``DatasetGame`` it saved.  The reference's ``gen_data`` forgets to
     pass ``depth`` and ``random_dep`` on to ``play_game`` (gen_data_stockfish.py:44-49); here both are honoured.
     ``workers`` is accepted and ignored; a game still running after ``max_plies`` plies is dropped.  ``quiescence``:
     the quiescence plies of both sides past their depths (0 .. CRL_OPP_MAX_QUIESCENCE; 0: none).  ``node_budget``
-    (None: none): both sides deepen iteratively up to their depths and stop at that many nodes per move."""
+    (None: none): both sides deepen iteratively up to their depths and stop at that many nodes per move; ``ordering``
+    (needs a ``node_budget``): with the move ORDERING of csrc/opponent.hpp."""
+    if ordering and node_budget is None:
+        raise ValueError("ordering needs a node_budget")
     if node_budget is not None and int(node_budget) < 1:
         raise ValueError("node_budget must be None or at least 1")
     quiescence = int(quiescence)
@@ -90,7 +93,7 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
             if not running.any():
                 break
             ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True,
-                               quiescence=quiescence, node_budget=node_budget)
+                               quiescence=quiescence, node_budget=node_budget, ordering=bool(ordering))
             results = ctx.results()
         moves, plies, results = ctx.records()
     finally:
@@ -114,6 +117,8 @@ def main(argv=None):
                    help="Quiescence plies of the built-in opponent past its depth, both sides (0-6; 0: none).")
     p.add_argument("--nodes", type=int, default=None,
                    help="Node budget per move, both sides: iterative deepening up to the depth (default: none).")
+    p.add_argument("--ordering", action="store_true", default=False,
+                   help="Order the moves of the --nodes search by victim and killer moves, both sides.")
     p.add_argument("--random_depth", action="store_true", default=False,
                    help="Use normal distribution of depths with mean --depth.")
     p.add_argument("--debug", action="store_true", default=False, help="Log debug messages on screen. Default false.")
@@ -123,7 +128,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.DEBUG if a.debug else logging.INFO)
     gen_data(a.data_path, num_games=a.games, depth=a.depth, random_dep=a.random_depth,
              opening_plies=a.opening_plies, seed=a.seed, quiescence=a.quiescence,
-             node_budget=a.nodes)
+             node_budget=a.nodes, ordering=a.ordering)
 
 
 if __name__ == "__main__":

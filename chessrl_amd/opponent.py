@@ -9,7 +9,8 @@ control, and no Elo is claimed -- a result reads "against the built-in depth-d o
 fixed depth it can search ``quiescence`` plies of captures, promotions and check evasions
 (opponent.hpp, QUIESCENCE); 0, the default, is the fixed-depth search alone.  With ``node_budget`` it deepens
 iteratively up to ``search_depth`` and stops at that many nodes per move (opponent.hpp, ITERATIVE DEEPENING): the
-deterministic counterpart of the reference's ``Limit(time=...)`` (stockfish.py:14-21).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
+deterministic counterpart of the reference's ``Limit(time=...)`` (stockfish.py:14-21); ``ordering=True`` on top of a
+budget orders the moves below the root by victim and killer moves (opponent.hpp, ORDERING).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
 these classes are the one-game drop-in surface over it.
 """
 import numpy as np
@@ -33,9 +34,11 @@ class MinimaxPlayer(Player):
     alpha-beta move for a ``chessrl_amd.Game`` (``'00000'`` on a finished game), with ``quiescence`` plies of
     quiescence search past that depth.  ``node_budget`` (None: no budget, the fixed-depth search): iterative deepening
     with ``search_depth`` as the maximum depth under ``min(node_budget, node_limit)`` nodes per move; ``last_depth`` is
-    then the depth the last search completed (None without a budget)."""
+    then the depth the last search completed (None without a budget).  ``ordering`` (needs a ``node_budget``): below
+    the root that search tries the moves by victim, then the killer moves of the ply (opponent.hpp, ORDERING); with a
+    budget it does not reach it plays the same move for fewer nodes."""
 
-    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0, node_budget=None):
+    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0, node_budget=None, ordering=False):
         super().__init__(color)
         if not 1 <= int(search_depth) <= MAX_DEPTH:
             raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
@@ -49,6 +52,9 @@ class MinimaxPlayer(Player):
             raise ValueError("node_budget must be None or at least 1")
         self.node_limit = int(node_limit)
         self.node_budget = None if node_budget is None else int(node_budget)
+        if ordering and self.node_budget is None:
+            raise ValueError("ordering needs a node_budget")
+        self.ordering = bool(ordering)
         self.last = None                      # (score, nodes, flag) of the last search
         self.last_depth = None                # with a budget: the depth that search completed
 
@@ -57,7 +63,7 @@ class MinimaxPlayer(Player):
             raise RuntimeError("Game was freed")
         ctx = arena().one(game._slot)
         out = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False, node_limit=self.node_limit,
-                                 quiescence=self.quiescence, node_budget=self.node_budget)
+                                 quiescence=self.quiescence, node_budget=self.node_budget, ordering=self.ordering)
         moves, scores, nodes, flags = out[:4]
         self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
         self.last_depth = int(out[4][0]) if self.node_budget is not None else None
@@ -71,18 +77,19 @@ class MinimaxPlayer(Player):
 
 class GameOpponent(Game):
     """Mirror of ``GameStockfish``: a game against the built-in opponent.  ``opponent``: a ``MinimaxPlayer``, or
-    None for one of depth ``opponent_depth``, ``opponent_quiescence`` and ``opponent_budget`` (the player's
-    ``node_budget``) with the colour opposite to ``player_color``."""
+    None for one of depth ``opponent_depth``, ``opponent_quiescence``, ``opponent_budget`` (the player's
+    ``node_budget``) and ``opponent_ordering`` (its ``ordering``) with the colour opposite to ``player_color``."""
 
     def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2,
-                 opponent_quiescence=0, opponent_budget=None):
+                 opponent_quiescence=0, opponent_budget=None, opponent_ordering=False):
         if opponent is not None and not isinstance(opponent, MinimaxPlayer):
             raise ValueError("opponent must be a MinimaxPlayer or None")
         self.opponent = None                  # (a board's move stack is replayed by plain Game.move)
         super().__init__(board=board, player_color=player_color, date=date)
         if opponent is None:
             opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth,
-                                     quiescence=opponent_quiescence, node_budget=opponent_budget)
+                                     quiescence=opponent_quiescence, node_budget=opponent_budget,
+                                     ordering=opponent_ordering)
         self.opponent = opponent
 
     def move(self, movement):

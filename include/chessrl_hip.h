@@ -69,7 +69,8 @@ typedef struct crl_ctx crl_ctx;
  * crl_abi_version() first and refuses a library of another version (a ctypes call through a stale
  * signature hands the GPU garbage pointers).  crl_source_hash(): sha256 over the sources (csrc/ + this
  * header + compiler flags) the library was built from, as chessrl_amd/_lib.py computes it; the string
- * is also findable in the file itself behind the marker "CRL_SRC_HASH=".  No reference counterpart. */
+ * is also findable in the file itself behind the marker "CRL_SRC_HASH=".  No reference counterpart.
+ * (The _ord entries of the built-in opponent are additions that change no existing signature: still 9.) */
 #define CRL_ABI_VERSION 9
 int  crl_abi_version(void);
 const char *crl_source_hash(void);
@@ -328,6 +329,20 @@ int  crl_opponent_moves_id(crl_ctx *ctx, const int32_t *depths /*G*/, int quiesc
 int  crl_sim_reply_opponent_id(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
                                void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
                                uint64_t *dev_depth_sum_u64);
+/* The two _id calls with an opt-in move ORDERING (csrc/opponent.hpp states the rule) for the budgeted search that
+ * stands for the reference's Limit(time=...) (stockfish.py:14-21).  ordering = 0 launches the kernels of the _id call
+ * and nothing else.  ordering = 1: below the root the moves are searched by victim (Q R B N P, promotions), then the two
+ * killer moves of the ply, then the other quiet moves; a quiet move that cuts a node below the root becomes the
+ * first killer of its ply, for this slot and this search only.  With a budget that no slot reaches, moves, scores,
+ * flags and depths_done are those of ordering = 0 and only the node counts differ; under a budget that cuts, all may
+ * differ.  The answer stays a function of the board and the arguments alone.
+ * CRL_ERR_ARG: an ordering other than 0 or 1, and what the _id calls refuse.  No state changes on an error. */
+int  crl_opponent_moves_ord(crl_ctx *ctx, const int32_t *depths /*G*/, int quiescence, int push, int64_t node_budget,
+                            int ordering, uint16_t *moves /*G*/, int32_t *scores /*G*/, int64_t *nodes /*G*/,
+                            uint8_t *flags /*G*/, int32_t *depths_done /*G*/);   /* stockfish.py:14-21 */
+int  crl_sim_reply_opponent_ord(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                                int ordering, void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                                uint64_t *dev_depth_sum_u64);                     /* stockfish.py:14-21 */
 
 /* ---- threads > 1: virtual-loss waves of simulations per game (csrc/search_wave.hpp) --------------------------
  * The reference runs `threads` explore_tree workers on one tree, kept apart by a virtual loss (mctree.py:12,173-176,

@@ -4,6 +4,7 @@
     python tools/opponent_probe.py [--games 4096] [--opening-plies 6] [--node-limit 200000] [--out profiles/opponent_probe.json]
     python tools/opponent_probe.py --quiescence 2,4,6 --depths 1,2 --out profiles/opponent_probe_q.json
     python tools/opponent_probe.py --budget 150,300,600,1500 --depths 2,3 --max-depth 3
+    python tools/opponent_probe.py --ordering --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words), so the slots hold
 different positions.  Per depth, in depth order: one warm-up launch, then three timed ones (host wall time around the
@@ -12,7 +13,10 @@ positions.  --quiescence Q[,Q..]: the same per quiescence (opponent.hpp QUIESCEN
 default, is the fixed-depth search and leaves the output as it was.  --budget B[,B..]: after the fixed depths, on the
 same games in the same process, iterative deepening up to --max-depth under each node budget (opponent.hpp ITERATIVE
 DEEPENING), keyed "<=<depth>@<B>[+q<Q>]", with the histogram of the completed depths; the output then goes to
-profiles/opponent_probe_id.json unless --out names another file.  No threshold: this is a measurement.
+profiles/opponent_probe_id.json unless --out names another file.  --ordering: every budget is run with the move
+ORDERING of opponent.hpp off and on in the same process, the launches alternating (warm-up off, warm-up on, then three
+times off, on); the ordered rows are keyed "<=<depth>@<B>[+q<Q>] ordered" and the output goes to
+profiles/opponent_probe_ord.json.  No threshold: this is a measurement.
 """
 import argparse
 import json
@@ -35,11 +39,13 @@ def main():
     ap.add_argument("--quiescence", default="0")
     ap.add_argument("--budget", default="", help="node budgets of the iterative-deepening launches (default: none)")
     ap.add_argument("--max-depth", type=int, default=3, help="maximum depth of the --budget launches")
+    ap.add_argument("--ordering", action="store_true", help="run every --budget with ordering off and on, alternating")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     budgets = [int(b) for b in args.budget.split(",") if b]
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "opponent_probe_id.json" if budgets else "opponent_probe.json")
+        name = "opponent_probe.json" if not budgets else "opponent_probe_ord.json" if args.ordering else "opponent_probe_id.json"
+        args.out = os.path.join(ROOT, "profiles", name)
     import numpy as np
     from chessrl_amd import _lib
     from chessrl_amd.gen_data import opening_words
@@ -57,23 +63,36 @@ def main():
         kw = {"quiescence": quiescence} if quiescence else {}
         if budget is not None:
             kw["node_budget"] = budget
-        times = []
+        # the launches of a case alternate between its variants: ordering off and, with --ordering, on
+        variants = [(key, kw)]
+        if budget is not None and args.ordering:
+            variants.append((key + " ordered", dict(kw, ordering=True)))
+        times = dict((k, []) for k, _ in variants)
+        last = {}
         for i in range(4):
-            t0 = time.perf_counter()
-            moves, scores, nodes, flags = ctx.opponent_moves(row, node_limit=args.node_limit, **kw)[:4]
-            if i:
-                times.append(time.perf_counter() - t0)
-        t = statistics.median(times)
-        searched = flags != _lib.OPP_SKIPPED
-        total = int(nodes.sum())
-        out["depths"][key] = {
-            "seconds": times, "ms_per_launch": 1e3 * t, "nodes": total, "nodes_per_slot_mean": float(nodes[searched].mean()),
-            "nodes_per_slot_max": int(nodes.max()), "nodes_per_s": total / t, "us_per_node_of_the_longest_slot":
-            1e6 * t / max(int(nodes.max()), 1), "cut_share": float((flags == _lib.OPP_CUT).mean())}
-        if budget is not None:
-            done = ctx.opponent_moves(row, node_limit=args.node_limit, **kw)[4]
-            out["depths"][key]["depth_done_histogram"] = np.bincount(done[searched], minlength=depth + 1).tolist()
-        print(key, json.dumps(out["depths"][key]), flush=True)
+            for k, vkw in variants:
+                t0 = time.perf_counter()
+                last[k] = ctx.opponent_moves(row, node_limit=args.node_limit, **vkw)
+                if i:
+                    times[k].append(time.perf_counter() - t0)
+        for k, vkw in variants:
+            moves, scores, nodes, flags = last[k][:4]
+            t = statistics.median(times[k])
+            searched = flags != _lib.OPP_SKIPPED
+            total = int(nodes.sum())
+            out["depths"][k] = {
+                "seconds": times[k], "ms_per_launch": 1e3 * t, "nodes": total,
+                "nodes_per_slot_mean": float(nodes[searched].mean()),
+                "nodes_per_slot_max": int(nodes.max()), "nodes_per_s": total / t, "us_per_node_of_the_longest_slot":
+                1e6 * t / max(int(nodes.max()), 1), "cut_share": float((flags == _lib.OPP_CUT).mean())}
+            if budget is not None:
+                out["depths"][k]["depth_done_histogram"] = np.bincount(last[k][4][searched], minlength=depth + 1).tolist()
+            print(k, json.dumps(out["depths"][k]), flush=True)
+        if len(variants) == 2:                       # what ORDERING promises when no slot is cut: the same answers
+            a, b = last[variants[0][0]], last[variants[1][0]]
+            if not (a[3] == _lib.OPP_CUT).any() and not (b[3] == _lib.OPP_CUT).any():
+                same = all(np.array_equal(a[j], b[j]) for j in (0, 1, 3, 4))
+                out["depths"][variants[1][0]]["answers_equal_unordered"] = bool(same)
     ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

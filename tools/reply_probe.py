@@ -5,7 +5,7 @@ tower call + the alpha-beta search), over the same games and weights in one proc
 
     python tools/reply_probe.py [--games 4096] [--opening-plies 6] [--towers 10x128:f16] [--depths 1,2]
                                 [--steps 32] [--windows 3] [--out profiles/reply_probe.json]
-                                [--budget 150,300,600 [--max-depth 3]]
+                                [--budget 150,300,600 [--max-depth 3] [--ordering]]
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words: the same games in every
 engine).  All engines live side by side; after ``search_begin`` and 8 warm-up steps each (graphs captured before),
@@ -15,7 +15,9 @@ Then one more step with cleared accumulators gives the nodes per reply (mean / m
 and the cuts; the accumulators over the whole run give the mean per slot and step.  --budget B[,B..] adds one engine
 per node budget, ``reply=MinimaxPlayer(search_depth=--max-depth, node_budget=B)`` (iterative deepening:
 k_reply_opponent_id), with the histogram of the completed depths of the last step's replies; such a run is stored as the
-block "node_budget" of the output file, whose other content stays.  No threshold: a measurement.
+block "node_budget" of the output file, whose other content stays.  --ordering adds, next to every budgeted engine,
+the same engine with ``ordering=True`` (k_reply_opponent_ido), so every budget runs with ordering off and on in the same
+process; such a run is stored as the block "ordering".  No threshold: a measurement.
 """
 import argparse
 import json
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--budget", default="", help="node budgets of the iterative-deepening engines (default: none)")
     ap.add_argument("--max-depth", type=int, default=3, help="maximum depth of the --budget engines")
+    ap.add_argument("--ordering", action="store_true", help="every --budget engine with ordering off and on")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reply_probe.json"))
     args = ap.parse_args()
     budgets = [int(b) for b in args.budget.split(",") if b]
@@ -65,6 +68,9 @@ def main():
         for b in budgets:
             engines["depth <= %d within %d" % (args.max_depth, b)] = LockstepEngine(
                 model, G, sims, reply=MinimaxPlayer(False, search_depth=args.max_depth, node_budget=b))
+            if args.ordering:
+                engines["depth <= %d within %d, ordered" % (args.max_depth, b)] = LockstepEngine(
+                    model, G, sims, reply=MinimaxPlayer(False, search_depth=args.max_depth, node_budget=b, ordering=True))
         for eng in engines.values():
             eng.ctx.rollout_games(words, np.full(G, words.shape[1], np.int32), 1, args.opening_plies)
             eng.search_begin()
@@ -115,7 +121,7 @@ def main():
         if os.path.exists(args.out):
             with open(args.out) as f:
                 kept = json.load(f)
-        kept["node_budget"] = dict(out, budgets=budgets, max_depth=args.max_depth)
+        kept["ordering" if args.ordering else "node_budget"] = dict(out, budgets=budgets, max_depth=args.max_depth)
         out = kept
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
