@@ -119,6 +119,19 @@ __device__ inline void stage_wtile_x16(const unsigned char *wts, lds_byte *lds, 
     }
 }
 
+// piece j (of GL) of the same transfer alone: the rank-tile kernels may spread a tile's requests (CRL_TRUNK_DMA_PHASE)
+template <class G>
+__device__ inline void stage_wpiece_x16(const unsigned char *wts, lds_byte *lds, int t, int tid, int wave_u, int slot,
+                                        int j)
+{
+    const unsigned char *src = wts + (size_t)t * G::TILE_BYTES;
+    const int dst0 = G::WRING_OFF + slot * G::TILE_BYTES + wave_u * 1024;      // uniform
+    const unsigned off = (unsigned)((j * 512 + tid) * 16);
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) void *)(src + off),
+        (__attribute__((address_space(3))) void *)(lds + dst0 + j * 8192), 16, 0, 0);
+}
+
 // bias row of layer `conv` (F floats) -> LDS row conv & 1, by LDS-DMA: F/64 waves move 256 bytes each.
 // Being a DMA like the weight tiles it is covered by the same counted vmcnt waits and barriers; no
 // register, no ds_write and no compiler-inserted vmcnt(0) (which would drain the weight stream).
@@ -152,6 +165,68 @@ struct RankTiles {
     static constexpr bool value = CRL_TRUNK_RANKPAIR != 0 && F == 128 && NB == 4 && PAIR == 1 && GROUP == 0 &&
                                   SPLIT == 0 && IDX == 0;
 };
+
+// Rank tiles only: WHEN the waves of the upper rank half (w >= 4) request the weight tiles t+3, t+4 (and their share
+// of the next bias row) that a tap's sync frees the slots for.  Waves w and w + 4 share a SIMD and leave the sync's
+// barrier together; with 0 both then issue their four 1-KiB requests at once and neither feeds the MFMA pipe
+// meanwhile.  The lower half always issues directly behind the barrier; the upper half
+//   0  does the same (the schedule of round 10, and its assembly byte for byte),
+//   1  issues behind the first-half MFMAs of the sync's sub-step, while its partner is back in its MFMAs,
+//   2  issues a whole sub-step later, at the start of the next tap (a layer's last tap: as 1),
+//   3  issues when 2 does, but one piece behind each of the first two MFMAs of the sub-step's two halves.
+// Every request still follows the sync that frees its slot and precedes the next sync's vmcnt(0); no barrier and
+// no wait changes, the MFMAs and their order are the same, results are bit-identical.  (-1 is a seeded fault for
+// tools/lds_race_check.py: the upper half requests IN FRONT of the sync.  It exists as assembly on a CPU only.)
+// The library builds 2: -2.4 % of the 10 x 128 launch at 4096 boards against 0, -1.5 % with 1, -1.1 % with 3
+// (tools/ubench/trunk_r3.hip times the variants; docs/history/experiments.md, round 11).
+#ifndef CRL_TRUNK_DMA_PHASE
+#define CRL_TRUNK_DMA_PHASE 2
+#endif
+static_assert(CRL_TRUNK_DMA_PHASE >= -1 && CRL_TRUNK_DMA_PHASE <= 3, "CRL_TRUNK_DMA_PHASE: 0 .. 3");
+
+// What run_tap gets as its rank half where the half has a request schedule of its own: the sync whose requests are
+// not issued yet (its tile, its ring slot, whether the next bias row goes with them: plain integers, the taps are
+// straight-line code) and the function that issues pieces [P0, P1) of them.  Every other body gets a bare constant,
+// so the kernels without rank halves hold none of this.
+struct TrunkDmaSync { int t = 0, slot = 0; bool bias = false; };
+template <int HH, class P>
+struct RankHalfDma {
+    static constexpr int value = HH;
+    TrunkDmaSync &sync;
+    P &pieces;
+};
+// (through overloads: run_tap names them in statements that a body without a schedule of its own discards, but
+// the bare constant must still be a valid argument while that body is being instantiated)
+template <class H, class A, class B>
+__device__ __forceinline__ void half_pieces(const H &, A, B) {}
+template <int HH, class P, class A, class B>
+__device__ __forceinline__ void half_pieces(const RankHalfDma<HH, P> &h, A a, B b) { h.pieces(a, b); }
+template <class H>
+__device__ __forceinline__ void half_record(const H &, bool, int, int) {}
+template <int HH, class P>
+__device__ __forceinline__ void half_record(const RankHalfDma<HH, P> &h, bool bias, int t, int slot)
+{
+    h.sync.bias = bias;
+    h.sync.t = t;
+    h.sync.slot = slot;
+}
+
+#if defined(CRL_TRUNK_STAMPS)
+// Harness diagnostic (tools/ubench/trunk_r3.hip -DCRL_TRUNK_STAMPS, never in the library, phases 0 .. 2): every wave
+// of a rank-tile kernel sums, over its tap syncs, the cycles from the sync's vmcnt wait to the end of its barrier and
+// the cycles its weight requests take to issue, wherever the schedule puts them, and lane 0 stores the sums to a
+// buffer of their own that nothing reads: [loop, sync wait, requests, syncs, one stamp's own cost] per wave.  A stamp
+// drains the wave's LDS reads (s_memtime returns out of order with them), so the build is slower: read its shares.
+__device__ unsigned long long *crl_trunk_stamp_buf = nullptr;
+__device__ __forceinline__ unsigned long long trunk_stamp()
+{
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#endif
 
 //   planes  fp16 [n_boards][64][128], or 128 plane bitboards per board (BITS)
 //   wts     fp16 weight planes in consumption order [conv][tap][in-ch/32][F rows][4 chunks][8 in],
@@ -310,6 +385,11 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
 
     constexpr int HP = PT / 2;                          // position blocks per half sub-step
 
+#if defined(CRL_TRUNK_STAMPS)
+    static_assert(CRL_TRUNK_DMA_PHASE >= 0 && CRL_TRUNK_DMA_PHASE <= 2, "stamps: not between the MFMAs of phase 3");
+    unsigned long long st_wait = 0, st_req = 0, st_syncs = 0;
+    const unsigned long long st_t0 = trunk_stamp(), st_self = trunk_stamp() - st_t0;
+#endif
     int t = 0;                                          // tile of the K-step being computed
     int slot_tap = 0;                                   // PAIR: ring slot (t mod 5) of the tap's first tile
     auto slot_add = [](int s, int k) { const int x = s + k; return x >= 5 ? x - 5 : x; };
@@ -342,8 +422,16 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         // SK / NSK (rank tiles): block 0 of this tap / of the next tap is off the board as a whole.  Its
         // fragment xa[0] is not read and its CT MFMAs are not issued; every lgkmcnt immediate below counts the
         // reads that are really issued (xb is always HP reads, the next xa HP - its skip).
-        auto run_tap = [&](auto NSC, auto DUPC, bool first_tap, bool last_tap, auto SKC, auto NSKC) {
+        auto run_tap = [&](auto NSC, auto DUPC, bool first_tap, bool last_tap, auto SKC, auto NSKC, auto HHC) {
             constexpr int NS = decltype(NSC)::value, DUP = decltype(DUPC)::value;
+            // the request schedule of this body: the upper rank half's, if it has one of its own
+            constexpr int DPH = (RP && decltype(HHC)::value == 1) ? CRL_TRUNK_DMA_PHASE : 0;
+            constexpr int NP = 2 * G::GL;                // pieces per wave and sync: tiles t+3 and t+4
+            constexpr std::integral_constant<int, 0> p0{};
+            constexpr std::integral_constant<int, 1> p1{};
+            constexpr std::integral_constant<int, 2> p2{};
+            constexpr std::integral_constant<int, NP> pn{};
+            static_assert(DPH == 0 || (PAIR && NS == 4 && DUP == 1 && G::SPT == 2 && NP == 4), "one sync per tap, in sub-step 3");
             constexpr int SK = decltype(SKC)::value ? 1 : 0, NSK = decltype(NSKC)::value ? 1 : 0;
             static_assert(RP || (SK == 0 && NSK == 0), "whole blocks leave the board only with rank tiles");
             static_assert(DUP == 1 || (SPLIT && DUP == 2), "shared weight sub-steps belong to the split kernels");
@@ -400,9 +488,23 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                         // start of the last sub-step of an odd tile t: tiles t+1, t+2 (moved at the
                         // previous sync, the only transfers in flight) are published; tiles <= t-1
                         // are dead and their slots take tiles t+3, t+4
+                        if constexpr (DPH != 0) {         // the requests go out later (seeded fault: now)
+                            half_record(HHC, !bias_staged, t, slot_add(slot_tap, wi / G::SPT));
+                            bias_staged = true;
+                            if constexpr (DPH < 0) half_pieces(HHC, p0, pn);
+                        }
+#if defined(CRL_TRUNK_STAMPS)
+                        const unsigned long long s0 = trunk_stamp();
+#endif
                         wait_vmcnt<0>();
                         __builtin_amdgcn_s_barrier();
                         __builtin_amdgcn_sched_barrier(0);
+#if defined(CRL_TRUNK_STAMPS)
+                        const unsigned long long s1 = trunk_stamp();
+                        st_wait += s1 - s0;
+                        st_syncs++;
+#endif
+                        if constexpr (DPH == 0) {
                         if (!bias_staged) {
                             bias_staged = true;
                             if (conv + 1 < n_convs) stage_bias_x16<G, F>(bias, lds, conv + 1, lane, wave_u);
@@ -410,6 +512,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                         const int slot_cur = slot_add(slot_tap, wi / G::SPT);
                         if (t + 3 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 3, tid, wave_u, slot_add(slot_cur, 3));
                         if (t + 4 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 4, tid, wave_u, slot_add(slot_cur, 4));
+#if defined(CRL_TRUNK_STAMPS)
+                        st_req += trunk_stamp() - s1;
+#endif
+                        }
                     }
                 } else if constexpr (s == G::SPT - 1) {
                     // publish tile t+1 before the half that prefetches its first fragments;
@@ -424,16 +530,31 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     }
                     if (t + 3 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 3, tid, wave_u);
                 }
+                // phase 2: the previous tap's sync was a whole sub-step ago
+                if constexpr (DPH == 2 && i == 0) { if (!first_tap) half_pieces(HHC, p0, pn); }
                 // ---- half 0: position blocks [0, HP)
                 fetch_xb(IC);
                 wait_lgkm<HP>();                         // xa and w[cur] have landed
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (DPH == 3 && (i == 0 || i == NS - 1)) {     // phase 3: behind the half's first two MFMAs
+                    const bool now = i == 0 ? !first_tap : last_tap;
+                    static_for<SK * CT, HP * CT>([&](auto KC) {
+                        constexpr int k = decltype(KC)::value, pt = k / CT, ct = k % CT;
+                        acc[pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xa[pt], acc[pt][ct], 0, 0, 0);
+                        if constexpr (k == SK * CT) { if (now) half_pieces(HHC, p0, p1); }
+                        if constexpr (k == SK * CT + 1) { if (now) half_pieces(HHC, p1, p2); }
+                    });
+                } else {
 #pragma unroll
                 for (int pt = SK; pt < HP; pt++)
 #pragma unroll
                     for (int ct = 0; ct < CT; ct++)
                         acc[pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xa[pt], acc[pt][ct], 0, 0, 0);
+                }
                 __builtin_amdgcn_sched_barrier(0);
+                // phase 1 (and a layer's last tap in phase 2): the partner wave is back in its MFMAs
+                if constexpr (DPH == 1 && i == NS - 1) half_pieces(HHC, p0, pn);
+                if constexpr (DPH == 2 && i == NS - 1) { if (last_tap) half_pieces(HHC, p0, pn); }
                 // ---- half 1: position blocks [HP, PT); prefetch the next sub-step
                 constexpr bool wrap = i + 1 >= NS;
                 bool issued = false;
@@ -459,6 +580,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                             else fetch_w1(std::integral_constant<int, wi + 1>{}, KC, false, w[nxt]);
                         }
                         __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (DPH == 3 && k < 2 && (i == 0 || i == NS - 1)) {
+                        if (i == 0 ? !first_tap : last_tap)
+                            half_pieces(HHC, std::integral_constant<int, 2 + k>{}, std::integral_constant<int, 3 + k>{});
                     }
                 });
                 __builtin_amdgcn_sched_barrier(0);
@@ -599,6 +724,27 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 };
                 fresh();
                 vtap_rows(0, ab[1]);
+                // pieces [P0, P1) of the 2 GL that tiles t+3, t+4 of the recorded sync are, the bias row in front of piece 0
+                TrunkDmaSync dma_sync;
+                auto dma_pieces = [&](auto P0C, auto P1C) {
+                    __builtin_amdgcn_sched_barrier(0);
+#if defined(CRL_TRUNK_STAMPS)
+                    const unsigned long long s0 = trunk_stamp();
+#endif
+                    static_for<decltype(P0C)::value, decltype(P1C)::value>([&](auto PC) {
+                        constexpr int p = decltype(PC)::value, k = 3 + p / G::GL;
+                        if constexpr (p == 0) {
+                            if (dma_sync.bias && conv + 1 < n_convs) stage_bias_x16<G, F>(bias, lds, conv + 1, lane, wave_u);
+                        }
+                        if (dma_sync.t + k < n_tiles)
+                            stage_wpiece_x16<G>(wts, lds, dma_sync.t + k, tid, wave_u, slot_add(dma_sync.slot, k), p % G::GL);
+                    });
+#if defined(CRL_TRUNK_STAMPS)
+                    st_req += trunk_stamp() - s0;
+#endif
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                const RankHalfDma<hh, decltype(dma_pieces)> half{dma_sync, dma_pieces};
                 static_for<0, 9>([&](auto VC) {
                     constexpr int v = decltype(VC)::value;
                     constexpr bool sk = hh == 0 ? v < 3 : v >= 6;
@@ -608,7 +754,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     fresh();
                     vtap_rows(v + 1 < 9 ? v + 1 : 0, ab[1]);
                     run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == 8, std::integral_constant<bool, sk>{},
-                            std::integral_constant<bool, nsk>{});
+                            std::integral_constant<bool, nsk>{}, half);
                     slot_tap = slot_add(slot_tap, 4 / G::SPT);
                 });
             };
@@ -616,6 +762,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             else run_conv(std::integral_constant<int, 1>{});
         } else {
         constexpr std::false_type nsk{};
+        constexpr std::integral_constant<int, 0> nh{};  // no rank halves: one body
         vtap_rows(0, ab[1]);
         for (int v = 0; v < nv; v++) {
 #pragma unroll
@@ -630,11 +777,11 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             if (whi_twice) {
                 if constexpr (SPLIT) {
                     constexpr std::integral_constant<int, 2> twice{};
-                    if (F == 64) run_tap(std::integral_constant<int, 4>{}, twice, v == 0, v == nv - 1, nsk, nsk);
-                    else run_tap(std::integral_constant<int, 8>{}, twice, v == 0, v == nv - 1, nsk, nsk);
+                    if (F == 64) run_tap(std::integral_constant<int, 4>{}, twice, v == 0, v == nv - 1, nsk, nsk, nh);
+                    else run_tap(std::integral_constant<int, 8>{}, twice, v == 0, v == nv - 1, nsk, nsk, nh);
                 }
-            } else if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1, nsk, nsk);
-            else run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == nv - 1, nsk, nsk);
+            } else if (F == 64 && conv != 0) run_tap(std::integral_constant<int, 2>{}, once, v == 0, v == nv - 1, nsk, nsk, nh);
+            else run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == nv - 1, nsk, nsk, nh);
             if constexpr (PAIR) slot_tap = slot_add(slot_tap, 4 / G::SPT);
             // The fragments prefetched for the next tap are in flight across this loop's back-edge, where
             // hipcc -- which cannot see the inline-asm reads -- is free to COPY their registers (phi moves)
@@ -747,6 +894,16 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     }
+#if defined(CRL_TRUNK_STAMPS)
+    if constexpr (RP) {
+        const unsigned long long st_loop = trunk_stamp() - st_t0;
+        unsigned long long *dbg = crl_trunk_stamp_buf;
+        if (lane == 0 && dbg) {
+            dbg += ((size_t)blockIdx.x * 8 + wave_u) * 5;
+            dbg[0] = st_loop; dbg[1] = st_wait; dbg[2] = st_req; dbg[3] = st_syncs; dbg[4] = st_self;
+        }
+    }
+#endif
     if (!IDX && out) {
 #pragma unroll
         for (int pt = 0; pt < PT; pt++) {

@@ -22,6 +22,12 @@ wait that retires it).  Reported:
      (exact on the executed path: no path-feasibility guesswork);
   4. an address or branch that depends on an unknown value (the emulation would be meaningless).
 
+A DMA request need not follow the barrier that frees its slot at once: the rank-tile kernels let one rank half issue
+its requests some MFMAs later (tower_x16.hpp, CRL_TRUNK_DMA_PHASE).  The emulation executes the stream, so a request
+counts from where it is issued; per wave it also records how many MFMAs lie between a barrier and the first request
+behind it ("sync_to_dma_mfma_per_wave", tests/test_trunk_dma_phase_cpu.py).  A request issued IN FRONT of its sync is
+in flight in the epoch that still reads the slot: finding 1.
+
 The statistics printed per kernel count what was executed: instructions, barrier epochs, DMA transfers, LDS reads and
 writes and "mfma", the MFMA wave-instructions of the 8 waves (a 128-filter wave tile issues 576 per convolution, 528
 with the rank tiles that skip off-board blocks; tests/test_trunk_rank_tiles_cpu.py holds the kernels to that).
@@ -153,6 +159,7 @@ class Wave(object):
         self.n_exec = 0
         self.n_mfma = 0                           # MFMA wave-instructions executed
         self.asm_reads = []                       # lowest LDS byte of every inline-asm (fragment) ds_read
+        self.marks = []                           # ("barrier" | "dma", MFMAs executed so far), in program order
 
     # ---- register access -------------------------------------------------------------------------
     def exec_mask(self):
@@ -318,6 +325,7 @@ class Wave(object):
                         self.lgkm = self.lgkm[len(self.lgkm) - keep:] if keep else []
             elif op == "s_barrier":
                 self.events.append(["barrier", self.epoch])
+                self.marks.append(("barrier", self.n_mfma))
                 self.epoch += 1
             elif op in ("s_nop", "s_setprio", "s_sleep", "s_sethalt", "s_waitcnt_depctr", "s_setreg_imm32_b32"):
                 pass
@@ -560,6 +568,7 @@ class Wave(object):
             addr = (base + sz * np.arange(64, dtype=np.int64))[lanes]
             by = (addr[:, None] + np.arange(sz, dtype=np.int64)[None, :]).ravel()
             self.vm.append(len(self.events))
+            self.marks.append(("dma", self.n_mfma))
             self.events.append(["dma", self.epoch, by, None, text])      # [3] = epoch of the retiring vmcnt wait
         elif "load" in op:
             self.vsrc(t[1])
@@ -808,6 +817,18 @@ class Wave(object):
             self.vunknown(t[0])
 
 
+def sync_to_dma(marks):
+    """For every barrier with a DMA request before the next barrier: the MFMAs between it and the first such request."""
+    out, at = [], None
+    for kind, n in marks:
+        if kind == "barrier":
+            at = n
+        elif at is not None:
+            out.append(n - at)
+            at = None
+    return out
+
+
 def check_workgroup(ins, labels, n_blocks, lds_bytes=160 * 1024, want_out=False, listed=None, kernarg=None, ring_at=None):
     """Emulate the 8 waves of workgroup 0 and cross-check their LDS traffic epoch by epoch.
     ``ring_at``: LDS offset of the weight ring; the statistics then also count, per wave, the fragment reads
@@ -879,6 +900,8 @@ def check_workgroup(ins, labels, n_blocks, lds_bytes=160 * 1024, want_out=False,
         stats["mfma_per_wave"] = [w.n_mfma for w in waves]
         stats["act_frag_reads_per_wave"] = [sum(1 for a in w.asm_reads if a < ring_at) for w in waves]
         stats["w_frag_reads_per_wave"] = [sum(1 for a in w.asm_reads if a >= ring_at) for w in waves]
+        stats["dma_per_wave"] = [sum(1 for k, _ in w.marks if k == "dma") for w in waves]
+        stats["sync_to_dma_mfma_per_wave"] = [sync_to_dma(w.marks) for w in waves]
     return findings, stats
 
 

@@ -7,8 +7,15 @@
 // Round 7: the rank tiles of the 128-filter NB = 4 kernel (tower_x16.hpp, CRL_TRUNK_RANKPAIR).  The default build
 // times them; -DCRL_TRUNK_RANKPAIR=0 builds the board tiles of before into a second binary.  Alternate the two
 // binaries in ONE run on ONE device (MATCH selects rows by name): devices differ by up to 12 % on MFMA loops.
+// Round 11: when the upper rank half of that kernel requests its weight tiles (tower_x16.hpp, CRL_TRUNK_DMA_PHASE:
+// 0 = with its partner wave, directly behind the tap's sync; 1 = half a sub-step later; 2 = a whole sub-step later;
+// 3 = piece by piece over four half sub-steps).  Build -DCRL_TRUNK_DMA_PHASE=0 beside the default (and 1 .. 3 to
+// compare them) and alternate the binaries as above; the last column is a hash of head_out, equal across all of them.
+// -DCRL_TRUNK_STAMPS (with -DCRL_TRUNK_DMA_PHASE=0 .. 2) adds a diagnostic section: in-kernel cycle stamps around the tap
+// sync and around the weight requests, per rank half (tower_x16.hpp).  Read that build's shares, never its run time.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I chessrl_amd/csrc tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3
 // hipcc ... -DCRL_TRUNK_RANKPAIR=0 tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3_boards
+// hipcc ... -DCRL_TRUNK_DMA_PHASE=0 tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3_phase0
 //   [MATCH="x16<128,4> pair (production)"] ./trunk_r3 [boards=4096] [reps=20]
 #include "tower_x16.hpp"
 #include <cmath>
@@ -74,8 +81,10 @@ static double run(const char *name, kern_t k, int lds, int nb, int F, int blocks
     CK(hipMemcpy(out.data(), b.head_out, out.size() * 4, hipMemcpyDeviceToHost));
     const double flops = 2.0 * (73152.0 * F + 1152.0 * F * F * blocks + 192.0 * F) * boards;
     const bool same = ref && memcmp(ref->data(), out.data(), out.size() * 4) == 0;
-    printf("%-44s %8.4f ms  %7.1f TFLOP/s (algorithmic)  frac %.3f  %s\n", name, best, flops / best / 1e9,
-           flops / best / 1e9 / 2500.0, !ref ? "reference" : (same ? "bit-identical" : "DIFFERENT"));
+    uint64_t h = 1469598103934665603ull;                // FNV-1a of head_out: comparable across binaries
+    for (size_t i = 0; i < out.size() * 4; i++) h = (h ^ reinterpret_cast<const unsigned char *>(out.data())[i]) * 1099511628211ull;
+    printf("%-44s %8.4f ms  %7.1f TFLOP/s (algorithmic)  frac %.3f  %s  %016llx\n", name, best, flops / best / 1e9,
+           flops / best / 1e9 / 2500.0, !ref ? "reference" : (same ? "bit-identical" : "DIFFERENT"), (unsigned long long)h);
     fflush(stdout);
     return best;
 }
@@ -92,6 +101,34 @@ int main(int argc, char **argv)
         run("x16<128,4> pair (production)", k_trunk_x16<128, 4, 1, 0, 1>, lds, 4, 128, 10, boards, reps, b, ref, nullptr);
         run("x16<128,4> pair (production) again", k_trunk_x16<128, 4, 1, 0, 1>, lds, 4, 128, 10, boards, reps, b, out, &ref);
     }
+#if defined(CRL_TRUNK_STAMPS)
+    {   // per wave [loop, sync wait, requests, syncs, one stamp]: means over the workgroups, per rank half (waves 0-3 / 4-7)
+        Bufs b = make(128, 10, boards, 1);
+        const int lds = Geo16<128, 4>::lds_bytes(ring_slots<4, 1, 0>()), n_wg = boards / 4;
+        const size_t n_dbg = (size_t)n_wg * 8 * 5;
+        unsigned long long *d_dbg;
+        CK(hipMalloc(&d_dbg, n_dbg * 8));
+        CK(hipMemset(d_dbg, 0, n_dbg * 8));
+        CK(hipMemcpyToSymbol(HIP_SYMBOL(crl_trunk_stamp_buf), &d_dbg, sizeof d_dbg));
+        CK(hipFuncSetAttribute((const void *)k_trunk_x16<128, 4, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        for (int i = 0; i < 3; i++)
+            hipLaunchKernelGGL((k_trunk_x16<128, 4, 1, 0, 1>), dim3(n_wg), dim3(512), lds, 0, b.planes, b.wts, b.bias, nullptr, 10, b.head_w, b.head_b, b.head_out);
+        CK(hipDeviceSynchronize());
+        std::vector<unsigned long long> dbg(n_dbg);
+        CK(hipMemcpy(dbg.data(), d_dbg, n_dbg * 8, hipMemcpyDeviceToHost));
+        for (int half = 0; half < 2; half++) {
+            double sum[5] = {0, 0, 0, 0, 0};
+            for (int wg = 0; wg < n_wg; wg++)
+                for (int w = 4 * half; w < 4 * half + 4; w++)
+                    for (int k = 0; k < 5; k++) sum[k] += (double)dbg[((size_t)wg * 8 + w) * 5 + k];
+            const double nw = 4.0 * n_wg, syncs = sum[3] / nw, self = sum[4] / nw;
+            printf("stamps phase %d, rank half %d, mean per wave: loop %.0f cycles, %.0f tap syncs; per sync: vmcnt wait + barrier %.0f, "
+                   "weight requests %.0f (one stamp's own %.0f taken off each); per convolution of 9 taps: %.0f and %.0f of %.0f\n",
+                   CRL_TRUNK_DMA_PHASE, half, sum[0] / nw, syncs, sum[1] / nw / syncs - self, sum[2] / nw / syncs - self, self,
+                   9 * (sum[1] / nw / syncs - self), 9 * (sum[2] / nw / syncs - self), sum[0] / nw / 21);
+        }
+    }
+#endif
     {
         Bufs b = make(256, 20, boards, 1);
         printf("== 20 x 256, %d boards\n", boards);
