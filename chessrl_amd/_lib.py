@@ -69,6 +69,7 @@ SYMBOLS = [
     "crl_opponent_moves_ord", "crl_sim_reply_opponent_ord",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
+    "crl_advance_one",
 ]
 
 
@@ -208,6 +209,7 @@ def lib():
     L.crl_sim_backup.argtypes = [vp, vp, vp]
     L.crl_root_children.argtypes = [vp] * 8
     L.crl_advance.argtypes = [vp, vp, vp, vp]
+    L.crl_advance_one.argtypes = [vp, vp, vp]
     L.crl_counters.argtypes = [vp, vp]
     L.crl_end_move_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.crl_advance_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -621,6 +623,15 @@ class Context(object):
         am = np.zeros(self.G, np.uint16)
         self._ck(self._L.crl_advance(self._h, _ptr(c), _ptr(bm), _ptr(am)), "crl_advance")
         return bm, am
+
+    def advance_one(self, chosen):
+        """``advance`` by ONE ply: our move is played and the stored reply is not (the other side moves for itself);
+        returns bm."""
+        c = np.ascontiguousarray(chosen, dtype=np.int32)
+        assert c.shape == (self.G,)
+        bm = np.zeros(self.G, np.uint16)
+        self._ck(self._L.crl_advance_one(self._h, _ptr(c), _ptr(bm)), "crl_advance_one")
+        return bm
 
     def end_move_fetch(self, dev_policy_s2, dev_value_s2):
         """sim_backup + root children (nchild, visits, root_visits) + plies in one synchronising call."""

@@ -627,6 +627,16 @@ int crl_advance(crl_ctx *ctx, const int32_t *chosen, uint16_t *bm, uint16_t *am)
     return check_dev_error(ctx);
 }
 
+int crl_advance_one(crl_ctx *ctx, const int32_t *chosen, uint16_t *bm)
+{
+    ENTER(ctx, chosen);
+    const size_t G = ctx->W;
+    HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, chosen, G));
+    LAUNCH(ctx, k_advance_one, ctx->d, (const int32_t *)ctx->t_i32b, ctx->t_u16a);
+    HIP_TRY(ctx, to_host(ctx, bm, ctx->t_u16a, G));
+    return check_dev_error(ctx);
+}
+
 // ---- the move boundary in two synchronising calls (SelfPlayRunner.end_move) --------------------------------
 int crl_end_move_fetch(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32, int32_t *nchild,
                        int32_t *visits, int32_t *root_visits, int32_t *plies)

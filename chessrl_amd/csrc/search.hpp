@@ -10,6 +10,7 @@
 //   k_backup           simulate + backprop + child priors     mctree.py:259-303
 //   k_root_children    [c.visits for c in root.children]      mctree.py:178,313-315
 //   k_advance          gam.move(bm); gam.move(am)             selfplay.py:77-78
+//   k_advance_one      gam.move(bm) alone                     gameagent.py, benchmark.py:100-118
 //   k_encode_cur       netencoder.get_game_state              netencoder.py:72-91
 //   k_legal/k_push/... Game.get_legal_moves/move/get_result   game.py:28-57,92-109
 //   k_greedy           AgentDistributed.best_move(real_game)  agentdistributed.py:56-58
@@ -836,6 +837,9 @@ __global__ __launch_bounds__(64) void k_root_children(Dev d, int32_t *nchild, in
 
 // gam.move(bm); gam.move(am) (selfplay.py:77-78) with the moves of root child c, reached over edge record ed: the
 // game goes on by one ply (the game ended on our move) or two, to ply np; the tree is consumed.  One lane.
+// ONE_PLY: gam.move(bm) alone (k_advance_one) -- a child with a reply stops at S1, which is a running position
+// (a node gets its reply only where the game went on after our move); am is not written.
+template <bool ONE_PLY = false>
 __device__ inline void advance_game(const Dev &d, int g, int r, int c, const Edge &ed, const NodeMeta &cm, int np,
                                     u16 *bm, u16 *am)
 {
@@ -846,6 +850,13 @@ __device__ inline void advance_game(const Dev &d, int g, int r, int c, const Edg
     d.hist_hash[hi] = n.h1;
     d.rec_moves[(size_t)g * d.MAXPLY + p] = ed.move;
     bm[r] = ed.move;
+    if (ONE_PLY && cm.has_s2) {
+        d.cur[g] = n.s1;
+        d.game[g].ply = np;
+        d.game[g].game_result = RESULT_NONE;
+        d.game[g].root_dead = 1;
+        return;
+    }
     if (cm.has_s2) {
         hi = (size_t)g * HIST_RING + ((p + 2) & (HIST_RING - 1));
         d.hist[hi] = n.s2;
@@ -875,6 +886,27 @@ __global__ __launch_bounds__(64) void k_advance(Dev d, const int32_t *chosen, u1
     const int np = d.game[g].ply + (cm.has_s2 ? 2 : 1);
     if (np > d.MAXPLY) { dev_error(d, DERR_PLY_POOL); return; }
     advance_game(d, g, r, c, ed, cm, np, bm, am);
+}
+
+// gam.move(bm) alone: Agent.best_move in a game whose other side moves for itself (gameagent.py, benchmark.py:100-118).
+// k_advance's checks; the game goes on by ONE ply, to S1 of the chosen child, and the tree is consumed.  A child
+// without a reply ended the game on our move: exactly k_advance's outcome.
+__global__ __launch_bounds__(64) void k_advance_one(Dev d, const int32_t *chosen, u16 *bm)
+{
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    if (lane != 0) return;
+    bm[r] = NO_MOVE;
+    const int k = chosen[r];
+    if (k < 0 || d.game[g].root_dead) return;
+    const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
+    NodeMeta m = d.node[nb].meta;
+    if (k >= m.nexp || d.game[g].leaf_kind != LEAF_NONE) { dev_error(d, DERR_STATE); return; }
+    const Edge ed = d.edge[eb + m.edge0 + (m.nmoves - 1 - k)];
+    const int c = ed.child & CHILD_NONE;
+    NodeMeta cm = d.node[nb + c].meta;
+    const int np = d.game[g].ply + 1;
+    if (np > d.MAXPLY) { dev_error(d, DERR_PLY_POOL); return; }
+    advance_game<true>(d, g, r, c, ed, cm, np, bm, nullptr);
 }
 
 // ---- Tree(Node) (mctree.py:98-111): the chosen child becomes the root and keeps its subtree --------------------

@@ -650,8 +650,23 @@ class LockstepEngine(object):
     def root_children(self):
         return self.ctx.root_children()
 
-    def advance(self, chosen):
-        return self.ctx.advance(chosen)
+    def advance(self, chosen, plies=2):
+        """Play the chosen root children.  ``plies=2`` (default): our move and the reply stored in the tree,
+        returns (bm, am).  ``plies=1``: our move alone -- the other side moves for itself and its move arrives
+        through ``ctx.push_moves`` -- returns bm; only on a plain leaf-mode engine with a fresh tree per move."""
+        if plies == 2:
+            return self.ctx.advance(chosen)
+        if plies != 1:
+            raise ValueError("advance: plies must be 1 or 2")
+        # the one-ply boundary belongs to a game whose other side searches for itself: nothing that answers for it
+        # (reply=), keeps a tree rooted two plies on (max_nodes above max_sims + 1) or runs waves is covered
+        if self.reply is not None:
+            raise ValueError("advance(plies=1): the engine was created with reply=, which plays the reply itself")
+        if self.max_nodes != self.max_sims + 1:
+            raise ValueError("advance(plies=1): max_nodes above max_sims + 1 is tree reuse, which stays two-ply")
+        if self.threads > 1:
+            raise ValueError("advance(plies=1): not with threads > 1")
+        return self.ctx.advance_one(chosen)
 
     def reroot(self, chosen, next_sims):
         """``advance`` that keeps the chosen child's subtree in every slot where kept nodes + ``next_sims`` fit

@@ -195,6 +195,13 @@ int  crl_root_children(crl_ctx *ctx, int32_t *nchild /*G*/, int32_t *visits, dou
  * (children-order index, -1 = leave the slot alone).  bm/am (host, may be NULL) get our
  * move and the stored reply (CRL_NO_MOVE when the game ended on our move). */
 int  crl_advance(crl_ctx *ctx, const int32_t *chosen /*G*/, uint16_t *bm, uint16_t *am);
+/* gam.move(bm) alone: Agent.best_move in a game whose other side moves for itself (gameagent.py,
+ * benchmark.py:100-118).  crl_advance's checks and its bm; the game goes on by ONE ply, to the position after
+ * our move, and the stored reply is not played: the other side's move comes from its own search and
+ * arrives through crl_push_moves.  The tree is consumed.  A child on which the game ended is played
+ * exactly as by crl_advance.  Window-relative like crl_advance; bm (host, may be NULL).
+ * (An addition that changes no existing signature: still 9.) */
+int  crl_advance_one(crl_ctx *ctx, const int32_t *chosen /*G*/, uint16_t *bm /*G*/);
 /* The move boundary of the lockstep runner in TWO synchronising calls instead of five (a synchronisation costs
  * ~70 us; at C2 a move is 13 ms).  crl_end_move_fetch = crl_sim_backup + crl_root_children(nchild, visits,
  * root_visits) + len(Game) of every slot; the host then computes the policies (compute_policy, mctree.py:305-322)
