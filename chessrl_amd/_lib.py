@@ -70,6 +70,7 @@ SYMBOLS = [
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
     "crl_advance_one",
+    "crl_advance_one_argmax", "crl_push_moves_dev",
 ]
 
 
@@ -210,6 +211,8 @@ def lib():
     L.crl_root_children.argtypes = [vp] * 8
     L.crl_advance.argtypes = [vp, vp, vp, vp]
     L.crl_advance_one.argtypes = [vp, vp, vp]
+    L.crl_advance_one_argmax.argtypes = [vp, i32, vp, vp, vp]
+    L.crl_push_moves_dev.argtypes = [vp, vp, vp]
     L.crl_counters.argtypes = [vp, vp]
     L.crl_end_move_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.crl_advance_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -516,6 +519,12 @@ class Context(object):
         self._ck(self._L.crl_push_moves(self._h, _ptr(m), _ptr(ok)), "crl_push_moves")
         return ok
 
+    def push_moves_dev(self, dev_moves, dev_ok=None):
+        """``push_moves`` with the moves in device memory (uint16 [G], a tensor or an address) and no synchronisation;
+        ``dev_ok`` (uint8 [G], device) may be None.  A refused move is a device error at the next synchronising call."""
+        self._ck(self._L.crl_push_moves_dev(self._h, _Dev(dev_moves, "dev_moves").p, _Dev(dev_ok, "dev_ok", None).p),
+                 "crl_push_moves_dev")
+
     def push_sequences(self, moves, counts):
         """Every game replays its own move list (one launch); returns the number applied per game."""
         m = np.ascontiguousarray(moves, dtype=np.uint16)
@@ -632,6 +641,13 @@ class Context(object):
         bm = np.zeros(self.G, np.uint16)
         self._ck(self._L.crl_advance_one(self._h, _ptr(c), _ptr(bm)), "crl_advance_one")
         return bm
+
+    def advance_one_argmax(self, mover_white, dev_ply_limit, dev_bm, dev_chosen):
+        """The noise-free one-ply boundary on the device (``crl_advance_one_argmax``): device int32 [G] ply limits in,
+        device uint16 [G] moves and int32 [G] chosen children out; asynchronous."""
+        self._ck(self._L.crl_advance_one_argmax(
+            self._h, 1 if mover_white else 0, _Dev(dev_ply_limit, "dev_ply_limit").p, _Dev(dev_bm, "dev_bm").p,
+            _Dev(dev_chosen, "dev_chosen").p), "crl_advance_one_argmax")
 
     def end_move_fetch(self, dev_policy_s2, dev_value_s2):
         """sim_backup + root children (nchild, visits, root_visits) + plies in one synchronising call."""

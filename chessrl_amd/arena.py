@@ -25,6 +25,15 @@ and has played fewer than ``max_plies`` plies after its opening.  No refill, no 
 GREEDY ARENA (``sims=0``): the reference's ``best_move(real_game=True)`` on both sides -- one context per set, the
 tower of the side to move, ``greedy_moves(policy, mask, push=True)`` as ``benchmark`` does on the agent's plies.
 
+DEVICE BOUNDARY (``boundary="device"``, ``sims`` > 0, no noise).  Per ply and set the mover runs ``search(sims)`` and
+``advance_argmax`` -- ``k_choose_advance_one``: the first maximum of the root children's visits in children order,
+which is what ``choose_children(noise=False)`` chooses at every ply count, and the one-ply advance, in one kernel --
+and the mirror takes ``bm`` from device memory (``push_moves_dev``).  The only host round trip of a ply is the
+``records(with_moves=False)`` that the termination test reads.  ``boundary="host"`` (default) is the path above.
+
+EARLY END.  ``Arena.play(until=f)`` calls ``f(results by game number)`` after every ply of both sets; a true return
+ends the play, and the games still running are reported as unfinished (``gating`` stops a decided gate so).
+
 NOISE.  Off by default.  ``noise=True``: game ``i`` draws its Dirichlet rows from ``np.random.default_rng([seed, i])``,
 one row per searched ply, whichever side searches.
 
@@ -55,6 +64,27 @@ def check_arguments(games, sims, openings, opening_plies, max_plies):
         raise ValueError("opening_plies must not be negative")
     if max_plies < 1:
         raise ValueError("max_plies must be at least 1")
+
+
+BOUNDARIES = ("host", "device")
+
+
+def check_boundary(boundary, noise, sims, model_a=None, model_b=None):
+    """The refusals of ``Arena(..., boundary=...)``, before any device is touched.  The device boundary plays the first
+    maximum of the visits, which is the noise-free choice only; it belongs to the searching arena; and the two engines
+    of a set hand their moves over in device memory in stream order, so both must sit on one device's stream."""
+    if boundary not in BOUNDARIES:
+        raise ValueError("boundary must be one of %s" % (BOUNDARIES,))
+    if boundary == "host":
+        return
+    if noise:
+        raise ValueError('boundary="device" chooses the most visited child: not with noise=True')
+    if sims == 0:
+        raise ValueError('boundary="device" is the boundary of a search: not with sims=0 (the greedy arena)')
+    dev_a, dev_b = getattr(model_a, "device", None), getattr(model_b, "device", None)
+    if dev_a is not None and dev_b is not None and str(dev_a) != str(dev_b):
+        raise ValueError('boundary="device": the two engines of a set must be on one stream, the evaluators are on '
+                         "%s and %s" % (dev_a, dev_b))
 
 
 def game_colours(games):
@@ -140,6 +170,7 @@ class _Set(object):
         self.ctx = None                      # sims = 0
         self.planes = None
         self.rngs = None
+        self.ply_limit = None                # boundary="device": int32 per slot on the device
 
     def main_ctx(self):
         return self.ctx if self.ctx is not None else self.engines["a"].ctx
@@ -151,12 +182,14 @@ class Arena(object):
     ``arena`` returns; ``close()`` frees the device state."""
 
     def __init__(self, model_a, model_b, games=2, sims=0, seed=0, opening_plies=6, openings=None, max_plies=512,
-                 noise=False, use_graph=True, device=None):
+                 noise=False, use_graph=True, device=None, boundary="host"):
         check_arguments(games, sims, openings, opening_plies, max_plies)
+        check_boundary(boundary, noise, sims, model_a, model_b)
         import torch
         self.models = {"a": model_a, "b": model_b}
         self.games, self.sims, self.seed, self.noise = int(games), int(sims), seed, bool(noise)
-        self.max_plies, self.use_graph = int(max_plies), use_graph
+        self.max_plies, self.use_graph, self.boundary = int(max_plies), use_graph, boundary
+        self.plies_played = 0                    # plies of the play so far (both sets have played that many)
         pairs = self.games // 2
         specs = None if openings is None else [parse_opening(o) for o in openings]
         if device is None:
@@ -182,6 +215,9 @@ class Arena(object):
                         s.engines[who] = LockstepEngine(self.models[who], pairs, self.sims, device=index,
                                                         max_plies=max(pool, 2), use_graph=use_graph)
                         _load(s.engines[who].ctx, specs)
+                    if boundary == "device":     # a game is searched while it has played fewer plies than this
+                        limit = np.array([len(ids) + self.max_plies for _, ids in specs], dtype=np.int32)
+                        s.ply_limit = torch.from_numpy(limit).to(self.dev)
                 else:
                     s.ctx = _lib.Context(pairs, 1, max_plies=max(pool, 2), device=index)
                     s.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
@@ -220,6 +256,19 @@ class Arena(object):
             bm = eng.advance(chosen, plies=1)
             s.engines[other].ctx.push_moves(bm)              # the mirror follows; NO_MOVE slots are left alone
 
+    def _search_ply_device(self, s, movers):
+        """``_search_ply`` without the host between search and move: the choice and the advance are one kernel
+        (``LockstepEngine.advance_argmax``) and the mirror takes the moves from device memory, in stream order."""
+        for who, other in (("a", "b"), ("b", "a")):
+            if not movers[who].any():
+                continue
+            eng = s.engines[who]
+            eng.search(self.sims)
+            bm, _ = eng.advance_argmax(s.a_white == (who == "a"), s.ply_limit)
+            mirror = s.engines[other]
+            mirror._bind_stream()
+            mirror.ctx.push_moves_dev(bm)
+
     def _greedy_ply(self, s, movers):
         s.ctx.encode(s.planes.data_ptr())
         for who in ("a", "b"):
@@ -228,7 +277,10 @@ class Arena(object):
                 policy = self.models[who](s.planes)[0].float().contiguous()
                 s.ctx.greedy_moves(policy.data_ptr(), mask=mask, push=True, want_moves=False)
 
-    def play(self):
+    def play(self, until=None):
+        """Plays the games out and returns the report.  ``until``: called after every ply of both sets with the
+        results by game number (1 / 0 / -1 for white, None for a running game); a true return ends the play, and the
+        games still running are reported as unfinished.  ``plies_played`` counts the plies."""
         state = []
         for s in self.sets:
             ctx = s.main_ctx()
@@ -244,13 +296,29 @@ class Arena(object):
                 if not live.any():
                     continue
                 movers = self._movers(s, live, white)
-                if self.sims > 0:
+                if self.sims > 0 and self.boundary == "device":
+                    self._search_ply_device(s, movers)
+                elif self.sims > 0:
                     self._search_ply(s, movers, plies)
                 else:
                     self._greedy_ply(s, movers)
                 _, st[0], st[1] = s.main_ctx().records(with_moves=False)
                 st[2] = np.where(live, ~white, white)
+            self.plies_played += 1
+            if until is not None and until(self._results_by_number(state)):
+                break
+        if self.boundary == "device":            # the mirrors' own device errors (a refused move) surface here
+            for s in self.sets:
+                s.engines["b"].ctx.sync()
         return self._report()
+
+    def _results_by_number(self, state):
+        out = [None] * self.games
+        for s, st in zip(self.sets, state):
+            for slot, number in enumerate(s.numbers):
+                r = int(st[1][slot])
+                out[number] = None if r == _lib.RESULT_NONE else r
+        return out
 
     def _report(self):
         games = [None] * self.games
@@ -269,17 +337,19 @@ class Arena(object):
 
 
 def arena(model_a, model_b, games=2, sims=0, seed=0, opening_plies=6, openings=None, max_plies=512, noise=False,
-          use_graph=True, device=None):
+          use_graph=True, device=None, boundary="host"):
     """Plays ``games`` games (even: pairs on a shared opening, colours exchanged) between the ready evaluators
     ``model_a`` and ``model_b`` with ``sims`` simulations per move (0: both sides greedy) and returns
     ``dict(played, a_won, b_won, drawn, unfinished, score_a, as_white, games)``: ``score_a = (a_won + drawn / 2) /
     played``, ``as_white`` the same counts over A's white games, ``games`` a list of ``dict(a_white, opening, moves,
     result)`` -- the opening as UCI moves or its FEN, the moves played after it as UCI strings, the result 1 / 0 / -1
     for white or None.  A game still running after ``max_plies`` plies past its opening is played, unfinished and
-    scored as nothing.  Module docstring: pairs, openings, engines, noise."""
+    scored as nothing.  ``boundary="device"``: the noise-free move boundary without the host.  Module docstring: pairs,
+    openings, engines, noise, boundary."""
     check_arguments(games, sims, openings, opening_plies, max_plies)
+    check_boundary(boundary, noise, sims, model_a, model_b)
     ar = Arena(model_a, model_b, games=games, sims=sims, seed=seed, opening_plies=opening_plies, openings=openings,
-               max_plies=max_plies, noise=noise, use_graph=use_graph, device=device)
+               max_plies=max_plies, noise=noise, use_graph=use_graph, device=device, boundary=boundary)
     try:
         return ar.play()
     finally:

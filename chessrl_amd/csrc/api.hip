@@ -637,7 +637,24 @@ int crl_advance_one(crl_ctx *ctx, const int32_t *chosen, uint16_t *bm)
     return check_dev_error(ctx);
 }
 
-// ---- the move boundary in two synchronising calls (SelfPlayRunner.end_move) --------------------------------
+// ---- the noise-free one-ply boundary without the host: choice and advance in one kernel, its moves pushed into the
+// mirror context from device memory (the arena's boundary="device").  Neither call synchronises.
+int crl_advance_one_argmax(crl_ctx *ctx, int mover_white, const int32_t *dev_ply_limit, uint16_t *dev_bm,
+                           int32_t *dev_chosen)
+{
+    ENTER(ctx, dev_ply_limit && dev_bm && dev_chosen);
+    LAUNCH(ctx, k_choose_advance_one, ctx->d, mover_white ? 1 : 0, dev_ply_limit, dev_bm, dev_chosen);
+    return CRL_OK;
+}
+
+int crl_push_moves_dev(crl_ctx *ctx, const uint16_t *dev_moves, uint8_t *dev_ok)
+{
+    ENTER(ctx, dev_moves);
+    LAUNCH(ctx, k_push_dev, ctx->d, (const u16 *)dev_moves, dev_ok);
+    return CRL_OK;
+}
+
+// ---- the move boundary in two synchronising calls (SelfPlayRunner.end_move)--------------------------------
 int crl_end_move_fetch(crl_ctx *ctx, const void *dev_policy_s2_f32, const void *dev_value_s2_f32, int32_t *nchild,
                        int32_t *visits, int32_t *root_visits, int32_t *plies)
 {

@@ -11,7 +11,8 @@
 //   k_root_children    [c.visits for c in root.children]      mctree.py:178,313-315
 //   k_advance          gam.move(bm); gam.move(am)             selfplay.py:77-78
 //   k_advance_one      gam.move(bm) alone                     gameagent.py, benchmark.py:100-118
-//   k_encode_cur       netencoder.get_game_state              netencoder.py:72-91
+//   k_choose_advance_one  argmax of compute_policy + gam.move(bm)   gameagent.py, mctree.py:305-322
+//   k_encode_cur       netencoder.get_game_state             netencoder.py:72-91
 //   k_legal/k_push/... Game.get_legal_moves/move/get_result   game.py:28-57,92-109
 //   k_greedy           AgentDistributed.best_move(real_game)  agentdistributed.py:56-58
 //
@@ -369,6 +370,24 @@ __global__ __launch_bounds__(64) void k_push(Dev d, const u16 *moves, uint8_t *o
     Board b = d.cur[g];
     const bool legal = is_legal_move(b, mv, lane, s);
     if (lane == 0) ok[r] = legal ? 1 : 0;
+    if (legal) game_push(d, g, b, mv, lane, s);
+}
+
+// k_push with nobody waiting for ok[]: the moves come from another context's move boundary on the same stream
+// (k_choose_advance_one's bm), ok may be NULL, and a refused move is a device error that the next synchronising call
+// reports.
+__global__ __launch_bounds__(64) void k_push_dev(Dev d, const u16 *moves, uint8_t *ok)
+{
+    __shared__ WaveLds s;
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    const u32 mv = moves[r];
+    if (mv == NO_MOVE) { if (lane == 0 && ok) ok[r] = 0; return; }
+    Board b = d.cur[g];
+    const bool legal = is_legal_move(b, mv, lane, s);
+    if (lane == 0) {
+        if (ok) ok[r] = legal ? 1 : 0;
+        if (!legal) dev_error(d, DERR_STATE);
+    }
     if (legal) game_push(d, g, b, mv, lane, s);
 }
 
@@ -906,6 +925,49 @@ __global__ __launch_bounds__(64) void k_advance_one(Dev d, const int32_t *chosen
     NodeMeta cm = d.node[nb + c].meta;
     const int np = d.game[g].ply + 1;
     if (np > d.MAXPLY) { dev_error(d, DERR_PLY_POOL); return; }
+    advance_game<true>(d, g, r, c, ed, cm, np, bm, nullptr);
+}
+
+// The noise-free move boundary of a game whose two sides search for themselves, without the host in between
+// (gameagent.py; the choice is compute_policy + np.argmax, mctree.py:305-322): k_root_children, the host's
+// choose_children(noise=False) and k_advance_one in one kernel.  One wavefront per slot.  A slot MOVES iff its tree is
+// alive, its game has no result, ply < ply_limit[r], the side to move is mover_white and the root has an expanded
+// child.  The chosen child is the FIRST MAXIMUM of the root children's visits in children order (reverse legal order
+// over the nexp expanded children): the policy visits**(1/tau) / root_visits**(1/tau) is strictly increasing in visits
+// for every tau, and np.argmax takes the first maximum.  The slot is then advanced as k_advance_one advances that
+// child.  bm[r] / chosen[r] (device): the move and the child, NO_MOVE / -1 for a slot that does not move -- its state
+// is untouched.
+__global__ __launch_bounds__(64) void k_choose_advance_one(Dev d, int mover_white, const int32_t *ply_limit, u16 *bm,
+                                                           int32_t *chosen)
+{
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    if (lane == 0) { bm[r] = NO_MOVE; chosen[r] = -1; }
+    if (uni(d.game[g].root_dead) || uni(d.game[g].game_result) != RESULT_NONE) return;
+    const int p = uni(d.game[g].ply);
+    if (p >= uni(ply_limit[r]) || (int)st_turn(uni(d.cur[g].state)) != (mover_white ? 1 : 0)) return;
+    const size_t nb = (size_t)g * d.N, eb = (size_t)g * d.ECAP;
+    const NodeMeta m = d.node[nb].meta;
+    const int nexp = uni((int)m.nexp), first = uni((int)m.edge0) + uni((int)m.nmoves) - 1;
+    if (nexp < 1) return;
+    int best = -1, bk = 0x7FFFFFFF;                                     // lane-strided scan: roots have up to 218 children
+    for (int k = lane; k < nexp; k += 64) {
+        const int v = d.edge[eb + first - k].visits;
+        if (v > best) { best = v; bk = k; }                            // ascending k: the first maximum of this lane
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int ov = __shfl_xor(best, o), ok = __shfl_xor(bk, o);
+        if (ov > best || (ov == best && ok < bk)) { best = ov; bk = ok; }
+    }
+    if (lane != 0) return;
+    const int k = bk;
+    if (k >= nexp || d.game[g].leaf_kind != LEAF_NONE) { dev_error(d, DERR_STATE); return; }
+    const Edge ed = d.edge[eb + first - k];
+    const int c = ed.child & CHILD_NONE;
+    const NodeMeta cm = d.node[nb + c].meta;
+    const int np = p + 1;
+    if (np > d.MAXPLY) { dev_error(d, DERR_PLY_POOL); return; }
+    chosen[r] = k;
     advance_game<true>(d, g, r, c, ed, cm, np, bm, nullptr);
 }
 

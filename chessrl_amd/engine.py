@@ -658,6 +658,10 @@ class LockstepEngine(object):
             return self.ctx.advance(chosen)
         if plies != 1:
             raise ValueError("advance: plies must be 1 or 2")
+        self._require_one_ply()
+        return self.ctx.advance_one(chosen)
+
+    def _require_one_ply(self):
         # the one-ply boundary belongs to a game whose other side searches for itself: nothing that answers for it
         # (reply=), keeps a tree rooted two plies on (max_nodes above max_sims + 1) or runs waves is covered
         if self.reply is not None:
@@ -666,7 +670,25 @@ class LockstepEngine(object):
             raise ValueError("advance(plies=1): max_nodes above max_sims + 1 is tree reuse, which stays two-ply")
         if self.threads > 1:
             raise ValueError("advance(plies=1): not with threads > 1")
-        return self.ctx.advance_one(chosen)
+
+    def advance_argmax(self, mover_white, ply_limit):
+        """``root_children()``, ``choose_children(noise=False)`` and ``advance(chosen, plies=1)`` in one kernel and
+        without the host (``crl_advance_one_argmax``).  A slot moves iff its tree is alive, its game has no result,
+        it has played fewer than ``ply_limit[slot]`` plies (int32 per slot; a device tensor is taken as it is), the
+        side to move is ``mover_white`` and its root has an expanded child; it plays the first maximum of the root
+        children's visits in children order.  Returns ``(bm, chosen)`` as DEVICE tensors on the current stream --
+        int16 [G] holding the uint16 move ids (``NO_MOVE`` where the slot did not move) and int32 [G] (-1 there) --
+        and does not synchronise.  Refuses the engines ``advance(plies=1)`` refuses."""
+        self._require_one_ply()
+        if not torch.is_tensor(ply_limit):
+            ply_limit = torch.from_numpy(np.ascontiguousarray(ply_limit, dtype=np.int32)).to(self.dev)
+        if ply_limit.dtype != torch.int32 or tuple(ply_limit.shape) != (self.G,) or ply_limit.device != self.dev:
+            raise ValueError("advance_argmax: ply_limit must be int32 [%d] on %s" % (self.G, self.dev))
+        self._bind_stream()
+        bm = torch.empty((self.G,), dtype=torch.int16, device=self.dev)
+        chosen = torch.empty((self.G,), dtype=torch.int32, device=self.dev)
+        self.ctx.advance_one_argmax(bool(mover_white), ply_limit.contiguous(), bm, chosen)
+        return bm, chosen
 
     def reroot(self, chosen, next_sims):
         """``advance`` that keeps the chosen child's subtree in every slot where kept nodes + ``next_sims`` fit

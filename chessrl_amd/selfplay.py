@@ -13,6 +13,10 @@ does not depend on the number of GPUs.
 157-163): one epoch over the games just played, one batch per game.
 The CLI keeps ``modeldir --games --threads --debug`` and adds the knobs the reference hard-codes
 (``--sims`` 900 in selfplay.py:76, net size, parallel games, ``--rounds`` of play+train).
+
+``--gate-games N`` puts a gate between a round's training and the next round (``gated_round``, ``chessrl_amd.gating``):
+the trained weights are a candidate that has to beat the weights it was trained from in the arena before the run adopts
+them.  Without the flag every trained set is adopted, as in the reference.
 """
 import argparse
 import logging
@@ -562,7 +566,99 @@ def train_weights(weights, records, device, model_dir=None, epochs=1, batch_size
     return trainer.weights(), history
 
 
-TRAINER_STREAM_PRIORITY = 0       # the background trainer's HIP stream (a high priority, -1, was measured: no effect)
+# ---- the gate of ``--rounds --gate-games N``: a trained set is adopted only if it beats the set it was trained from ----
+GATE_CARRY_ROUNDS = 4             # a rejected round's games train the next candidates too, for this many rounds at most
+GATE_LOG = "gate_log.jsonl"
+GATE_LOG_KEYS = ("round", "candidate", "accepted", "score", "threshold", "played", "a_won", "b_won", "drawn",
+                 "unfinished", "games", "sims", "seed", "stopped_at_ply", "seconds", "trained_on",
+                 "precision_candidate", "precision_incumbent")
+
+
+def save_weights_file(weights, path):
+    """``ChessModel.save_weights`` of a weight dict: ``.h5`` = a Keras weight file, else ``.npz``."""
+    if str(path).endswith((".h5", ".hdf5")):
+        from .keras_h5 import save_keras_h5
+        save_keras_h5(weights, path)
+    else:
+        np.savez(path, **weights)
+
+
+def device_gate(settings, incumbent_model=None):
+    """The ``gate_fn`` of a real round: the incumbent evaluator is the playing model itself (its runner is closed at a
+    round's end), the candidate a second ``ChessModel`` that lives for the gate only."""
+    def gate_fn(candidate, incumbent):
+        from .gating import gate
+        from .model import ChessModel
+        kw = dict(device=settings["device"]) if settings.get("device") is not None else {}
+        if settings.get("precision") is not None:
+            kw["precision"] = settings["precision"]
+        cand = ChessModel(weights=candidate, **kw)
+        inc = incumbent_model if incumbent_model is not None else ChessModel(weights=incumbent, **kw)
+        try:
+            return gate(cand, inc, settings["games"], settings["sims"], threshold=settings["threshold"],
+                        seed=settings["seed"], opening_plies=settings["opening_plies"],
+                        max_plies=settings["max_plies"], **settings.get("gate_options", {}))
+        finally:
+            del cand, inc
+    return gate_fn
+
+
+def gated_round(weights, new_records, carried, settings, train_fn=None, gate_fn=None):
+    """One round's training and gate, free of devices where ``train_fn`` and ``gate_fn`` are: returns ``(weights,
+    carried, entry)``.
+
+    The candidate is trained from ``weights`` on ``carried + new_records`` -- ``train_fn(weights, records) ->
+    (candidate, history)``, by default ``train_weights``: a fresh optimizer, the arithmetic of ``train_model_job``,
+    the playing model untouched -- and plays the incumbent: ``gate_fn(candidate, weights) -> dict`` with ``accepted``
+    (``gating.gate``'s result).  ACCEPTED: the candidate is returned, written to ``settings["model_path"]`` and handed
+    to ``settings["on_accept"]`` (the playing model's in-place ``load_dict``); ``carried`` is emptied.  REJECTED: the
+    incumbent is returned, the file and the playing tensors stay, and ``carried`` gains this round's records, capped at
+    the last ``GATE_CARRY_ROUNDS`` rounds -- a rejected round's games are not wasted and a run that never passes does
+    not grow without bound.  With no trainable game there is no candidate and no gate (the round counts as rejected).
+    ``carried`` is a list of per-round record lists.  ``settings``: round, model_path, model_dir, games, sims,
+    threshold, seed, opening_plies, max_plies (and device, precision, on_accept).  One JSON line per round goes to
+    ``model_dir/gate_log.jsonl`` (``GATE_LOG_KEYS``); ``entry`` is that line."""
+    import json
+    records = [r for rnd in carried for r in rnd] + list(new_records)
+    trained_on = len(trainable_records(records))
+    entry = dict.fromkeys(GATE_LOG_KEYS)
+    entry.update(round=settings["round"], candidate=False, accepted=False, threshold=float(settings["threshold"]),
+                 games=int(settings["games"]), sims=int(settings["sims"]), seed=settings["seed"],
+                 trained_on=trained_on)
+    candidate = None
+    if trained_on > 0:
+        if train_fn is None:
+            def train_fn(w, recs):
+                return train_weights(w, recs, settings.get("device") or "cuda:0", model_dir=settings["model_dir"])
+        candidate, history = train_fn(weights, records)
+        if gate_fn is None:
+            gate_fn = device_gate(settings)
+        out = gate_fn(candidate, weights)
+        entry["candidate"] = True
+        for k in GATE_LOG_KEYS:
+            if k in out and k not in ("round", "games", "candidate", "trained_on"):
+                entry[k] = out[k]
+        entry["accepted"] = bool(out["accepted"])
+    if entry["accepted"]:
+        save_weights_file(candidate, settings["model_path"])
+        if settings.get("on_accept") is not None:
+            settings["on_accept"](candidate)
+        weights, carried = candidate, []
+        log.info("round %d: gate ACCEPTED the candidate (score %.3f against %.3f, %d games trained on)",
+                 entry["round"], entry["score"], entry["threshold"], trained_on)
+    else:
+        carried = (list(carried) + [list(new_records)])[-GATE_CARRY_ROUNDS:]
+        if candidate is None:
+            log.info("round %d: no trainable game, so no candidate and no gate; the weights stay", entry["round"])
+        else:
+            log.info("round %d: gate REJECTED the candidate (score %.3f against %.3f); the weights stay and the "
+                     "round's games are carried over", entry["round"], entry["score"], entry["threshold"])
+    with open(os.path.join(settings["model_dir"], GATE_LOG), "a") as f:
+        f.write(json.dumps(entry) + "\n")
+    return weights, carried, entry
+
+
+TRAINER_STREAM_PRIORITY = 0      # the background trainer's HIP stream (a high priority, -1, was measured: no effect)
 
 
 class BackgroundTrainer(object):
@@ -748,7 +844,33 @@ def build_parser():
                         help="arithmetic of the PUCT term 10 * prior (mctree.py:79-87): 'legacy' = the float64 "
                              "product of the reference's pinned numpy 1.17.2, 'nep50' = the float32 product "
                              "of numpy >= 2, 'auto' = whichever the installed numpy computes")
+    parser.add_argument("--gate-games", type=int, default=0,
+                        help="--rounds: after every round the trained weights play this many arena games (even: "
+                             "paired openings) against the weights they were trained from and are adopted only if "
+                             "they reach --gate-threshold; a rejected round's games train the next candidate too.  "
+                             "0 = no gate: every trained set is adopted.  Not with --rolling or --no-train")
+    parser.add_argument("--gate-sims", type=int, default=None,
+                        help="simulations per move in the gate's games (default: min(--sims, 100))")
+    parser.add_argument("--gate-threshold", type=float, default=0.55,
+                        help="the candidate's score (wins + draws / 2, a game cut off counts as a draw) that adopts it")
+    parser.add_argument("--gate-opening-plies", type=int, default=6, help="random plies in front of every gate pair")
+    parser.add_argument("--gate-max-plies", type=int, default=512, help="plies searched per gate game after its opening")
     return parser
+
+
+def check_gate_args(parser, args):
+    """The refusals of the gate flags (``parser.error``) and the default of ``--gate-sims``."""
+    if args.gate_games < 0 or args.gate_games % 2:
+        parser.error("--gate-games must be even (games 2i and 2i + 1 share an opening with the colours exchanged)")
+    if args.gate_games and args.rolling:
+        parser.error("--gate-games cannot be combined with --rolling: rolling rounds are ungated")
+    if args.gate_games and args.no_train:
+        parser.error("--gate-games cannot be combined with --no-train: there is no candidate to gate")
+    if args.gate_sims is None:
+        args.gate_sims = min(args.sims, 100)
+    if args.gate_sims < 0:
+        parser.error("--gate-sims must not be negative")
+    return args
 
 
 def main(argv=None):
@@ -757,6 +879,7 @@ def main(argv=None):
     # --virtual-loss asks for the wave kind whatever --threads says
     if args.reuse_tree and "tree_reuse" not in COVERS["wave" if args.virtual_loss else "leaf"]:
         parser.error("--virtual-loss cannot be combined with --reuse-tree")
+    check_gate_args(parser, args)
     logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO)
 
     import datetime
@@ -784,9 +907,12 @@ def main(argv=None):
     weights = path if os.path.exists(path) else None
     model = ChessModel(compile_model=not args.no_train, weights=weights, blocks=args.blocks,
                        filters=args.filters, device="cuda:%d" % local, seed=args.seed, precision=args.precision)
+    if args.gate_games and rank == 0 and weights is None:
+        model.save_weights(path)                  # a gated run may adopt nothing: its incumbent is on file from the start
     per_rank = (args.games + world - 1) // world
     parallel = args.parallel or min(per_rank, 4096)
     allrecs = []
+    gate_carried = []                             # --gate-games: the records of the rounds rejected since the last adoption
     max_plies = args.max_plies
     dp = args.train_mode == "dp" and world > 1 and args.rolling and not args.no_train
     # (data-parallel: the trainer THREADS of all ranks talk over a process group of their own -- a communicator
@@ -818,7 +944,16 @@ def main(argv=None):
             # the reference trains in ONE process; here rank 0 trains on every rank's games and the
             # new weights go to the other ranks over RCCL (one broadcast per round).  The inference
             # tensors are rewritten in place: hipGraphs of running engines stay valid
-            if rank == 0:
+            if rank == 0 and args.gate_games:
+                # the gate (``gated_round``): the candidate is trained beside the playing model and replaces it -- in
+                # place, and in the file -- only if it beats it; the broadcast below ships whichever set won
+                settings = dict(round=rnd, model_path=path, model_dir=args.model_dir, games=args.gate_games,
+                                sims=args.gate_sims, threshold=args.gate_threshold, seed=args.seed + rnd,
+                                opening_plies=args.gate_opening_plies, max_plies=args.gate_max_plies,
+                                device="cuda:%d" % local, precision=args.precision, on_accept=model.load_dict)
+                _, gate_carried[:], _ = gated_round(model.weights, newrecs, list(gate_carried), settings,
+                                                    gate_fn=device_gate(settings, incumbent_model=model))
+            elif rank == 0:
                 t0 = time.perf_counter()
                 hist = train_model_job(model, newrecs, path, args.model_dir)
                 log.info("round %d: trained on %d games in %.1fs: %s", rnd, len(newrecs),

@@ -202,6 +202,22 @@ int  crl_advance(crl_ctx *ctx, const int32_t *chosen /*G*/, uint16_t *bm, uint16
  * exactly as by crl_advance.  Window-relative like crl_advance; bm (host, may be NULL).
  * (An addition that changes no existing signature: still 9.) */
 int  crl_advance_one(crl_ctx *ctx, const int32_t *chosen /*G*/, uint16_t *bm /*G*/);
+/* The noise-free one-ply boundary without the host (gameagent.py; the choice is compute_policy followed by
+ * np.argmax, mctree.py:305-322): crl_root_children, the choice and crl_advance_one in one kernel.  A slot moves iff its
+ * tree is alive, its game has no result, its ply count is below dev_ply_limit[g], the side to move is mover_white
+ * (1 white, 0 black) and its root has an expanded child.  The chosen child is the first maximum of the root
+ * children's visits in CHILDREN order -- what the policy visits**(1/tau) / root_visits**(1/tau) and np.argmax choose
+ * for every tau, since the policy is strictly increasing in visits.  The slot is advanced as by crl_advance_one.
+ * dev_bm[g] / dev_chosen[g] (DEVICE memory): the move and the child, CRL_NO_MOVE / -1 for a slot that does not move
+ * and whose state is untouched.  Asynchronous on the context's stream; window-relative; a device error shows at the
+ * next synchronising call.  (An addition that changes no existing signature: still 9.) */
+int  crl_advance_one_argmax(crl_ctx *ctx, int mover_white, const int32_t *dev_ply_limit /*G*/,
+                            uint16_t *dev_bm /*G*/, int32_t *dev_chosen /*G*/);
+/* crl_push_moves with the moves already in DEVICE memory (crl_advance_one_argmax's dev_bm of the mirror context, on
+ * the same stream) and no synchronisation: Game.move (game.py:28-41) per slot, CRL_NO_MOVE skips.  dev_ok (device,
+ * may be NULL) gets 1/0.  A refused move is a device error (CRL_ERR_STATE) at the next synchronising call.
+ * (An addition that changes no existing signature: still 9.) */
+int  crl_push_moves_dev(crl_ctx *ctx, const uint16_t *dev_moves /*G*/, uint8_t *dev_ok /*G, may be NULL*/);
 /* The move boundary of the lockstep runner in TWO synchronising calls instead of five (a synchronisation costs
  * ~70 us; at C2 a move is 13 ms).  crl_end_move_fetch = crl_sim_backup + crl_root_children(nchild, visits,
  * root_visits) + len(Game) of every slot; the host then computes the policies (compute_policy, mctree.py:305-322)
