@@ -67,6 +67,7 @@ SYMBOLS = [
     "crl_rollout_games", "crl_rollout", "crl_opponent_moves", "crl_sim_reply_opponent",
     "crl_opponent_moves_q", "crl_sim_reply_opponent_q", "crl_opponent_moves_id", "crl_sim_reply_opponent_id",
     "crl_opponent_moves_ord", "crl_sim_reply_opponent_ord",
+    "crl_opponent_moves_rep", "crl_sim_reply_opponent_rep",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
     "crl_advance_one",
@@ -252,6 +253,8 @@ def lib():
     L.crl_sim_reply_opponent_id.argtypes = [vp, vp, i32, ctypes.c_int64, vp, vp, vp, vp]
     L.crl_opponent_moves_ord.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, vp, vp, vp, vp, vp]
     L.crl_sim_reply_opponent_ord.argtypes = [vp, vp, i32, ctypes.c_int64, i32, vp, vp, vp, vp]
+    L.crl_opponent_moves_rep.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp, vp]
+    L.crl_sim_reply_opponent_rep.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     L.crl_wave_config.argtypes = [vp, i32]
     L.crl_wave_begin.argtypes = [vp, i32]
@@ -580,13 +583,23 @@ class Context(object):
                                        ctypes.c_void_p(dev_planes_s2)), "crl_sim_reply")
 
     def sim_reply_opponent(self, dev_depths, node_limit, dev_planes_s2, dev_nodes, dev_cuts, quiescence=0,
-                           node_budget=None, dev_depth_sum=None, ordering=False):
+                           node_budget=None, dev_depth_sum=None, ordering=False, repetition=False):
         """``sim_reply`` with the built-in opponent's move as the reply: device pointers to int32 [count] depths, the
         planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies; ``quiescence`` plies (0 ..
         OPP_MAX_QUIESCENCE) past the depth.  ``node_budget`` (not None): iterative deepening up to the depths under
         ``min(node_budget, node_limit)`` nodes per reply, ``dev_depth_sum`` the int64 [count] accumulator of the
         completed depths.  ``ordering`` (needs a ``node_budget``): the budgeted search with ORDERING (csrc/opponent.hpp),
-        ``crl_sim_reply_opponent_ord``; False calls the entry it called."""
+        ``crl_sim_reply_opponent_ord``; False calls the entry it called.  ``repetition`` (needs a ``node_budget``): the
+        budgeted search with REPETITION (a repeated position below the root is a draw), ``crl_sim_reply_opponent_rep``;
+        False calls the entry it called."""
+        if repetition:
+            if node_budget is None:
+                raise ValueError("repetition needs a node_budget")
+            self._ck(self._L.crl_sim_reply_opponent_rep(
+                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)),
+                1 if ordering else 0, 1, ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes),
+                ctypes.c_void_p(dev_cuts), ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_rep")
+            return
         if ordering:
             if node_budget is None:
                 raise ValueError("ordering needs a node_budget")
@@ -735,16 +748,20 @@ class Context(object):
 
     # ---- the built-in opponent (csrc/opponent.hpp; stockfish.py:23-31, gamestockfish.py:27-41) ------
     def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT, quiescence=0, node_budget=None,
-                       ordering=False):
+                       ordering=False, repetition=False):
         """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it,
         with ``quiescence`` plies (0 .. OPP_MAX_QUIESCENCE, one value per call) of quiescence search past the depth.
         Returns (moves u16, scores i32, nodes i64, flags u8); with ``push`` the moves are played.  ``node_budget`` (not
         None): iterative deepening, ``depths`` the maximum depths, under ``min(node_budget, node_limit)`` nodes per
         slot; returns (moves, scores, nodes, flags, depths_done i32).  ``ordering`` (needs a ``node_budget``): that
         search with ORDERING (csrc/opponent.hpp: victims first, then the killer moves of the ply), through
-        ``crl_opponent_moves_ord``; False calls the entry it called."""
+        ``crl_opponent_moves_ord``; False calls the entry it called.  ``repetition`` (needs a ``node_budget``): that
+        search with REPETITION (a position below the root that occurred before, on the path or in the slot's reversible
+        history, is worth 0), through ``crl_opponent_moves_rep``; False calls the entry it called."""
         if ordering and node_budget is None:
             raise ValueError("ordering needs a node_budget")
+        if repetition and node_budget is None:
+            raise ValueError("repetition needs a node_budget")
         dp = np.ascontiguousarray(depths, dtype=np.int32)
         assert dp.shape == (self.G,)
         moves = np.zeros(self.G, np.uint16)
@@ -753,6 +770,12 @@ class Context(object):
         flags = np.zeros(self.G, np.uint8)
         if node_budget is not None:
             done = np.zeros(self.G, np.int32)
+            if repetition:
+                self._ck(self._L.crl_opponent_moves_rep(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
+                                                        min(int(node_budget), int(node_limit)), 1 if ordering else 0, 1,
+                                                        _ptr(moves), _ptr(scores), _ptr(nodes), _ptr(flags), _ptr(done)),
+                         "crl_opponent_moves_rep")
+                return moves, scores, nodes, flags, done
             if ordering:
                 self._ck(self._L.crl_opponent_moves_ord(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
                                                         min(int(node_budget), int(node_limit)), 1, _ptr(moves),

@@ -844,12 +844,14 @@ int crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t 
 
 // ITERATIVE DEEPENING under a node budget (csrc/opponent.hpp): kernels of their own, so the calls above launch what
 // they launched
-// (ordering = 1: ORDERING of csrc/opponent.hpp, the _ido kernels; 0 launches the _id kernels, whoever calls)
+// (ordering = 1: ORDERING of csrc/opponent.hpp, the _ido kernels; 0 launches the _id kernels, whoever calls;
+// repetition = 1: REPETITION, the _idr / _idor kernels; 0 launches what the call launched without it)
 static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depths, int quiescence, int push,
-                             int64_t node_budget, int ordering, uint16_t *moves, int32_t *scores, int64_t *nodes,
-                             uint8_t *flags, int32_t *depths_done)
+                             int64_t node_budget, int ordering, int repetition, uint16_t *moves, int32_t *scores,
+                             int64_t *nodes, uint8_t *flags, int32_t *depths_done)
 {
-    ENTER(ctx, depths && moves && node_budget >= 1 && (ordering == 0 || ordering == 1));
+    ENTER(ctx, depths && moves && node_budget >= 1 && (ordering == 0 || ordering == 1) &&
+                   (repetition == 0 || repetition == 1));
     if (quiescence < 0 || quiescence > CRL_OPP_MAX_QUIESCENCE)
         return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
     const size_t G = ctx->W;
@@ -858,7 +860,19 @@ static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depth
             return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a depth outside 0 .. CRL_OPP_MAX_DEPTH");
     long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
     HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
-    if (ordering && quiescence > 0)
+    if (repetition && ordering && quiescence > 0)
+        LAUNCH(ctx, k_opponent_moves_idor_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
+               (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    else if (repetition && ordering)
+        LAUNCH(ctx, k_opponent_moves_idor, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_budget,
+               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    else if (repetition && quiescence > 0)
+        LAUNCH(ctx, k_opponent_moves_idr_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
+               (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    else if (repetition)
+        LAUNCH(ctx, k_opponent_moves_idr, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_budget,
+               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    else if (ordering && quiescence > 0)
         LAUNCH(ctx, k_opponent_moves_ido_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
                (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
     else if (ordering)
@@ -881,26 +895,46 @@ static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depth
 int crl_opponent_moves_id(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
                           uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
 {
-    return opponent_moves_id(ctx, "crl_opponent_moves_id", depths, quiescence, push, node_budget, 0, moves, scores,
-                             nodes, flags, depths_done);
+    return opponent_moves_id(ctx, "crl_opponent_moves_id", depths, quiescence, push, node_budget, 0, 0, moves,
+                             scores, nodes, flags, depths_done);
 }
 
 int crl_opponent_moves_ord(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
                            int ordering, uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags,
                            int32_t *depths_done)
 {
-    return opponent_moves_id(ctx, "crl_opponent_moves_ord", depths, quiescence, push, node_budget, ordering, moves,
+    return opponent_moves_id(ctx, "crl_opponent_moves_ord", depths, quiescence, push, node_budget, ordering, 0, moves,
                              scores, nodes, flags, depths_done);
 }
 
-int crl_sim_reply_opponent_ord(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
-                               int ordering, void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
-                               uint64_t *dev_depth_sum_u64)
+int crl_opponent_moves_rep(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
+                           int ordering, int repetition, uint16_t *moves, int32_t *scores, int64_t *nodes,
+                           uint8_t *flags, int32_t *depths_done)
+{
+    return opponent_moves_id(ctx, "crl_opponent_moves_rep", depths, quiescence, push, node_budget, ordering, repetition,
+                             moves, scores, nodes, flags, depths_done);
+}
+
+int crl_sim_reply_opponent_rep(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, int repetition, void *dev_planes_s2, uint64_t *dev_nodes_u64,
+                               uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
 {
     ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
                    node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
-                   (ordering == 0 || ordering == 1));
-    if (ordering && quiescence > 0)
+                   (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1));
+    if (repetition && ordering && quiescence > 0)
+        LAUNCH(ctx, k_reply_opponent_idor_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    else if (repetition && ordering)
+        LAUNCH(ctx, k_reply_opponent_idor, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    else if (repetition && quiescence > 0)
+        LAUNCH(ctx, k_reply_opponent_idr_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    else if (repetition)
+        LAUNCH(ctx, k_reply_opponent_idr, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
+               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    else if (ordering && quiescence > 0)
         LAUNCH(ctx, k_reply_opponent_ido_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
                (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
     else if (ordering)
@@ -913,6 +947,14 @@ int crl_sim_reply_opponent_ord(crl_ctx *ctx, const int32_t *dev_depths_i32, int 
         LAUNCH(ctx, k_reply_opponent_id, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
                (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
     return CRL_OK;
+}
+
+int crl_sim_reply_opponent_ord(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                               uint64_t *dev_depth_sum_u64)
+{
+    return crl_sim_reply_opponent_rep(ctx, dev_depths_i32, quiescence, node_budget, ordering, 0, dev_planes_s2,
+                                      dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
 }
 
 int crl_sim_reply_opponent_id(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,

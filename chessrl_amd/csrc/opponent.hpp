@@ -125,6 +125,42 @@
 // value up needs no board to decide whether a cut sets a killer, and lane 0 stores the pair with the frame's own
 // cursor, best and alpha.  The partition is the seven ballots of 4c per 64 moves and two more that find the killers: a
 // killer class holds at most one move.  (tests/ordering_util.py restates this section.)
+//
+// REPETITION (the _idr and _idor kernels only; it requires ITERATIVE DEEPENING, so a node budget, and everything in
+// ITERATIVE DEEPENING, QUIESCENCE and ORDERING holds; it combines freely with quiescence and with ordering).
+//     One step is added to NODE VALUE for the node at search ply k >= 1, after steps 1-3 (the moves are generated
+//     first: one node, counted and tested against the budget like any other; a result -- mate, stalemate,
+//     insufficient material, the fifty-move claim, the 75-move rule -- takes precedence with the value it has):
+//         3b. no result, and the position of this node has occurred before: the value is 0.
+//     Such a node searches no move, takes no stand-pat, no evaluation and no frame, and sets no killer.  3b comes
+//     before 4 / 4a / 4b / 4c: a quiescence node that would have stood pat at or above beta is a draw first.
+//     Occurred before: an earlier position with the same side to move has the same _transposition_key -- piece
+//     placement, turn, castling rights, and the en-passant square only where a capture there is legal (bit 20 as
+//     wave_movegen derives it).  The earlier position is looked for
+//         among the positions of the search path at plies k - 4, k - 6, .. >= 0, the root included, and
+//         beyond the root among the positions that led to it: for crl_opponent_moves* the game's history ring; for
+//         the reply kernels the tree path of the pending node (S1 / S2 of its ancestors) and then the game's ring,
+//         which is what past_ref resolves.
+//     Only the node's reversible plies can hold it: distances 4, 6, .. up to its halfmove clock (a running node has
+//     clock < 100, so the 256-ply ring always suffices).  ONE earlier occurrence is enough; the game itself still ends
+//     on the fifth, as the reference's does.  The root is never tested.  The value is 0 at every ply and for either
+//     side: no contempt.  The decision is exact: the 64-bit hash is a filter, same_key on the boards decides, as in
+//     count_prior.
+// Consequences.  (a) The search is still minimax over its tree; a node's value now also depends on its path, and there
+// is no transposition table, so nothing is shared between paths: with a budget nothing reaches, move, score, flag and
+// depth_done with ordering on and off are equal, only `nodes` differs.  (b) From a root with halfmove clock 0 and
+// D + Q <= 3 no node can be a repetition (the shortest distance is 4 and only reversible plies count): every output,
+// `nodes` included, equals the search without REPETITION.  (c) The answer is a function of the root, its reversible
+// history and the arguments; for the games form that is still a function of the slot's state alone.
+// Structure.  No dependent HBM read per node: once per search the hashes of the root's reversible history, min(root
+// clock, 99) positions as far as they exist, are copied into LDS through past_ref (at most 99 x 8 B; the copy survives
+// the iterations), and beside them live, per ply that has a frame, the hash of the node's key-normalised board and its
+// state word with the derived en-passant bit (the frame's board has it clear: apply_move builds it so).  The node's own
+// bit comes from the MoveGenInfo of the movegen it runs anyway.  Per node the lanes compare the node's hash at the
+// distances 4, 6, .. in parallel, against the path's plies where the distance stays inside the search and against the
+// history copy beyond; a board is read (a frame's from LDS, a history one from the ring or the tree) only on a hash
+// hit.  These arrays lie outside the union game_push reuses.  LDS: 3.6 KiB + 864 B = 4 512 B (_idr, _idor) and
+// 6.5 KiB + 928 B = 7 616 B (their _q forms).  (tests/repetition_util.py restates this section.)
 #pragma once
 #include "search.hpp"
 
@@ -151,6 +187,19 @@ union OppLds {
     OppFrame f[QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1];
     WaveLds w;                             // game_push, after the search
 };
+
+// REPETITION: what lives beside the frames.  hh[i - 1] is the hash of the position i plies before the root (i = 1 ..
+// the root's reversible history, at most OPP_REP_WINDOW); ph[k] / ps[k] are the hash of the key-normalised board of
+// the node that holds frame k and its state word with the derived en-passant bit.
+constexpr int OPP_REP_WINDOW = 99;
+template <bool QS>
+struct OppRepLds {
+    u64 hh[OPP_REP_WINDOW];
+    u64 ph[QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1];
+    u32 ps[QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1];
+};
+// ... and where the root stands: at tree ply `tp` of slot g (0: the game's current position), whose game ply is `ply`
+struct OppRepRoot { const Dev *d; int g, tp, ply; };
 
 // a wave-uniform board read from LDS, moved to scalar registers
 __device__ inline Board uni_board(const Board &x)
@@ -347,17 +396,29 @@ __device__ inline void opp_move_to_front(u16 *mv, int n, u32 pm, int lane)
 // ID, D = Dmax throughout, depth_done is not set and every line marked ID folds away.
 // ORD: ORDERING of the header comment, on top of ID; NF is the number of frames behind f (their killers are cleared
 // here).  Every line marked ORD folds away without it.
+// REP: REPETITION of the header comment, on top of ID; rs and rr are read only then.  Every line marked REP folds away
+// without it.
 struct OppResult { u32 mv; int score; long long nodes; bool done; int depth_done; };
 
-template <bool QS, bool ID = false, bool ORD = false>
-__device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long long limit, OppFrame *f, int lane)
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false>
+__device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long long limit, OppFrame *f, int lane,
+                                       OppRepLds<QS> *rs = nullptr, OppRepRoot rr = OppRepRoot())
 {
     static_assert(ID || !ORD, "ORDERING requires ITERATIVE DEEPENING");
+    static_assert(ID || !REP, "REPETITION requires ITERATIVE DEEPENING");
+    int K = 0;                                             // REP: the positions behind the root that hh holds
     if (ORD) {                                             // both killers of every ply: NO_MOVE
         constexpr int NF = QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1;
         if (lane < NF) f[lane].killers = ((u32)NO_MOVE << 16) | (u32)NO_MOVE;
-        __syncthreads();
     }
+    if (REP) {                                             // the root's reversible history, as far as it exists
+        const int c0 = (int)st_clock(root.state);
+        K = c0 < OPP_REP_WINDOW ? c0 : OPP_REP_WINDOW;
+        const int have = rr.tp + (rr.ply < HIST_RING - 1 ? rr.ply : HIST_RING - 1);
+        if (K > have) K = have;
+        for (int i = lane + 1; i <= K; i += 64) rs->hh[i - 1] = *past_ref(*rr.d, rr.g, rr.tp - i, rr.ply, rr.ply).h;
+    }
+    if (ORD || REP) __syncthreads();
     Board b = root;
     int k = 0, a = -OPP_INF, be = OPP_INF, v = 0, root_best = -OPP_INF;
     u32 best_mv = NO_MOVE, first_mv = NO_MOVE;
@@ -379,7 +440,36 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
         const int n = uni(mi.n);
         const int res = uni(position_result(b, n, mi.in_check, 1));
         bool have_v = true;
+        bool rep_hit = false;                              // REP: step 3b
+        u64 nh = 0;                                        // REP: the hash and the state of the key-normalised node
+        u32 ns = 0;
+        if (REP && res == RESULT_NONE) {
+            const int clock = (int)st_clock(b.state);      // (< 100: no result)
+            if (!horizon || (k >= 1 && clock >= 4)) {
+                Board nb = b;
+                nb.state = ns = (b.state & ~(1u << 20)) | ((uni((int)mi.ep_legal) ? 1u : 0u) << 20);
+                nh = board_hash(nb);
+                if (k >= 1 && clock >= 4) {
+                    const int dist = 2 * (lane + 2);       // 4, 6, .. 130 >= clock: one pass
+                    bool hit = false;
+                    if (dist <= clock && dist <= k) {      // on the path: ply k - dist, its frame's board
+                        const int j = k - dist;
+                        if (rs->ph[j] == nh) {
+                            Board o = f[j].b;
+                            o.state = rs->ps[j];
+                            hit = same_key(o, nb);
+                        }
+                    } else if (dist <= clock && dist - k <= K) {           // behind the root
+                        const int hd = dist - k;
+                        if (rs->hh[hd - 1] == nh)
+                            hit = same_key(*past_ref(*rr.d, rr.g, rr.tp - hd, rr.ply, rr.ply).b, nb);
+                    }
+                    rep_hit = __ballot(hit) != 0;
+                }
+            }
+        }
         if (res != RESULT_NONE) v = res == 0 ? 0 : -(OPP_MATE - k);
+        else if (REP && rep_hit) v = 0;
         else if (horizon) v = QS ? stand : uni(opp_evaluate(b, lane));
         else {
             __syncthreads();                               // F->mv visible
@@ -403,6 +493,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
                 if (lane == 0) {
                     F->b = b; F->cur = 0; F->n = cnt; F->alpha = a; F->beta = be; F->best = best0;
                     if (ORD) F->nt = nt;
+                    if (REP) { rs->ph[k] = nh; rs->ps[k] = ns; }
                 }
                 __syncthreads();
                 have_v = false;
@@ -481,10 +572,10 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
 
 // One slot of k_opponent_moves / k_opponent_moves_q and, ID, of their _id forms.  Window-relative rows: depths / moves /
 // scores / nodes_out / flags [count] and, ID only, depths_done [count]
-template <bool QS, bool ID = false, bool ORD = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false>
 __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, int push, long long limit, u16 *moves,
                                            int32_t *scores, long long *nodes_out, uint8_t *flags, OppLds<QS> &s,
-                                           int32_t *depths_done = nullptr)
+                                           int32_t *depths_done = nullptr, OppRepLds<QS> *rs = nullptr)
 {
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
     int D = uni(depths[r]);
@@ -499,7 +590,9 @@ __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, 
         return;
     }
     const Board root = uni_board(d.cur[g]);
-    const OppResult o = opp_search<QS, ID, ORD>(root, D, Q, limit, s.f, lane);
+    OppRepRoot rr;                                         // REP: the root is the game's current position
+    rr.d = &d; rr.g = g; rr.tp = 0; rr.ply = REP ? uni(d.game[g].ply) : 0;
+    const OppResult o = opp_search<QS, ID, ORD, REP>(root, D, Q, limit, s.f, lane, rs, rr);
     if (lane == 0) {
         moves[r] = (u16)o.mv;
         scores[r] = o.score;
@@ -509,7 +602,7 @@ __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, 
     }
     if (push && o.mv != NO_MOVE) {
         __syncthreads();                                   // the frames are dead: s.w takes their bytes
-        game_push(d, g, ORD ? uni_board(d.cur[g]) : root, o.mv, lane, s.w);    // (ORD: not held across the search)
+        game_push(d, g, ORD || REP ? uni_board(d.cur[g]) : root, o.mv, lane, s.w);   // (not held across the search)
     }
 }
 
@@ -565,16 +658,60 @@ __global__ __launch_bounds__(64) void k_opponent_moves_ido_q(Dev d, const int32_
     opponent_moves_slot<true, true, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s, depths_done);
 }
 
+// the _id and _ido kernels with REPETITION: the same arguments
+__global__ __launch_bounds__(64) void k_opponent_moves_idr(Dev d, const int32_t *depths, int push, long long budget,
+                                                           u16 *moves, int32_t *scores, long long *nodes_out,
+                                                           uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<false> s;
+    __shared__ OppRepLds<false> rs;
+    opponent_moves_slot<false, true, false, true>(d, depths, 0, push, budget, moves, scores, nodes_out, flags, s,
+                                                  depths_done, &rs);
+}
+
+__global__ __launch_bounds__(64) void k_opponent_moves_idr_q(Dev d, const int32_t *depths, int Q, int push,
+                                                             long long budget, u16 *moves, int32_t *scores,
+                                                             long long *nodes_out, uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<true> s;
+    __shared__ OppRepLds<true> rs;
+    opponent_moves_slot<true, true, false, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s,
+                                                 depths_done, &rs);
+}
+
+__global__ __launch_bounds__(64) void k_opponent_moves_idor(Dev d, const int32_t *depths, int push, long long budget,
+                                                            u16 *moves, int32_t *scores, long long *nodes_out,
+                                                            uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<false> s;
+    __shared__ OppRepLds<false> rs;
+    opponent_moves_slot<false, true, true, true>(d, depths, 0, push, budget, moves, scores, nodes_out, flags, s,
+                                                 depths_done, &rs);
+}
+
+__global__ __launch_bounds__(64) void k_opponent_moves_idor_q(Dev d, const int32_t *depths, int Q, int push,
+                                                              long long budget, u16 *moves, int32_t *scores,
+                                                              long long *nodes_out, uint8_t *flags,
+                                                              int32_t *depths_done)
+{
+    __shared__ OppLds<true> s;
+    __shared__ OppRepLds<true> rs;
+    opponent_moves_slot<true, true, true, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s,
+                                                depths_done, &rs);
+}
+
 // expand, the opponent's half (mctree.py:244-246) with the built-in opponent as the mover (gamestockfish.py:27-41):
 // the reply stored for S1 is the move k_opponent_moves plays from S1 -- it reads the board alone, so the tree holds the
 // real opponent's reply.  Rows as k_reply: one whose pending leaf is not LEAF_NEW_REPLY only clears lab_n2.  The root
 // order of the search is wave_movegen's (s1_moves is not read).  A cut reply is a move like any other.  nodes_acc /
 // cuts_acc [count], window-relative: this wave owns its row, so lane 0 adds with a plain load and store.  ID: the
 // search is ITERATIVE DEEPENING under the budget `limit`, and depth_acc [count] sums the completed depths.
-template <bool QS, bool ID = false, bool ORD = false>
+// REP: REPETITION -- S1 stands at tree ply 2 * path_len - 1 of the one path d.path_node holds, so what led to it is the
+// S1 / S2 of the pending node's ancestors and then the game's ring.
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false>
 __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, long long limit, void *planes2,
                                           unsigned long long *nodes_acc, uint32_t *cuts_acc, OppLds<QS> &s,
-                                          unsigned long long *depth_acc = nullptr)
+                                          unsigned long long *depth_acc = nullptr, OppRepLds<QS> *rs = nullptr)
 {
     const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
     if (lane == 0) d.lab_n2[r] = 0;                     // no policy(S2) wanted unless a new node gets priors
@@ -586,7 +723,9 @@ __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, l
     }
     const int c = uni(d.game[g].leaf_node);
     const Board s1 = uni_board(d.node[(size_t)g * d.N + c].s1);
-    const OppResult o = opp_search<QS, ID, ORD>(s1, D, Q, limit, s.f, lane);
+    OppRepRoot rr;
+    rr.d = &d; rr.g = g; rr.tp = REP ? 2 * uni(d.game[g].path_len) - 1 : 0; rr.ply = REP ? uni(d.game[g].ply) : 0;
+    const OppResult o = opp_search<QS, ID, ORD, REP>(s1, D, Q, limit, s.f, lane, rs, rr);
     if (o.mv == NO_MOVE) { dev_error(d, DERR_STATE); return; }              // S1 is running: it has a legal move
     if (lane == 0) {
         nodes_acc[r] += (unsigned long long)o.nodes;
@@ -644,6 +783,43 @@ __global__ __launch_bounds__(64) void k_reply_opponent_ido_q(Dev d, const int32_
 {
     __shared__ OppLds<true> s;
     reply_opponent_row<true, true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
+}
+
+// the _id and _ido kernels with REPETITION: the same arguments
+__global__ __launch_bounds__(64) void k_reply_opponent_idr(Dev d, const int32_t *depths, long long budget,
+                                                           void *planes2, unsigned long long *nodes_acc,
+                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<false> s;
+    __shared__ OppRepLds<false> rs;
+    reply_opponent_row<false, true, false, true>(d, depths, 0, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
+}
+
+__global__ __launch_bounds__(64) void k_reply_opponent_idr_q(Dev d, const int32_t *depths, int Q, long long budget,
+                                                             void *planes2, unsigned long long *nodes_acc,
+                                                             uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<true> s;
+    __shared__ OppRepLds<true> rs;
+    reply_opponent_row<true, true, false, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
+}
+
+__global__ __launch_bounds__(64) void k_reply_opponent_idor(Dev d, const int32_t *depths, long long budget,
+                                                            void *planes2, unsigned long long *nodes_acc,
+                                                            uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<false> s;
+    __shared__ OppRepLds<false> rs;
+    reply_opponent_row<false, true, true, true>(d, depths, 0, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
+}
+
+__global__ __launch_bounds__(64) void k_reply_opponent_idor_q(Dev d, const int32_t *depths, int Q, long long budget,
+                                                              void *planes2, unsigned long long *nodes_acc,
+                                                              uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<true> s;
+    __shared__ OppRepLds<true> rs;
+    reply_opponent_row<true, true, true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
 }
 
 }  // namespace crl

@@ -7,6 +7,10 @@ sides are the built-in alpha-beta player (csrc/opponent.hpp; NOT Stockfish), eve
 context and all games advance together: one ``opponent_moves(depths, push=True)`` launch per ply with the per-slot
 depth of the side to move.  That player is deterministic, so every game first plays ``opening_plies`` random plies
 with the in-slot playout call (``Context.rollout_games``, words from ``random.Random(seed)``).
+
+The player sees a repetition below the root only on request (``repetition=True`` / ``--repetition``, with a node
+budget; csrc/opponent.hpp, REPETITION): without it a large share of the games are draws in which the side that is ahead
+shuffles until the fifth occurrence.
 """
 import argparse
 import logging
@@ -55,16 +59,19 @@ def side_depths(draws, white_to_move):
 
 
 def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512,
-             quiescence=0, node_budget=None, ordering=False):
+             quiescence=0, node_budget=None, ordering=False, repetition=False):
     """Plays ``num_games`` games, saves the finished ones to ``save_path`` (appending to what the file holds, as
     ``DatasetGame.save`` does) and returns the ``DatasetGame`` it saved.  The reference's ``gen_data`` forgets to
     pass ``depth`` and ``random_dep`` on to ``play_game`` (gen_data_stockfish.py:44-49); here both are honoured.
     ``workers`` is accepted and ignored; a game still running after ``max_plies`` plies is dropped.  ``quiescence``:
     the quiescence plies of both sides past their depths (0 .. CRL_OPP_MAX_QUIESCENCE; 0: none).  ``node_budget``
     (None: none): both sides deepen iteratively up to their depths and stop at that many nodes per move; ``ordering``
-    (needs a ``node_budget``): with the move ORDERING of csrc/opponent.hpp."""
+    (needs a ``node_budget``): with the move ORDERING of csrc/opponent.hpp; ``repetition`` (needs a ``node_budget``):
+    with its REPETITION rule, both sides score a position below the root that occurred before a draw."""
     if ordering and node_budget is None:
         raise ValueError("ordering needs a node_budget")
+    if repetition and node_budget is None:
+        raise ValueError("repetition needs a node_budget")
     if node_budget is not None and int(node_budget) < 1:
         raise ValueError("node_budget must be None or at least 1")
     quiescence = int(quiescence)
@@ -93,7 +100,8 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
             if not running.any():
                 break
             ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True,
-                               quiescence=quiescence, node_budget=node_budget, ordering=bool(ordering))
+                               quiescence=quiescence, node_budget=node_budget, ordering=bool(ordering),
+                               repetition=bool(repetition))
             results = ctx.results()
         moves, plies, results = ctx.records()
     finally:
@@ -119,6 +127,8 @@ def main(argv=None):
                    help="Node budget per move, both sides: iterative deepening up to the depth (default: none).")
     p.add_argument("--ordering", action="store_true", default=False,
                    help="Order the moves of the --nodes search by victim and killer moves, both sides.")
+    p.add_argument("--repetition", action="store_true", default=False,
+                   help="The --nodes search scores a position below the root that occurred before a draw, both sides.")
     p.add_argument("--random_depth", action="store_true", default=False,
                    help="Use normal distribution of depths with mean --depth.")
     p.add_argument("--debug", action="store_true", default=False, help="Log debug messages on screen. Default false.")
@@ -128,7 +138,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.DEBUG if a.debug else logging.INFO)
     gen_data(a.data_path, num_games=a.games, depth=a.depth, random_dep=a.random_depth,
              opening_plies=a.opening_plies, seed=a.seed, quiescence=a.quiescence,
-             node_budget=a.nodes, ordering=a.ordering)
+             node_budget=a.nodes, ordering=a.ordering, repetition=a.repetition)
 
 
 if __name__ == "__main__":

@@ -4,13 +4,15 @@ The reference measures and bootstraps against an engine: ``Stockfish(Player)``
 (/root/reference/src/chessrl/stockfish.py:11-34) and ``GameStockfish(Game)``, a game that answers
 every move of ours with the engine's (gamestockfish.py:6-61).  No engine binary belongs to this
 package; what stands in its place is the fixed-depth alpha-beta player of ``csrc/opponent.hpp``,
-one wavefront per game on the GPU.  It is NOT Stockfish: no repetition below the root, no time
-control, and no Elo is claimed -- a result reads "against the built-in depth-d opponent".  Past the
+one wavefront per game on the GPU.  It is NOT Stockfish: repetition below the root only on request
+(``repetition=True``, below), no time control, and no Elo is claimed -- a result reads "against the built-in depth-d opponent".  Past the
 fixed depth it can search ``quiescence`` plies of captures, promotions and check evasions
 (opponent.hpp, QUIESCENCE); 0, the default, is the fixed-depth search alone.  With ``node_budget`` it deepens
 iteratively up to ``search_depth`` and stops at that many nodes per move (opponent.hpp, ITERATIVE DEEPENING): the
 deterministic counterpart of the reference's ``Limit(time=...)`` (stockfish.py:14-21); ``ordering=True`` on top of a
-budget orders the moves below the root by victim and killer moves (opponent.hpp, ORDERING).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
+budget orders the moves below the root by victim and killer moves (opponent.hpp, ORDERING); ``repetition=True`` on top
+of a budget scores a position below the root that occurred before -- on the search path or in the game's reversible
+history -- a draw (opponent.hpp, REPETITION), so a side that is ahead stops shuffling into the fivefold.  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
 these classes are the one-game drop-in surface over it.
 """
 import numpy as np
@@ -36,9 +38,11 @@ class MinimaxPlayer(Player):
     with ``search_depth`` as the maximum depth under ``min(node_budget, node_limit)`` nodes per move; ``last_depth`` is
     then the depth the last search completed (None without a budget).  ``ordering`` (needs a ``node_budget``): below
     the root that search tries the moves by victim, then the killer moves of the ply (opponent.hpp, ORDERING); with a
-    budget it does not reach it plays the same move for fewer nodes."""
+    budget it does not reach it plays the same move for fewer nodes.  ``repetition`` (needs a ``node_budget``): a node
+    below the root whose position occurred before is worth 0 (opponent.hpp, REPETITION)."""
 
-    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0, node_budget=None, ordering=False):
+    def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0, node_budget=None, ordering=False,
+                 repetition=False):
         super().__init__(color)
         if not 1 <= int(search_depth) <= MAX_DEPTH:
             raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
@@ -55,6 +59,9 @@ class MinimaxPlayer(Player):
         if ordering and self.node_budget is None:
             raise ValueError("ordering needs a node_budget")
         self.ordering = bool(ordering)
+        if repetition and self.node_budget is None:
+            raise ValueError("repetition needs a node_budget")
+        self.repetition = bool(repetition)
         self.last = None                      # (score, nodes, flag) of the last search
         self.last_depth = None                # with a budget: the depth that search completed
 
@@ -63,7 +70,8 @@ class MinimaxPlayer(Player):
             raise RuntimeError("Game was freed")
         ctx = arena().one(game._slot)
         out = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False, node_limit=self.node_limit,
-                                 quiescence=self.quiescence, node_budget=self.node_budget, ordering=self.ordering)
+                                 quiescence=self.quiescence, node_budget=self.node_budget, ordering=self.ordering,
+                                 repetition=self.repetition)
         moves, scores, nodes, flags = out[:4]
         self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
         self.last_depth = int(out[4][0]) if self.node_budget is not None else None
@@ -78,10 +86,11 @@ class MinimaxPlayer(Player):
 class GameOpponent(Game):
     """Mirror of ``GameStockfish``: a game against the built-in opponent.  ``opponent``: a ``MinimaxPlayer``, or
     None for one of depth ``opponent_depth``, ``opponent_quiescence``, ``opponent_budget`` (the player's
-    ``node_budget``) and ``opponent_ordering`` (its ``ordering``) with the colour opposite to ``player_color``."""
+    ``node_budget``), ``opponent_ordering`` (its ``ordering``) and ``opponent_repetition`` (its ``repetition``) with the
+    colour opposite to ``player_color``."""
 
     def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2,
-                 opponent_quiescence=0, opponent_budget=None, opponent_ordering=False):
+                 opponent_quiescence=0, opponent_budget=None, opponent_ordering=False, opponent_repetition=False):
         if opponent is not None and not isinstance(opponent, MinimaxPlayer):
             raise ValueError("opponent must be a MinimaxPlayer or None")
         self.opponent = None                  # (a board's move stack is replayed by plain Game.move)
@@ -89,7 +98,7 @@ class GameOpponent(Game):
         if opponent is None:
             opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth,
                                      quiescence=opponent_quiescence, node_budget=opponent_budget,
-                                     ordering=opponent_ordering)
+                                     ordering=opponent_ordering, repetition=opponent_repetition)
         self.opponent = opponent
 
     def move(self, movement):

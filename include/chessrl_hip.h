@@ -70,7 +70,7 @@ typedef struct crl_ctx crl_ctx;
  * signature hands the GPU garbage pointers).  crl_source_hash(): sha256 over the sources (csrc/ + this
  * header + compiler flags) the library was built from, as chessrl_amd/_lib.py computes it; the string
  * is also findable in the file itself behind the marker "CRL_SRC_HASH=".  No reference counterpart.
- * (The _ord entries of the built-in opponent are additions that change no existing signature: still 9.) */
+ * (The _ord and _rep entries of the built-in opponent are additions that change no existing signature: still 9.) */
 #define CRL_ABI_VERSION 9
 int  crl_abi_version(void);
 const char *crl_source_hash(void);
@@ -295,7 +295,7 @@ int  crl_rollout(crl_ctx *ctx, int root_source, int repetitions, int max_moves, 
 /* ---- the built-in opponent: a fixed-depth alpha-beta player per slot (csrc/opponent.hpp states the search, the
  * node value, the move order, the static evaluation and the node limit).  It stands where the reference calls its
  * engine: Stockfish.best_move (stockfish.py:23-31, engine.play(board, Limit(depth))) and the reply inside
- * GameStockfish.move (gamestockfish.py:27-41).  It is not that engine: no repetition below the root, quiescence
+ * GameStockfish.move (gamestockfish.py:27-41).  It is not that engine: repetition below the root only on request (the _rep calls), quiescence
  * only through the _q calls below, no time control, no Elo.  Host arrays, synchronous, window-relative like crl_greedy_moves.
  * depths[g] (host int32): 0 leaves slot g alone, 1 .. CRL_OPP_MAX_DEPTH searches it to that depth -- the array is
  * both the mask and the per-game depth.  node_limit >= 1 bounds the nodes (move generations) of every slot: a slot
@@ -366,6 +366,20 @@ int  crl_opponent_moves_ord(crl_ctx *ctx, const int32_t *depths /*G*/, int quies
 int  crl_sim_reply_opponent_ord(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
                                 int ordering, void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
                                 uint64_t *dev_depth_sum_u64);                     /* stockfish.py:14-21 */
+/* The two _ord calls with an opt-in REPETITION rule (csrc/opponent.hpp states it).  repetition = 0 is the _ord call,
+ * array for array, from the same kernels.  repetition = 1: a node below the root whose position -- the same
+ * _transposition_key, the same side to move -- occurred before, on the search path or among the reversible plies
+ * that led to the root (the game's history ring; for the reply call the tree path of the pending node and then the
+ * ring), is worth 0 and is searched no further.  One earlier occurrence is enough and the decision is exact; the root
+ * is never tested, a result takes precedence, and the game itself still ends on the fifth occurrence.  The answer is
+ * a function of the root, its reversible history and the arguments.
+ * CRL_ERR_ARG: a repetition other than 0 or 1, and what the _ord calls refuse.  No state changes on an error. */
+int  crl_opponent_moves_rep(crl_ctx *ctx, const int32_t *depths /*G*/, int quiescence, int push, int64_t node_budget,
+                            int ordering, int repetition, uint16_t *moves /*G*/, int32_t *scores /*G*/,
+                            int64_t *nodes /*G*/, uint8_t *flags /*G*/, int32_t *depths_done /*G*/);
+int  crl_sim_reply_opponent_rep(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                                int ordering, int repetition, void *dev_planes_s2, uint64_t *dev_nodes_u64,
+                                uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64);
 
 /* ---- threads > 1: virtual-loss waves of simulations per game (csrc/search_wave.hpp) --------------------------
  * The reference runs `threads` explore_tree workers on one tree, kept apart by a virtual loss (mctree.py:12,173-176,

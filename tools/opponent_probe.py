@@ -5,6 +5,7 @@
     python tools/opponent_probe.py --quiescence 2,4,6 --depths 1,2 --out profiles/opponent_probe_q.json
     python tools/opponent_probe.py --budget 150,300,600,1500 --depths 2,3 --max-depth 3
     python tools/opponent_probe.py --ordering --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2
+    python tools/opponent_probe.py --repetition --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2 --opening-plies 40
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words), so the slots hold
 different positions.  Per depth, in depth order: one warm-up launch, then three timed ones (host wall time around the
@@ -16,7 +17,11 @@ DEEPENING), keyed "<=<depth>@<B>[+q<Q>]", with the histogram of the completed de
 profiles/opponent_probe_id.json unless --out names another file.  --ordering: every budget is run with the move
 ORDERING of opponent.hpp off and on in the same process, the launches alternating (warm-up off, warm-up on, then three
 times off, on); the ordered rows are keyed "<=<depth>@<B>[+q<Q>] ordered" and the output goes to
-profiles/opponent_probe_ord.json.  No threshold: this is a measurement.
+profiles/opponent_probe_ord.json.  --repetition: likewise every budget is run with the REPETITION rule of opponent.hpp
+off and on in the same process, the launches alternating; the rule-on rows are keyed "<=<depth>@<B>[+q<Q>] repeating-aware"
+and carry the cost per node as a ratio to the rule-off row of the same run and the share of slots that play another
+move; the output goes to profiles/opponent_probe_rep.json.  At --opening-plies 6 few slots have reversible plies behind
+them; at 40 most do.  With --ordering as well, both rows of a budget are ordered.  No threshold: this is a measurement.
 """
 import argparse
 import json
@@ -40,21 +45,25 @@ def main():
     ap.add_argument("--budget", default="", help="node budgets of the iterative-deepening launches (default: none)")
     ap.add_argument("--max-depth", type=int, default=3, help="maximum depth of the --budget launches")
     ap.add_argument("--ordering", action="store_true", help="run every --budget with ordering off and on, alternating")
+    ap.add_argument("--repetition", action="store_true",
+                    help="run every --budget with the repetition rule off and on, alternating")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     budgets = [int(b) for b in args.budget.split(",") if b]
     if args.out is None:
-        name = "opponent_probe.json" if not budgets else "opponent_probe_ord.json" if args.ordering else "opponent_probe_id.json"
+        name = ("opponent_probe.json" if not budgets else "opponent_probe_rep.json" if args.repetition else
+                "opponent_probe_ord.json" if args.ordering else "opponent_probe_id.json")
         args.out = os.path.join(ROOT, "profiles", name)
     import numpy as np
     from chessrl_amd import _lib
     from chessrl_amd.gen_data import opening_words
     G = args.games
-    ctx = _lib.Context(G, 1, max_plies=64)
+    ctx = _lib.Context(G, 1, max_plies=max(64, args.opening_plies + 2))
     words = opening_words(random.Random(1), G, args.opening_plies)
     played, _, _ = ctx.rollout_games(words, np.full(G, words.shape[1], np.int32), 1, args.opening_plies)
     out = {"games": G, "opening_plies": args.opening_plies, "mean_opening_plies": float(played.mean()),
-           "node_limit": args.node_limit, "running": int((ctx.results() == _lib.RESULT_NONE).sum()), "depths": {}}
+           "node_limit": args.node_limit, "clock_at_least_4_share": float((((ctx.get_positions()[:, 7] >> 12) & 255) >= 4).mean()),
+           "running": int((ctx.results() == _lib.RESULT_NONE).sum()), "depths": {}}
     cases = [(int(d), int(q), None) for q in args.quiescence.split(",") for d in args.depths.split(",")]
     cases += [(args.max_depth, int(q), b) for q in args.quiescence.split(",") for b in budgets]
     for depth, quiescence, budget in cases:
@@ -65,7 +74,11 @@ def main():
             kw["node_budget"] = budget
         # the launches of a case alternate between its variants: ordering off and, with --ordering, on
         variants = [(key, kw)]
-        if budget is not None and args.ordering:
+        if budget is not None and args.repetition:
+            if args.ordering:
+                variants = [(key + " ordered", dict(kw, ordering=True))]
+            variants.append((variants[0][0] + " repeating-aware", dict(variants[0][1], repetition=True)))
+        elif budget is not None and args.ordering:
             variants.append((key + " ordered", dict(kw, ordering=True)))
         times = dict((k, []) for k, _ in variants)
         last = {}
@@ -88,7 +101,12 @@ def main():
             if budget is not None:
                 out["depths"][k]["depth_done_histogram"] = np.bincount(last[k][4][searched], minlength=depth + 1).tolist()
             print(k, json.dumps(out["depths"][k]), flush=True)
-        if len(variants) == 2:                       # what ORDERING promises when no slot is cut: the same answers
+        if len(variants) == 2 and args.repetition:   # the rule's cost per node against the rule-off row of this run
+            off, on = out["depths"][variants[0][0]], out["depths"][variants[1][0]]
+            on["time_per_node_ratio_to_rule_off"] = off["nodes_per_s"] / on["nodes_per_s"]
+            on["ms_per_launch_ratio_to_rule_off"] = on["ms_per_launch"] / off["ms_per_launch"]
+            on["share_of_slots_with_another_move"] = float((last[variants[0][0]][0] != last[variants[1][0]][0]).mean())
+        elif len(variants) == 2:                     # what ORDERING promises when no slot is cut: the same answers
             a, b = last[variants[0][0]], last[variants[1][0]]
             if not (a[3] == _lib.OPP_CUT).any() and not (b[3] == _lib.OPP_CUT).any():
                 same = all(np.array_equal(a[j], b[j]) for j in (0, 1, 3, 4))
