@@ -41,6 +41,7 @@ RESULT_NONE = 2
 ROLLOUT_GAMES, ROLLOUT_LEAVES, ROLLOUT_SKIPPED = 0, 1, 0xFFFF
 OPP_MAX_DEPTH, OPP_CUT, OPP_SKIPPED = 5, 1, 2     # include/chessrl_hip.h: CRL_OPP_*
 OPP_MAX_QUIESCENCE = 6    # include/chessrl_hip.h: CRL_OPP_MAX_QUIESCENCE
+OPP_EVALUATIONS = {"material": 0, "positional": 1}    # include/chessrl_hip.h: CRL_OPP_EVAL_*
 OPP_NODE_LIMIT = 200000   # default node limit per slot of Context.opponent_moves (a first choice)
 FLAG_NUMPY_LEGACY = 1
 WAVE_MAX_THREADS = 64     # include/chessrl_hip.h: CRL_WAVE_MAX_THREADS
@@ -68,6 +69,7 @@ SYMBOLS = [
     "crl_opponent_moves_q", "crl_sim_reply_opponent_q", "crl_opponent_moves_id", "crl_sim_reply_opponent_id",
     "crl_opponent_moves_ord", "crl_sim_reply_opponent_ord",
     "crl_opponent_moves_rep", "crl_sim_reply_opponent_rep",
+    "crl_opponent_moves_ev", "crl_sim_reply_opponent_ev", "crl_opponent_evaluate",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
     "crl_advance_one",
@@ -77,6 +79,23 @@ SYMBOLS = [
 
 class HipLibraryError(RuntimeError):
     pass
+
+
+def evaluation_name(evaluation):
+    """``evaluation`` if it names an evaluation of the built-in opponent; a ValueError otherwise."""
+    if not isinstance(evaluation, str) or evaluation not in OPP_EVALUATIONS:
+        raise ValueError("evaluation must be one of %s" % ", ".join('"%s"' % k for k in OPP_EVALUATIONS))
+    return evaluation
+
+
+def opponent_evaluation(evaluation, node_budget):
+    """True for "positional", False for "material"; a ValueError for another name and for "positional" without a
+    ``node_budget`` (only the budgeted kernels exist with it)."""
+    if evaluation_name(evaluation) == "material":
+        return False
+    if node_budget is None:
+        raise ValueError("evaluation needs a node_budget")
+    return True
 
 
 ABI_VERSION = 9          # include/chessrl_hip.h: CRL_ABI_VERSION (checked against the loaded library)
@@ -255,6 +274,9 @@ def lib():
     L.crl_sim_reply_opponent_ord.argtypes = [vp, vp, i32, ctypes.c_int64, i32, vp, vp, vp, vp]
     L.crl_opponent_moves_rep.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp, vp]
     L.crl_sim_reply_opponent_rep.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp]
+    L.crl_opponent_moves_ev.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.crl_sim_reply_opponent_ev.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, i32, vp, vp, vp, vp]
+    L.crl_opponent_evaluate.argtypes = [vp, i32, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     L.crl_wave_config.argtypes = [vp, i32]
     L.crl_wave_begin.argtypes = [vp, i32]
@@ -583,7 +605,8 @@ class Context(object):
                                        ctypes.c_void_p(dev_planes_s2)), "crl_sim_reply")
 
     def sim_reply_opponent(self, dev_depths, node_limit, dev_planes_s2, dev_nodes, dev_cuts, quiescence=0,
-                           node_budget=None, dev_depth_sum=None, ordering=False, repetition=False):
+                           node_budget=None, dev_depth_sum=None, ordering=False, repetition=False,
+                           evaluation="material"):
         """``sim_reply`` with the built-in opponent's move as the reply: device pointers to int32 [count] depths, the
         planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies; ``quiescence`` plies (0 ..
         OPP_MAX_QUIESCENCE) past the depth.  ``node_budget`` (not None): iterative deepening up to the depths under
@@ -591,7 +614,16 @@ class Context(object):
         completed depths.  ``ordering`` (needs a ``node_budget``): the budgeted search with ORDERING (csrc/opponent.hpp),
         ``crl_sim_reply_opponent_ord``; False calls the entry it called.  ``repetition`` (needs a ``node_budget``): the
         budgeted search with REPETITION (a repeated position below the root is a draw), ``crl_sim_reply_opponent_rep``;
-        False calls the entry it called."""
+        False calls the entry it called.  ``evaluation`` ("positional" needs a ``node_budget``): the budgeted search with
+        EVALUATION in place of the material evaluation, ``crl_sim_reply_opponent_ev``; "material" calls the entry it
+        called."""
+        if opponent_evaluation(evaluation, node_budget):
+            self._ck(self._L.crl_sim_reply_opponent_ev(
+                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)),
+                1 if ordering else 0, 1 if repetition else 0, 1, ctypes.c_void_p(dev_planes_s2),
+                ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts), ctypes.c_void_p(dev_depth_sum)),
+                "crl_sim_reply_opponent_ev")
+            return
         if repetition:
             if node_budget is None:
                 raise ValueError("repetition needs a node_budget")
@@ -748,7 +780,7 @@ class Context(object):
 
     # ---- the built-in opponent (csrc/opponent.hpp; stockfish.py:23-31, gamestockfish.py:27-41) ------
     def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT, quiescence=0, node_budget=None,
-                       ordering=False, repetition=False):
+                       ordering=False, repetition=False, evaluation="material"):
         """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it,
         with ``quiescence`` plies (0 .. OPP_MAX_QUIESCENCE, one value per call) of quiescence search past the depth.
         Returns (moves u16, scores i32, nodes i64, flags u8); with ``push`` the moves are played.  ``node_budget`` (not
@@ -757,11 +789,15 @@ class Context(object):
         search with ORDERING (csrc/opponent.hpp: victims first, then the killer moves of the ply), through
         ``crl_opponent_moves_ord``; False calls the entry it called.  ``repetition`` (needs a ``node_budget``): that
         search with REPETITION (a position below the root that occurred before, on the path or in the slot's reversible
-        history, is worth 0), through ``crl_opponent_moves_rep``; False calls the entry it called."""
+        history, is worth 0), through ``crl_opponent_moves_rep``; False calls the entry it called.  ``evaluation``
+        ("positional" needs a ``node_budget``): that search with EVALUATION (csrc/opponent.hpp: pawn structure,
+        mobility, files, king safety, tapered) in place of the material evaluation, through ``crl_opponent_moves_ev``;
+        "material" calls the entry it called."""
         if ordering and node_budget is None:
             raise ValueError("ordering needs a node_budget")
         if repetition and node_budget is None:
             raise ValueError("repetition needs a node_budget")
+        positional = opponent_evaluation(evaluation, node_budget)
         dp = np.ascontiguousarray(depths, dtype=np.int32)
         assert dp.shape == (self.G,)
         moves = np.zeros(self.G, np.uint16)
@@ -770,6 +806,12 @@ class Context(object):
         flags = np.zeros(self.G, np.uint8)
         if node_budget is not None:
             done = np.zeros(self.G, np.int32)
+            if positional:
+                self._ck(self._L.crl_opponent_moves_ev(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
+                                                       min(int(node_budget), int(node_limit)), 1 if ordering else 0,
+                                                       1 if repetition else 0, 1, _ptr(moves), _ptr(scores),
+                                                       _ptr(nodes), _ptr(flags), _ptr(done)), "crl_opponent_moves_ev")
+                return moves, scores, nodes, flags, done
             if repetition:
                 self._ck(self._L.crl_opponent_moves_rep(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
                                                         min(int(node_budget), int(node_limit)), 1 if ordering else 0, 1,
@@ -790,6 +832,14 @@ class Context(object):
                                               _ptr(moves), _ptr(scores), _ptr(nodes), _ptr(flags)),
                  "crl_opponent_moves_q")
         return moves, scores, nodes, flags
+
+    def opponent_evaluate(self, evaluation="material"):
+        """The static evaluation (int32 [G], from the side to move) of every window slot's current position:
+        "material" is STATIC EVALUATION of csrc/opponent.hpp, "positional" its EVALUATION.  No search."""
+        kind = OPP_EVALUATIONS[evaluation_name(evaluation)]
+        scores = np.zeros(self.G, np.int32)
+        self._ck(self._L.crl_opponent_evaluate(self._h, kind, _ptr(scores)), "crl_opponent_evaluate")
+        return scores
 
     # ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------
     def wave_config(self, threads):

@@ -16,6 +16,8 @@ black first get the opponent's opening move (gamestockfish.py:31-33); then per m
 
 The opponent sees a repetition below the root only on request: ``opponent_repetition=True`` / ``--repetition`` (needs a
 budget; csrc/opponent.hpp, REPETITION).  Without it, games it is winning may still end as draws by the fifth occurrence.
+Its static evaluation is material and centrality unless ``opponent_evaluation="positional"`` / ``--eval positional``
+(needs a budget; csrc/opponent.hpp, EVALUATION) asks for the positional one.
 """
 import argparse
 import os
@@ -47,7 +49,7 @@ def _load_model(model_dir):
 
 
 def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence=0, budget=None,
-                 ordering=False, repetition=False):
+                 ordering=False, repetition=False, evaluation="material"):
     """(moves, plies, results) of the games with ``Agent.best_move(real_game=True)`` on the agent's plies."""
     import torch
     ctx = _lib.Context(games, 1, max_plies=max(max_plies, 2), device=dev.index or 0)
@@ -68,7 +70,8 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quie
                 ctx.greedy_moves(policy.data_ptr(), mask=agent_turn, push=True, want_moves=False)
             if opp_turn.any():
                 ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True, quiescence=quiescence,
-                                   node_budget=budget, ordering=ordering, repetition=repetition)
+                                   node_budget=budget, ordering=ordering, repetition=repetition,
+                                   evaluation=evaluation)
             results = ctx.results()
         return ctx.records()
     finally:
@@ -76,7 +79,7 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quie
 
 
 def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, quiescence=0, budget=None,
-                 ordering=False, repetition=False):
+                 ordering=False, repetition=False, evaluation="material"):
     """(moves, plies, results) of the games with ``sims`` simulations per move against the opponent's replies.  A game
     is searched while it runs and has fewer than ``max_plies`` plies; a move adds two plies (one if it ends the game),
     so a game may end one ply past ``max_plies``."""
@@ -84,12 +87,13 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
     from .opponent import MinimaxPlayer
     eng = LockstepEngine(model, games, sims, device=dev.index or 0, max_plies=max_plies + 2,
                          reply=MinimaxPlayer(False, search_depth=opponent_depth, quiescence=quiescence,
-                                             node_budget=budget, ordering=ordering, repetition=repetition))
+                                             node_budget=budget, ordering=ordering, repetition=repetition,
+                                             evaluation=evaluation))
     try:
         ctx = eng.ctx
         if not agent_white.all():                            # gamestockfish.py:31-33: the opponent opens as white
             ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True, quiescence=quiescence,
-                               node_budget=budget, ordering=ordering, repetition=repetition)
+                               node_budget=budget, ordering=ordering, repetition=repetition, evaluation=evaluation)
         while True:
             _, plies, results = ctx.records(with_moves=False)
             live = (results == _lib.RESULT_NONE) & (plies < max_plies)
@@ -107,7 +111,7 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
 
 def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=None, max_plies=512, model=None,
               sims=0, opponent_quiescence=0, opponent_budget=None, opponent_ordering=False,
-              opponent_repetition=False):
+              opponent_repetition=False, opponent_evaluation="material"):
     """Plays ``games`` games against the built-in depth-``opponent_depth`` opponent (with ``opponent_quiescence``
     plies of quiescence search, 0 by default) and returns
     ``dict(played=, won=, drawn=, games=)``: the reference's tallies and the per-game UCI move lists.  ``workers`` is
@@ -118,7 +122,8 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     ``opponent_budget`` (None: none): the opponent deepens iteratively up to ``opponent_depth`` and stops at that many
     nodes per move (csrc/opponent.hpp, ITERATIVE DEEPENING); ``opponent_ordering`` (needs ``opponent_budget``): with
     the move ORDERING of that header; ``opponent_repetition`` (needs ``opponent_budget``): with its REPETITION rule, a
-    position below the root that occurred before is a draw to the opponent's search."""
+    position below the root that occurred before is a draw to the opponent's search; ``opponent_evaluation``
+    ("positional" needs ``opponent_budget``): with its EVALUATION in place of the material evaluation."""
     if not 1 <= int(opponent_depth) <= _lib.OPP_MAX_DEPTH:
         raise ValueError("opponent_depth must lie in [1, %d]" % _lib.OPP_MAX_DEPTH)
     quiescence = int(opponent_quiescence)
@@ -133,6 +138,8 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     repetition = bool(opponent_repetition)
     if repetition and budget is None:
         raise ValueError("repetition needs a node_budget")
+    evaluation = _lib.evaluation_name(opponent_evaluation)
+    positional = _lib.opponent_evaluation(evaluation, budget)
     sims = int(sims)
     if sims < 0:
         raise ValueError("sims must be 0 (the greedy agent) or the number of simulations per move")
@@ -148,10 +155,10 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     agent_white = np.array(colors, dtype=bool)
     if sims > 0:
         moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims,
-                                             quiescence, budget, ordering, repetition)
+                                             quiescence, budget, ordering, repetition, evaluation)
     else:
         moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence,
-                                             budget, ordering, repetition)
+                                             budget, ordering, repetition, evaluation)
     res = [None if r == _lib.RESULT_NONE else int(r) for r in results]
     out = tally(colors, res)
     out["games"] = [[move_to_uci(m) for m in moves[i, :plies[i]]] for i in range(games)]
@@ -161,10 +168,11 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
             print("Against the built-in depth-%d opponent%s (not Stockfish, no Elo)"
                   % (opponent_depth, ", quiescence %d" % quiescence if quiescence else ""))
         else:
-            print("Against the built-in opponent, depth <= %d within %d nodes per move%s%s%s (not Stockfish, no Elo)"
+            print("Against the built-in opponent, depth <= %d within %d nodes per move%s%s%s%s (not Stockfish, no Elo)"
                   % (opponent_depth, budget, ", ordered" if ordering else "",
                      ", repetition-aware" if repetition else "",
-                     ", quiescence %d" % quiescence if quiescence else ""))
+                     ", quiescence %d" % quiescence if quiescence else "",
+                     ", positional evaluation" if positional else ""))
         if sims > 0:
             print("agent: MCTS, %d simulations per move" % sims)
         print("Games played: %d" % out["played"])
@@ -189,6 +197,8 @@ def main(argv=None):
                    help="order the moves of the --nodes search by victim and killer moves (needs --nodes)")
     p.add_argument("--repetition", action="store_true",
                    help="the --nodes search scores a position below the root that occurred before a draw (needs --nodes)")
+    p.add_argument("--eval", dest="evaluation", choices=sorted(_lib.OPP_EVALUATIONS), default="material",
+                   help="static evaluation of the --nodes search (positional needs --nodes)")
     p.add_argument("--seed", type=int, default=None, help="seed of the colour draw")
     p.add_argument("--max-plies", type=int, default=512)
     p.add_argument("--sims", type=int, default=0,
@@ -196,7 +206,7 @@ def main(argv=None):
     a = p.parse_args(argv)
     benchmark(a.model_dir, games=a.games, opponent_depth=a.depth, seed=a.seed, max_plies=a.max_plies, log=True,
               sims=a.sims, opponent_quiescence=a.quiescence, opponent_budget=a.nodes, opponent_ordering=a.ordering,
-              opponent_repetition=a.repetition)
+              opponent_repetition=a.repetition, opponent_evaluation=a.evaluation)
 
 
 if __name__ == "__main__":

@@ -845,13 +845,39 @@ int crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t 
 // ITERATIVE DEEPENING under a node budget (csrc/opponent.hpp): kernels of their own, so the calls above launch what
 // they launched
 // (ordering = 1: ORDERING of csrc/opponent.hpp, the _ido kernels; 0 launches the _id kernels, whoever calls;
-// repetition = 1: REPETITION, the _idr / _idor kernels; 0 launches what the call launched without it)
+// repetition = 1: REPETITION, the _idr / _idor kernels; 0 launches what the call launched without it;
+// evaluation = CRL_OPP_EVAL_POSITIONAL: EVALUATION, the k_opponent_moves_ev / k_reply_opponent_ev kernels of the same
+// shape; CRL_OPP_EVAL_MATERIAL launches what the call launched without it)
+using MovesEvKernel = void (*)(Dev, const int32_t *, int, int, long long, u16 *, int32_t *, long long *, uint8_t *,
+                               int32_t *);
+using ReplyEvKernel = void (*)(Dev, const int32_t *, int, long long, void *, unsigned long long *, uint32_t *,
+                               unsigned long long *);
+static MovesEvKernel moves_ev_kernel(bool qs, bool ord, bool rep)
+{
+    static const MovesEvKernel t[8] = {
+        k_opponent_moves_ev<false, false, false>, k_opponent_moves_ev<true, false, false>,
+        k_opponent_moves_ev<false, true, false>,  k_opponent_moves_ev<true, true, false>,
+        k_opponent_moves_ev<false, false, true>,  k_opponent_moves_ev<true, false, true>,
+        k_opponent_moves_ev<false, true, true>,   k_opponent_moves_ev<true, true, true>};
+    return t[(rep ? 4 : 0) | (ord ? 2 : 0) | (qs ? 1 : 0)];
+}
+static ReplyEvKernel reply_ev_kernel(bool qs, bool ord, bool rep)
+{
+    static const ReplyEvKernel t[8] = {
+        k_reply_opponent_ev<false, false, false>, k_reply_opponent_ev<true, false, false>,
+        k_reply_opponent_ev<false, true, false>,  k_reply_opponent_ev<true, true, false>,
+        k_reply_opponent_ev<false, false, true>,  k_reply_opponent_ev<true, false, true>,
+        k_reply_opponent_ev<false, true, true>,   k_reply_opponent_ev<true, true, true>};
+    return t[(rep ? 4 : 0) | (ord ? 2 : 0) | (qs ? 1 : 0)];
+}
+
 static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depths, int quiescence, int push,
-                             int64_t node_budget, int ordering, int repetition, uint16_t *moves, int32_t *scores,
-                             int64_t *nodes, uint8_t *flags, int32_t *depths_done)
+                             int64_t node_budget, int ordering, int repetition, int evaluation, uint16_t *moves,
+                             int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
 {
     ENTER(ctx, depths && moves && node_budget >= 1 && (ordering == 0 || ordering == 1) &&
-                   (repetition == 0 || repetition == 1));
+                   (repetition == 0 || repetition == 1) &&
+                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL));
     if (quiescence < 0 || quiescence > CRL_OPP_MAX_QUIESCENCE)
         return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
     const size_t G = ctx->W;
@@ -860,7 +886,11 @@ static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depth
             return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a depth outside 0 .. CRL_OPP_MAX_DEPTH");
     long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
     HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
-    if (repetition && ordering && quiescence > 0)
+    if (evaluation == CRL_OPP_EVAL_POSITIONAL)
+        LAUNCH(ctx, moves_ev_kernel(quiescence > 0, ordering != 0, repetition != 0), ctx->d,
+               (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes,
+               ctx->t_u8, ctx->t_i32d);
+    else if (repetition && ordering && quiescence > 0)
         LAUNCH(ctx, k_opponent_moves_idor_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
                (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
     else if (repetition && ordering)
@@ -895,7 +925,7 @@ static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depth
 int crl_opponent_moves_id(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
                           uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
 {
-    return opponent_moves_id(ctx, "crl_opponent_moves_id", depths, quiescence, push, node_budget, 0, 0, moves,
+    return opponent_moves_id(ctx, "crl_opponent_moves_id", depths, quiescence, push, node_budget, 0, 0, 0, moves,
                              scores, nodes, flags, depths_done);
 }
 
@@ -903,7 +933,7 @@ int crl_opponent_moves_ord(crl_ctx *ctx, const int32_t *depths, int quiescence, 
                            int ordering, uint16_t *moves, int32_t *scores, int64_t *nodes, uint8_t *flags,
                            int32_t *depths_done)
 {
-    return opponent_moves_id(ctx, "crl_opponent_moves_ord", depths, quiescence, push, node_budget, ordering, 0, moves,
+    return opponent_moves_id(ctx, "crl_opponent_moves_ord", depths, quiescence, push, node_budget, ordering, 0, 0, moves,
                              scores, nodes, flags, depths_done);
 }
 
@@ -912,7 +942,24 @@ int crl_opponent_moves_rep(crl_ctx *ctx, const int32_t *depths, int quiescence, 
                            uint8_t *flags, int32_t *depths_done)
 {
     return opponent_moves_id(ctx, "crl_opponent_moves_rep", depths, quiescence, push, node_budget, ordering, repetition,
-                             moves, scores, nodes, flags, depths_done);
+                             0, moves, scores, nodes, flags, depths_done);
+}
+
+int crl_opponent_moves_ev(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
+                          int ordering, int repetition, int evaluation, uint16_t *moves, int32_t *scores,
+                          int64_t *nodes, uint8_t *flags, int32_t *depths_done)
+{
+    return opponent_moves_id(ctx, "crl_opponent_moves_ev", depths, quiescence, push, node_budget, ordering, repetition,
+                             evaluation, moves, scores, nodes, flags, depths_done);
+}
+
+// the static evaluation of every window slot's current position (csrc/opponent.hpp: STATIC EVALUATION / EVALUATION)
+int crl_opponent_evaluate(crl_ctx *ctx, int evaluation, int32_t *scores)
+{
+    ENTER(ctx, scores && (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL));
+    LAUNCH(ctx, k_opponent_evaluate, ctx->d, evaluation == CRL_OPP_EVAL_POSITIONAL ? 1 : 0, ctx->t_i32c);
+    HIP_TRY(ctx, to_host(ctx, scores, ctx->t_i32c, (size_t)ctx->W));
+    return check_dev_error(ctx);
 }
 
 int crl_sim_reply_opponent_rep(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
@@ -946,6 +993,25 @@ int crl_sim_reply_opponent_rep(crl_ctx *ctx, const int32_t *dev_depths_i32, int 
     else
         LAUNCH(ctx, k_reply_opponent_id, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
                (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    return CRL_OK;
+}
+
+// evaluation = CRL_OPP_EVAL_MATERIAL is the _rep call; CRL_OPP_EVAL_POSITIONAL launches the k_reply_opponent_ev kernel
+// of the same shape
+int crl_sim_reply_opponent_ev(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                              int ordering, int repetition, int evaluation, void *dev_planes_s2,
+                              uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
+{
+    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
+                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
+                   (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1) &&
+                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL));
+    if (evaluation == CRL_OPP_EVAL_MATERIAL)
+        return crl_sim_reply_opponent_rep(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition,
+                                          dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
+    LAUNCH(ctx, reply_ev_kernel(quiescence > 0, ordering != 0, repetition != 0), ctx->d, dev_depths_i32, quiescence,
+           (long long)node_budget, dev_planes_s2, (unsigned long long *)dev_nodes_u64, dev_cuts_u32,
+           (unsigned long long *)dev_depth_sum_u64);
     return CRL_OK;
 }
 

@@ -161,6 +161,64 @@
 // history copy beyond; a board is read (a frame's from LDS, a history one from the ring or the tree) only on a hash
 // hit.  These arrays lie outside the union game_push reuses.  LDS: 3.6 KiB + 864 B = 4 512 B (_idr, _idor) and
 // 6.5 KiB + 928 B = 7 616 B (their _q forms).  (tests/repetition_util.py restates this section.)
+//
+// EVALUATION (the _ev kernels only: evaluation = "positional", an opt-in on top of ITERATIVE DEEPENING, so of a node
+// budget; it combines freely with QUIESCENCE, ORDERING and REPETITION.  Every other launch uses STATIC EVALUATION above
+// and nothing else).  It replaces the static evaluation and nothing else: NODE VALUE 1-3 and 3b, the stand-pat (4c
+// still reads the evaluation before the moves are generated), the orders, the windows, the budget and the cut stay.
+//     Notation.  c is the colour of the piece on square sq and own the pieces of c; rel(sq, c) is the rank for white
+//     and 7 - rank for black; ring(sq) as above; occ is all pieces; PA(c') the squares attacked by the pawns of c';
+//     ksq(c') the king square of c'; zone(c') = king_attacks(ksq(c')) | bit(ksq(c')) (empty for a side without a
+//     king); "ahead" means towards promotion.
+//     Per-piece terms.  Two int32 sums, MG and EG, run over all pieces; a white piece adds, a black piece subtracts;
+//     a term given once goes to both sums.
+//         Pawn    material 100
+//                 advancement, adv = rel - 1 (0 .. 5):                      MG 5 * ring + 6 * adv     EG 12 * adv
+//                 passed -- no enemy pawn ahead on its own or an adjacent file:
+//                                                      MG {0,5,10,20,40,70}[adv]     EG {0,10,20,40,80,140}[adv]
+//                 doubled -- a friendly pawn ahead on its file:             MG -10                    EG -20
+//                 isolated -- no friendly pawn on an adjacent file, any rank:  MG -10                 EG -15
+//         Knight  material 320; position 10 * ring;
+//                 mobility, m = popc(knight_attacks & ~own & ~PA(enemy)):   4 * m
+//         Bishop  material 330; position 5 * ring;
+//                 mobility, m = popc(bishop_attacks(sq, occ) & ~own & ~PA(enemy)):   4 * m
+//         Rook    material 500;
+//                 mobility, m = popc(rook_attacks(sq, occ) & ~own):         MG 2 * m                  EG 4 * m
+//                 its file holds no pawn of either colour:                  MG +20                    EG +10
+//                 its file holds no own pawn but an enemy pawn:             MG +10                    EG +5
+//                 rel = 6:                                                  MG +10                    EG +20
+//         Queen   material 900; position 2 * ring;
+//                 mobility, m = popc((rook_attacks | bishop_attacks) & ~own & ~PA(enemy)):   MG m     EG 2 * m
+//         King    position                                                  MG -10 * ring             EG +10 * ring
+//                 shelter, only when rel(ksq) <= 1: the friendly pawns on the king's file and the adjacent files, on
+//                 the next two ranks ahead of the king:                     MG +8 per pawn            EG 0
+//         N, B, R, Q   king attack -- the piece's attack set (as computed for its mobility, before the ~own and ~PA
+//                 masks) meets zone(enemy):                                 MG N 8, B 8, R 12, Q 20   EG 0
+//     Per side.  Bishop pair: a side with two or more bishops gets MG +30 and EG +40, once.
+//     Phase.  ph = min(24, N + B + 2 * R + 4 * Q), counted over both colours.
+//     Taper.  white = (MG * ph + EG * (24 - ph)) / 24, the division truncating toward zero, so a colour flip (ranks
+//     mirrored, colours and the side to move exchanged) negates it exactly.
+//     Score.  (white to move ? white : -white) + 10; the 10 is the tempo.
+//     Decisions where the table leaves room.  Attack sets stop at the first piece of either colour and include it
+//     (x-rays count nothing); a pinned piece moves as if it were free; en-passant and castling rights are not read;
+//     PA includes squares a pawn attacks whatever stands there; a rook's "file" terms read pawns of every rank, behind
+//     it included; "isolated" and "doubled" are per pawn, so both pawns of an isolated doubled pair are isolated and
+//     the rear one is doubled; with several kings of a colour (no legal game has them) zone is the union.
+//     Bound.  A piece's terms are at most P 100 + 60 + 140 = 300, N 320 + 30 + 32 + 8 = 390, B 330 + 15 + 52 + 8 = 405,
+//     R 500 + 56 + 10 + 20 = 586 (EG; MG 500 + 28 + 20 + 10 + 12 = 570), Q 900 + 6 + 54 = 960 (EG; MG 953), K 48 (MG:
+//     six shelter pawns; EG 30), and never below -30 (the king, MG).  A side has a king and at most 15 other pieces,
+//     each at most a queen: a side's sum lies in [-30, 15 * 960 + 48 + 40] = [-30, 14488], so |MG|, |EG| <= 14518, the
+//     taper lies between them, and |score| <= 14528: well inside (-30000 + k, 30000 - k) for every ply k <= 11, so a
+//     score that is not a mate still cannot be taken for one.
+//     Structure.  Uniform quantities come from the scalar board: PA of both colours, the fills behind passed and
+//     doubled, the eight-bit sets of files that hold a pawn of a colour (isolated, the rook's files), both zones, the
+//     phase and the bishop counts.  Lane-local: the one piece of the lane; the diagonal line_attacks are computed
+//     under predication for B and Q, the orthogonal ones for R and Q, so a wave pays for each once and not once per
+//     piece type; the lane tests its attack set against the masks of both colours and selects the counts, not the
+//     masks.  What depends on the lane number alone is kept from being hoisted out of the search loop (an empty asm
+//     on the lane number): hoisted, it cost the kernels a wave of occupancy and reserved scratch.  |MG|, |EG| < 2^15 (also for every partial sum: a
+//     subset of the pieces obeys the same bound), so MG * 65536 + EG travels through ONE wave reduction as an int32
+//     and is taken apart exactly afterwards.  No LDS, no scratch.  (tests/evaluation_util.py restates this section.)
 #pragma once
 #include "search.hpp"
 
@@ -232,6 +290,109 @@ __device__ inline int opp_evaluate(const Board &b, int lane)
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
     return st_turn(b.state) ? v : -v;
+}
+
+// EVALUATION of the header comment: the positional static evaluation, from the side to move.  `b` is wave-uniform.
+__device__ inline u64 opp_nfill(u64 x) { x |= x << 8; x |= x << 16; return x | (x << 32); }
+__device__ inline u64 opp_sfill(u64 x) { x |= x >> 8; x |= x >> 16; return x | (x >> 32); }
+__device__ inline u64 opp_widen(u64 x) { return x | ((x << 1) & ~FILE_A) | ((x >> 1) & ~FILE_H); }
+
+__device__ inline int opp_evaluate_positional(const Board &b, int lane)
+{
+    // Inside the search loop everything below that depends on the lane alone (the ring, the line masks, the shelter
+    // squares ..) is loop-invariant, and hoisted out it would hold some twenty VGPRs for the whole search.  The empty
+    // asm makes the lane number opaque, so these values are computed where they are used and die there.
+    asm volatile("" : "+v"(lane));
+    const u64 occ = occupied(b);
+    const u64 wh = b.white & occ, bl = occ & ~b.white;
+    // ---- the lane's piece and its attack set: the slider lines under predication, each once for the wave
+    const int pt = piece_at(b, lane);
+    const bool white = (wh >> lane) & 1;
+    const int f = lane & 7, r = lane >> 3;
+    const int rf = f < 7 - f ? f : 7 - f, rr = r < 7 - r ? r : 7 - r;
+    const int ring = rf < rr ? rf : rr;
+    const int rel = white ? r : 7 - r;
+    u64 at = 0;
+    if (pt == KNIGHT) at = knight_attacks(lane);
+    if (pt == BISHOP || pt == QUEEN) at = bishop_attacks(lane, occ);
+    if (pt == ROOK || pt == QUEEN) at |= rook_attacks(lane, occ);
+    // ---- uniform masks from the scalar board, each read by the lanes at once: bit sq = the pawn on sq has the
+    // property, whichever its colour; the files that hold a pawn of a colour are eight bits
+    const u64 wp = b.bb[PAWN] & wh, bp = b.bb[PAWN] & bl;
+    const u64 stopped = (opp_sfill(opp_widen(bp) >> 8) & wp) | (opp_nfill(opp_widen(wp) << 8) & bp);    // not passed
+    const u64 doubled = (opp_sfill(wp >> 8) & wp) | (opp_nfill(bp << 8) & bp);
+    const bool is_stopped = (stopped >> lane) & 1, is_doubled = (doubled >> lane) & 1;
+    const u32 wf8 = (u32)opp_sfill(wp) & 0xFFu, bf8 = (u32)opp_sfill(bp) & 0xFFu;
+    const u32 ownf = white ? wf8 : bf8, enf = white ? bf8 : wf8;
+    const bool is_lonely = !((((ownf << 1) | (ownf >> 1)) >> f) & 1);                  // (read by a pawn)
+    const bool is_open = !(((ownf | enf) >> f) & 1), is_half = !((ownf >> f) & 1);     // (by a rook; half: not open)
+    // ---- per colour, against uniform masks (no 64-bit select per lane): the squares of the attack set not held by
+    // an own piece, those of them an enemy pawn attacks, and whether the set meets the enemy king's zone
+    const u64 pa_w = ((wp << 9) & ~FILE_A) | ((wp << 7) & ~FILE_H), pa_b = ((bp >> 7) & ~FILE_A) | ((bp >> 9) & ~FILE_H);
+    const u64 wrow = opp_widen(b.bb[KING] & wh), brow = opp_widen(b.bb[KING] & bl);
+    const u64 zone_w = wrow | (wrow << 8) | (wrow >> 8), zone_b = brow | (brow << 8) | (brow >> 8);
+    const int free_sq = white ? popc(at & ~wh) : popc(at & ~bl);
+    const int guarded = white ? popc(at & ~wh & pa_b) : popc(at & ~bl & pa_w);
+    const int m = pt == ROOK ? free_sq : free_sq - guarded;
+    const bool hit = ((white ? zone_b : zone_w) & at) != 0;
+    int mg = 0, eg = 0;
+    if (pt == PAWN) {
+        const int adv = rel - 1;
+        mg = 100 + 5 * ring + 6 * adv;
+        eg = 100 + 12 * adv;
+        if (!is_stopped) {                                 // {0,5,10,20,40,70} and twice that
+            const int pm = adv <= 0 ? 0 : (5 << (adv - 1)) - (adv == 5 ? 10 : 0);      // adv = 5: 80 - 10
+            mg += pm; eg += 2 * pm;
+        }
+        if (is_doubled) { mg -= 10; eg -= 20; }
+        if (is_lonely) { mg -= 10; eg -= 15; }
+    } else if (pt == KNIGHT) {
+        mg = eg = 320 + 10 * ring + 4 * m;
+        if (hit) mg += 8;
+    } else if (pt == BISHOP) {
+        mg = eg = 330 + 5 * ring + 4 * m;
+        if (hit) mg += 8;
+    } else if (pt == ROOK) {
+        mg = 500 + 2 * m;
+        eg = 500 + 4 * m;
+        if (is_open) { mg += 20; eg += 10; }
+        else if (is_half) { mg += 10; eg += 5; }
+        if (rel == 6) { mg += 10; eg += 20; }
+        if (hit) mg += 12;
+    } else if (pt == QUEEN) {
+        mg = 900 + 2 * ring + m;
+        eg = 900 + 2 * ring + 2 * m;
+        if (hit) mg += 20;
+    } else if (pt == KING) {
+        mg = -10 * ring;
+        eg = 10 * ring;
+        if (rel <= 1) {                                    // the shelter: own pawns on the next two ranks ahead
+            const u64 row = opp_widen(bit(lane));
+            mg += 8 * (white ? popc(((row << 8) | (row << 16)) & wp) : popc(((row >> 8) | (row >> 16)) & bp));
+        }
+    }
+    int v = mg * 65536 + eg;                               // |mg|, |eg| < 2^15: one reduction carries both
+    if (!white) v = -v;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    // ---- uniform again: the bishop pairs, the phase, the taper
+    int EG = (int)(short)(v & 0xFFFF);
+    int MG = (v - EG) >> 16;                               // (v - EG is a multiple of 65536)
+    const int pair = (popc(b.bb[BISHOP] & wh) >= 2 ? 1 : 0) - (popc(b.bb[BISHOP] & bl) >= 2 ? 1 : 0);
+    MG += 30 * pair;
+    EG += 40 * pair;
+    int ph = popc(b.bb[KNIGHT]) + popc(b.bb[BISHOP]) + 2 * popc(b.bb[ROOK]) + 4 * popc(b.bb[QUEEN]);
+    if (ph > 24) ph = 24;
+    const int w = (MG * ph + EG * (24 - ph)) / 24;
+    return (st_turn(b.state) ? w : -w) + 10;
+}
+
+// the static evaluation of a search: POS selects EVALUATION, otherwise STATIC EVALUATION
+template <bool POS>
+__device__ inline int opp_static(const Board &b, int lane)
+{
+    if (POS) return opp_evaluate_positional(b, lane);
+    return opp_evaluate(b, lane);
 }
 
 __device__ inline bool opp_tactical(const Board &b, u64 occ, u64 own, u32 mv)
@@ -398,14 +559,16 @@ __device__ inline void opp_move_to_front(u16 *mv, int n, u32 pm, int lane)
 // here).  Every line marked ORD folds away without it.
 // REP: REPETITION of the header comment, on top of ID; rs and rr are read only then.  Every line marked REP folds away
 // without it.
+// POS: EVALUATION of the header comment in place of STATIC EVALUATION, on top of ID; nothing else reads it.
 struct OppResult { u32 mv; int score; long long nodes; bool done; int depth_done; };
 
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false>
 __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long long limit, OppFrame *f, int lane,
                                        OppRepLds<QS> *rs = nullptr, OppRepRoot rr = OppRepRoot())
 {
     static_assert(ID || !ORD, "ORDERING requires ITERATIVE DEEPENING");
     static_assert(ID || !REP, "REPETITION requires ITERATIVE DEEPENING");
+    static_assert(ID || !POS, "EVALUATION requires ITERATIVE DEEPENING");
     int K = 0;                                             // REP: the positions behind the root that hh holds
     if (ORD) {                                             // both killers of every ply: NO_MOVE
         constexpr int NF = QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1;
@@ -432,7 +595,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
         const bool quiet = QS && k >= D;                   // a quiescence node, j = k - D
         int stand = 0;
         bool chk = false;
-        if (quiet) { stand = uni(opp_evaluate(b, lane)); chk = opp_in_check(b); }
+        if (quiet) { stand = uni(opp_static<POS>(b, lane)); chk = opp_in_check(b); }
         // a node that searches no move: the horizon; with quiescence 4a, and the stand-pat at or above beta of 4c
         const bool horizon = QS ? quiet && (k >= D + Q || (!chk && stand >= be)) : k == D;
         MoveGenInfo mi = wave_movegen(b, lane, horizon ? nullptr : F->mv);
@@ -470,7 +633,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
         }
         if (res != RESULT_NONE) v = res == 0 ? 0 : -(OPP_MATE - k);
         else if (REP && rep_hit) v = 0;
-        else if (horizon) v = QS ? stand : uni(opp_evaluate(b, lane));
+        else if (horizon) v = QS ? stand : uni(opp_static<POS>(b, lane));
         else {
             __syncthreads();                               // F->mv visible
             int cnt = n, best0 = -OPP_INF, nt = 0;         // ORD: nt, the node's tactical moves
@@ -572,7 +735,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
 
 // One slot of k_opponent_moves / k_opponent_moves_q and, ID, of their _id forms.  Window-relative rows: depths / moves /
 // scores / nodes_out / flags [count] and, ID only, depths_done [count]
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false>
 __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, int push, long long limit, u16 *moves,
                                            int32_t *scores, long long *nodes_out, uint8_t *flags, OppLds<QS> &s,
                                            int32_t *depths_done = nullptr, OppRepLds<QS> *rs = nullptr)
@@ -592,7 +755,7 @@ __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, 
     const Board root = uni_board(d.cur[g]);
     OppRepRoot rr;                                         // REP: the root is the game's current position
     rr.d = &d; rr.g = g; rr.tp = 0; rr.ply = REP ? uni(d.game[g].ply) : 0;
-    const OppResult o = opp_search<QS, ID, ORD, REP>(root, D, Q, limit, s.f, lane, rs, rr);
+    const OppResult o = opp_search<QS, ID, ORD, REP, POS>(root, D, Q, limit, s.f, lane, rs, rr);
     if (lane == 0) {
         moves[r] = (u16)o.mv;
         scores[r] = o.score;
@@ -708,7 +871,7 @@ __global__ __launch_bounds__(64) void k_opponent_moves_idor_q(Dev d, const int32
 // search is ITERATIVE DEEPENING under the budget `limit`, and depth_acc [count] sums the completed depths.
 // REP: REPETITION -- S1 stands at tree ply 2 * path_len - 1 of the one path d.path_node holds, so what led to it is the
 // S1 / S2 of the pending node's ancestors and then the game's ring.
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false>
 __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, long long limit, void *planes2,
                                           unsigned long long *nodes_acc, uint32_t *cuts_acc, OppLds<QS> &s,
                                           unsigned long long *depth_acc = nullptr, OppRepLds<QS> *rs = nullptr)
@@ -725,7 +888,7 @@ __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, l
     const Board s1 = uni_board(d.node[(size_t)g * d.N + c].s1);
     OppRepRoot rr;
     rr.d = &d; rr.g = g; rr.tp = REP ? 2 * uni(d.game[g].path_len) - 1 : 0; rr.ply = REP ? uni(d.game[g].ply) : 0;
-    const OppResult o = opp_search<QS, ID, ORD, REP>(s1, D, Q, limit, s.f, lane, rs, rr);
+    const OppResult o = opp_search<QS, ID, ORD, REP, POS>(s1, D, Q, limit, s.f, lane, rs, rr);
     if (o.mv == NO_MOVE) { dev_error(d, DERR_STATE); return; }              // S1 is running: it has a legal move
     if (lane == 0) {
         nodes_acc[r] += (unsigned long long)o.nodes;
@@ -820,6 +983,48 @@ __global__ __launch_bounds__(64) void k_reply_opponent_idor_q(Dev d, const int32
     __shared__ OppLds<true> s;
     __shared__ OppRepLds<true> rs;
     reply_opponent_row<true, true, true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
+}
+
+// EVALUATION: the sixteen budgeted kernels once more with the positional evaluation, as two kernel templates (the
+// shapes _id, _ido, _idr, _idor, each with and without quiescence).  One argument list for all: Q is not read
+// without QS, and the REPETITION arrays exist in LDS only with REP.
+template <bool QS, bool ORD, bool REP>
+__global__ __launch_bounds__(64) void k_opponent_moves_ev(Dev d, const int32_t *depths, int Q, int push,
+                                                          long long budget, u16 *moves, int32_t *scores,
+                                                          long long *nodes_out, uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<QS> s;
+    if constexpr (REP) {
+        __shared__ OppRepLds<QS> rs;
+        opponent_moves_slot<QS, true, ORD, true, true>(d, depths, QS ? Q : 0, push, budget, moves, scores, nodes_out,
+                                                       flags, s, depths_done, &rs);
+    } else
+        opponent_moves_slot<QS, true, ORD, false, true>(d, depths, QS ? Q : 0, push, budget, moves, scores, nodes_out,
+                                                        flags, s, depths_done);
+}
+
+template <bool QS, bool ORD, bool REP>
+__global__ __launch_bounds__(64) void k_reply_opponent_ev(Dev d, const int32_t *depths, int Q, long long budget,
+                                                          void *planes2, unsigned long long *nodes_acc,
+                                                          uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<QS> s;
+    if constexpr (REP) {
+        __shared__ OppRepLds<QS> rs;
+        reply_opponent_row<QS, true, ORD, true, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc, cuts_acc, s,
+                                                      depth_acc, &rs);
+    } else
+        reply_opponent_row<QS, true, ORD, false, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc, cuts_acc, s,
+                                                       depth_acc);
+}
+
+// the static evaluation of every window slot's current position: scores [count], window-relative
+__global__ __launch_bounds__(64) void k_opponent_evaluate(Dev d, int positional, int32_t *scores)
+{
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    const Board b = uni_board(d.cur[g]);
+    const int v = positional ? opp_evaluate_positional(b, lane) : opp_evaluate(b, lane);
+    if (lane == 0) scores[r] = v;
 }
 
 }  // namespace crl

@@ -239,6 +239,7 @@ class LockstepEngine(object):
     A budgeted player with ``ordering`` replies through the ordered kernels (``k_reply_opponent_ido``), eager and captured.
     A budgeted player with ``repetition`` replies through the repetition-aware kernels (``k_reply_opponent_idr`` /
     ``_idor``): a reply search scores a position it has had, in its own line, on the tree path or in the game, a draw.
+    A budgeted player with ``evaluation="positional"`` replies through the ``k_reply_opponent_ev`` kernel of the same shape.
     """
 
     def __init__(self, evaluator, n_games, max_sims, device=0, max_plies=4096,
@@ -423,7 +424,8 @@ class LockstepEngine(object):
                                     self.reply_nodes.data_ptr(), self.reply_cuts.data_ptr(),
                                     quiescence=self.reply.quiescence, node_budget=budget,
                                     dev_depth_sum=None if budget is None else self.reply_depth_sum.data_ptr(),
-                                    ordering=self.reply.ordering, repetition=self.reply.repetition)
+                                    ordering=self.reply.ordering, repetition=self.reply.repetition,
+                                    evaluation=self.reply.evaluation)
 
     def phase_tower_s2(self):
         if self.legal_priors:

@@ -10,7 +10,8 @@ with the in-slot playout call (``Context.rollout_games``, words from ``random.Ra
 
 The player sees a repetition below the root only on request (``repetition=True`` / ``--repetition``, with a node
 budget; csrc/opponent.hpp, REPETITION): without it a large share of the games are draws in which the side that is ahead
-shuffles until the fifth occurrence.
+shuffles until the fifth occurrence.  ``evaluation="positional"`` / ``--eval positional`` (with a node budget;
+csrc/opponent.hpp, EVALUATION) gives both sides the positional static evaluation instead of material and centrality.
 """
 import argparse
 import logging
@@ -59,7 +60,7 @@ def side_depths(draws, white_to_move):
 
 
 def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512,
-             quiescence=0, node_budget=None, ordering=False, repetition=False):
+             quiescence=0, node_budget=None, ordering=False, repetition=False, evaluation="material"):
     """Plays ``num_games`` games, saves the finished ones to ``save_path`` (appending to what the file holds, as
     ``DatasetGame.save`` does) and returns the ``DatasetGame`` it saved.  The reference's ``gen_data`` forgets to
     pass ``depth`` and ``random_dep`` on to ``play_game`` (gen_data_stockfish.py:44-49); here both are honoured.
@@ -67,11 +68,13 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
     the quiescence plies of both sides past their depths (0 .. CRL_OPP_MAX_QUIESCENCE; 0: none).  ``node_budget``
     (None: none): both sides deepen iteratively up to their depths and stop at that many nodes per move; ``ordering``
     (needs a ``node_budget``): with the move ORDERING of csrc/opponent.hpp; ``repetition`` (needs a ``node_budget``):
-    with its REPETITION rule, both sides score a position below the root that occurred before a draw."""
+    with its REPETITION rule, both sides score a position below the root that occurred before a draw; ``evaluation``
+    ("positional" needs a ``node_budget``): both sides search with its EVALUATION."""
     if ordering and node_budget is None:
         raise ValueError("ordering needs a node_budget")
     if repetition and node_budget is None:
         raise ValueError("repetition needs a node_budget")
+    _lib.opponent_evaluation(evaluation, node_budget)
     if node_budget is not None and int(node_budget) < 1:
         raise ValueError("node_budget must be None or at least 1")
     quiescence = int(quiescence)
@@ -101,7 +104,7 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
                 break
             ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True,
                                quiescence=quiescence, node_budget=node_budget, ordering=bool(ordering),
-                               repetition=bool(repetition))
+                               repetition=bool(repetition), evaluation=evaluation)
             results = ctx.results()
         moves, plies, results = ctx.records()
     finally:
@@ -129,6 +132,8 @@ def main(argv=None):
                    help="Order the moves of the --nodes search by victim and killer moves, both sides.")
     p.add_argument("--repetition", action="store_true", default=False,
                    help="The --nodes search scores a position below the root that occurred before a draw, both sides.")
+    p.add_argument("--eval", dest="evaluation", choices=sorted(_lib.OPP_EVALUATIONS), default="material",
+                   help="Static evaluation of the --nodes search, both sides (positional needs --nodes).")
     p.add_argument("--random_depth", action="store_true", default=False,
                    help="Use normal distribution of depths with mean --depth.")
     p.add_argument("--debug", action="store_true", default=False, help="Log debug messages on screen. Default false.")
@@ -138,7 +143,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.DEBUG if a.debug else logging.INFO)
     gen_data(a.data_path, num_games=a.games, depth=a.depth, random_dep=a.random_depth,
              opening_plies=a.opening_plies, seed=a.seed, quiescence=a.quiescence,
-             node_budget=a.nodes, ordering=a.ordering, repetition=a.repetition)
+             node_budget=a.nodes, ordering=a.ordering, repetition=a.repetition, evaluation=a.evaluation)
 
 
 if __name__ == "__main__":

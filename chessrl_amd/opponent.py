@@ -12,7 +12,9 @@ iteratively up to ``search_depth`` and stops at that many nodes per move (oppone
 deterministic counterpart of the reference's ``Limit(time=...)`` (stockfish.py:14-21); ``ordering=True`` on top of a
 budget orders the moves below the root by victim and killer moves (opponent.hpp, ORDERING); ``repetition=True`` on top
 of a budget scores a position below the root that occurred before -- on the search path or in the game's reversible
-history -- a draw (opponent.hpp, REPETITION), so a side that is ahead stops shuffling into the fivefold.  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
+history -- a draw (opponent.hpp, REPETITION), so a side that is ahead stops shuffling into the fivefold;
+``evaluation="positional"`` on top of a budget replaces the static evaluation (material and centrality) by a tapered
+one with pawn structure, mobility, files, king shelter and king attack (opponent.hpp, EVALUATION).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
 these classes are the one-game drop-in surface over it.
 """
 import numpy as np
@@ -39,10 +41,11 @@ class MinimaxPlayer(Player):
     then the depth the last search completed (None without a budget).  ``ordering`` (needs a ``node_budget``): below
     the root that search tries the moves by victim, then the killer moves of the ply (opponent.hpp, ORDERING); with a
     budget it does not reach it plays the same move for fewer nodes.  ``repetition`` (needs a ``node_budget``): a node
-    below the root whose position occurred before is worth 0 (opponent.hpp, REPETITION)."""
+    below the root whose position occurred before is worth 0 (opponent.hpp, REPETITION).  ``evaluation``: "material"
+    or "positional" (needs a ``node_budget``; opponent.hpp, EVALUATION)."""
 
     def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0, node_budget=None, ordering=False,
-                 repetition=False):
+                 repetition=False, evaluation="material"):
         super().__init__(color)
         if not 1 <= int(search_depth) <= MAX_DEPTH:
             raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
@@ -62,6 +65,8 @@ class MinimaxPlayer(Player):
         if repetition and self.node_budget is None:
             raise ValueError("repetition needs a node_budget")
         self.repetition = bool(repetition)
+        _lib.opponent_evaluation(evaluation, self.node_budget)
+        self.evaluation = evaluation
         self.last = None                      # (score, nodes, flag) of the last search
         self.last_depth = None                # with a budget: the depth that search completed
 
@@ -71,7 +76,7 @@ class MinimaxPlayer(Player):
         ctx = arena().one(game._slot)
         out = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False, node_limit=self.node_limit,
                                  quiescence=self.quiescence, node_budget=self.node_budget, ordering=self.ordering,
-                                 repetition=self.repetition)
+                                 repetition=self.repetition, evaluation=self.evaluation)
         moves, scores, nodes, flags = out[:4]
         self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
         self.last_depth = int(out[4][0]) if self.node_budget is not None else None
@@ -86,11 +91,12 @@ class MinimaxPlayer(Player):
 class GameOpponent(Game):
     """Mirror of ``GameStockfish``: a game against the built-in opponent.  ``opponent``: a ``MinimaxPlayer``, or
     None for one of depth ``opponent_depth``, ``opponent_quiescence``, ``opponent_budget`` (the player's
-    ``node_budget``), ``opponent_ordering`` (its ``ordering``) and ``opponent_repetition`` (its ``repetition``) with the
-    colour opposite to ``player_color``."""
+    ``node_budget``), ``opponent_ordering`` (its ``ordering``), ``opponent_repetition`` (its ``repetition``) and
+    ``opponent_evaluation`` (its ``evaluation``) with the colour opposite to ``player_color``."""
 
     def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2,
-                 opponent_quiescence=0, opponent_budget=None, opponent_ordering=False, opponent_repetition=False):
+                 opponent_quiescence=0, opponent_budget=None, opponent_ordering=False, opponent_repetition=False,
+                 opponent_evaluation="material"):
         if opponent is not None and not isinstance(opponent, MinimaxPlayer):
             raise ValueError("opponent must be a MinimaxPlayer or None")
         self.opponent = None                  # (a board's move stack is replayed by plain Game.move)
@@ -98,7 +104,8 @@ class GameOpponent(Game):
         if opponent is None:
             opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth,
                                      quiescence=opponent_quiescence, node_budget=opponent_budget,
-                                     ordering=opponent_ordering, repetition=opponent_repetition)
+                                     ordering=opponent_ordering, repetition=opponent_repetition,
+                                     evaluation=opponent_evaluation)
         self.opponent = opponent
 
     def move(self, movement):

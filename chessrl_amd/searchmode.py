@@ -117,4 +117,5 @@ class SearchMode(object):
         """Hashable; equal for modes that search alike (the player's settings, not its identity)."""
         r = self.reply
         return (self.threads, self.simulate,
-                None if r is None else (r.search_depth, r.node_limit, r.quiescence, r.node_budget, r.ordering, r.repetition))
+                None if r is None else (r.search_depth, r.node_limit, r.quiescence, r.node_budget, r.ordering, r.repetition,
+                                         r.evaluation))

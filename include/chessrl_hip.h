@@ -70,7 +70,8 @@ typedef struct crl_ctx crl_ctx;
  * signature hands the GPU garbage pointers).  crl_source_hash(): sha256 over the sources (csrc/ + this
  * header + compiler flags) the library was built from, as chessrl_amd/_lib.py computes it; the string
  * is also findable in the file itself behind the marker "CRL_SRC_HASH=".  No reference counterpart.
- * (The _ord and _rep entries of the built-in opponent are additions that change no existing signature: still 9.) */
+ * (The _ord, _rep and _ev entries of the built-in opponent and crl_opponent_evaluate are additions that change no
+ * existing signature or meaning: still 9.) */
 #define CRL_ABI_VERSION 9
 int  crl_abi_version(void);
 const char *crl_source_hash(void);
@@ -380,6 +381,26 @@ int  crl_opponent_moves_rep(crl_ctx *ctx, const int32_t *depths /*G*/, int quies
 int  crl_sim_reply_opponent_rep(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
                                 int ordering, int repetition, void *dev_planes_s2, uint64_t *dev_nodes_u64,
                                 uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64);
+/* The two _rep calls with an opt-in positional EVALUATION (csrc/opponent.hpp states it, term by term, with its
+ * bound).  evaluation = CRL_OPP_EVAL_MATERIAL is the _rep call, array for array, from the same kernels.
+ * evaluation = CRL_OPP_EVAL_POSITIONAL: the static evaluation of the search -- at the horizon and as the stand-pat of
+ * a quiescence node -- is the tapered sum of material, advancement, passed / doubled / isolated pawns, mobility, open
+ * files, the seventh rank, the bishop pair, king shelter and king attack, plus a tempo; nothing else of the search
+ * changes.  Conventional untuned weights, no Elo claim.  |score| <= 14528 unless it is a mate score.
+ * CRL_ERR_ARG: an evaluation outside {0, 1}, and what the _rep calls refuse.  No state changes on an error. */
+#define CRL_OPP_EVAL_MATERIAL 0
+#define CRL_OPP_EVAL_POSITIONAL 1
+int  crl_opponent_moves_ev(crl_ctx *ctx, const int32_t *depths /*G*/, int quiescence, int push, int64_t node_budget,
+                           int ordering, int repetition, int evaluation, uint16_t *moves /*G*/, int32_t *scores /*G*/,
+                           int64_t *nodes /*G*/, uint8_t *flags /*G*/, int32_t *depths_done /*G*/);
+int  crl_sim_reply_opponent_ev(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, int repetition, int evaluation, void *dev_planes_s2,
+                               uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64);
+/* The static evaluation of every window slot's current position, from the side to move, whatever the game's result:
+ * scores[g] (host int32, synchronous, window-relative).  evaluation as above: 0 is STATIC EVALUATION of
+ * csrc/opponent.hpp, 1 its EVALUATION.  No search, no state change.
+ * CRL_ERR_ARG: NULL scores, an evaluation outside {0, 1}. */
+int  crl_opponent_evaluate(crl_ctx *ctx, int evaluation, int32_t *scores /*G*/);
 
 /* ---- threads > 1: virtual-loss waves of simulations per game (csrc/search_wave.hpp) --------------------------
  * The reference runs `threads` explore_tree workers on one tree, kept apart by a virtual loss (mctree.py:12,173-176,

@@ -6,6 +6,7 @@
     python tools/opponent_probe.py --budget 150,300,600,1500 --depths 2,3 --max-depth 3
     python tools/opponent_probe.py --ordering --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2
     python tools/opponent_probe.py --repetition --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2 --opening-plies 40
+    python tools/opponent_probe.py --eval positional --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words), so the slots hold
 different positions.  Per depth, in depth order: one warm-up launch, then three timed ones (host wall time around the
@@ -21,7 +22,11 @@ profiles/opponent_probe_ord.json.  --repetition: likewise every budget is run wi
 off and on in the same process, the launches alternating; the rule-on rows are keyed "<=<depth>@<B>[+q<Q>] repeating-aware"
 and carry the cost per node as a ratio to the rule-off row of the same run and the share of slots that play another
 move; the output goes to profiles/opponent_probe_rep.json.  At --opening-plies 6 few slots have reversible plies behind
-them; at 40 most do.  With --ordering as well, both rows of a budget are ordered.  No threshold: this is a measurement.
+them; at 40 most do.  With --ordering as well, both rows of a budget are ordered.  --eval positional: every budget is
+run with the material evaluation and with the positional EVALUATION of opponent.hpp in the same process, the launches
+alternating; --ordering and --repetition then hold for both rows, the positional rows are keyed "... positional" and
+carry the time per node and per launch as ratios to the material row of the same run and the share of slots that play
+another move; the output goes to profiles/opponent_probe_eval.json.  No threshold: this is a measurement.
 """
 import argparse
 import json
@@ -47,11 +52,15 @@ def main():
     ap.add_argument("--ordering", action="store_true", help="run every --budget with ordering off and on, alternating")
     ap.add_argument("--repetition", action="store_true",
                     help="run every --budget with the repetition rule off and on, alternating")
+    ap.add_argument("--eval", dest="evaluation", default="material", choices=("material", "positional"),
+                    help="positional: run every --budget with the material and the positional evaluation, alternating")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     budgets = [int(b) for b in args.budget.split(",") if b]
     if args.out is None:
-        name = ("opponent_probe.json" if not budgets else "opponent_probe_rep.json" if args.repetition else
+        name = ("opponent_probe.json" if not budgets else
+                "opponent_probe_eval.json" if args.evaluation == "positional" else
+                "opponent_probe_rep.json" if args.repetition else
                 "opponent_probe_ord.json" if args.ordering else "opponent_probe_id.json")
         args.out = os.path.join(ROOT, "profiles", name)
     import numpy as np
@@ -74,7 +83,11 @@ def main():
             kw["node_budget"] = budget
         # the launches of a case alternate between its variants: ordering off and, with --ordering, on
         variants = [(key, kw)]
-        if budget is not None and args.repetition:
+        if budget is not None and args.evaluation == "positional":
+            base = (key + (" ordered" if args.ordering else "") + (" repeating-aware" if args.repetition else ""),
+                    dict(kw, ordering=args.ordering, repetition=args.repetition))
+            variants = [base, (base[0] + " positional", dict(base[1], evaluation="positional"))]
+        elif budget is not None and args.repetition:
             if args.ordering:
                 variants = [(key + " ordered", dict(kw, ordering=True))]
             variants.append((variants[0][0] + " repeating-aware", dict(variants[0][1], repetition=True)))
@@ -101,7 +114,12 @@ def main():
             if budget is not None:
                 out["depths"][k]["depth_done_histogram"] = np.bincount(last[k][4][searched], minlength=depth + 1).tolist()
             print(k, json.dumps(out["depths"][k]), flush=True)
-        if len(variants) == 2 and args.repetition:   # the rule's cost per node against the rule-off row of this run
+        if len(variants) == 2 and args.evaluation == "positional":     # against the material row of this run
+            off, on = out["depths"][variants[0][0]], out["depths"][variants[1][0]]
+            on["time_per_node_ratio_to_material"] = off["nodes_per_s"] / on["nodes_per_s"]
+            on["ms_per_launch_ratio_to_material"] = on["ms_per_launch"] / off["ms_per_launch"]
+            on["share_of_slots_with_another_move"] = float((last[variants[0][0]][0] != last[variants[1][0]][0]).mean())
+        elif len(variants) == 2 and args.repetition:   # the rule's cost per node against the rule-off row of this run
             off, on = out["depths"][variants[0][0]], out["depths"][variants[1][0]]
             on["time_per_node_ratio_to_rule_off"] = off["nodes_per_s"] / on["nodes_per_s"]
             on["ms_per_launch_ratio_to_rule_off"] = on["ms_per_launch"] / off["ms_per_launch"]
