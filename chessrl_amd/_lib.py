@@ -70,6 +70,7 @@ SYMBOLS = [
     "crl_opponent_moves_ord", "crl_sim_reply_opponent_ord",
     "crl_opponent_moves_rep", "crl_sim_reply_opponent_rep",
     "crl_opponent_moves_ev", "crl_sim_reply_opponent_ev", "crl_opponent_evaluate",
+    "crl_opponent_moves_sel", "crl_sim_reply_opponent_sel",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
     "crl_advance_one",
@@ -86,6 +87,14 @@ def evaluation_name(evaluation):
     if not isinstance(evaluation, str) or evaluation not in OPP_EVALUATIONS:
         raise ValueError("evaluation must be one of %s" % ", ".join('"%s"' % k for k in OPP_EVALUATIONS))
     return evaluation
+
+
+def opponent_selective(selective, ordering):
+    """Whether the search is selective (csrc/opponent.hpp, SELECTIVE); a ValueError for one without ordering (which
+    itself needs a node budget)."""
+    if selective and not ordering:
+        raise ValueError("selective needs ordering")
+    return bool(selective)
 
 
 def opponent_evaluation(evaluation, node_budget):
@@ -276,6 +285,8 @@ def lib():
     L.crl_sim_reply_opponent_rep.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, vp, vp, vp, vp]
     L.crl_opponent_moves_ev.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, i32, i32, vp, vp, vp, vp, vp]
     L.crl_sim_reply_opponent_ev.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, i32, vp, vp, vp, vp]
+    L.crl_opponent_moves_sel.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.crl_sim_reply_opponent_sel.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, i32, i32, vp, vp, vp, vp]
     L.crl_opponent_evaluate.argtypes = [vp, i32, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     L.crl_wave_config.argtypes = [vp, i32]
@@ -606,7 +617,7 @@ class Context(object):
 
     def sim_reply_opponent(self, dev_depths, node_limit, dev_planes_s2, dev_nodes, dev_cuts, quiescence=0,
                            node_budget=None, dev_depth_sum=None, ordering=False, repetition=False,
-                           evaluation="material"):
+                           evaluation="material", selective=False):
         """``sim_reply`` with the built-in opponent's move as the reply: device pointers to int32 [count] depths, the
         planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies; ``quiescence`` plies (0 ..
         OPP_MAX_QUIESCENCE) past the depth.  ``node_budget`` (not None): iterative deepening up to the depths under
@@ -616,7 +627,17 @@ class Context(object):
         budgeted search with REPETITION (a repeated position below the root is a draw), ``crl_sim_reply_opponent_rep``;
         False calls the entry it called.  ``evaluation`` ("positional" needs a ``node_budget``): the budgeted search with
         EVALUATION in place of the material evaluation, ``crl_sim_reply_opponent_ev``; "material" calls the entry it
-        called."""
+        called.  ``selective`` (needs ``ordering``): the ordered search with SELECTIVE (null-move pruning and late-move
+        reductions), ``crl_sim_reply_opponent_sel``; False calls the entry it called."""
+        if opponent_selective(selective, ordering):
+            if node_budget is None:
+                raise ValueError("ordering needs a node_budget")
+            self._ck(self._L.crl_sim_reply_opponent_sel(
+                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)), 1,
+                1 if repetition else 0, 1 if opponent_evaluation(evaluation, node_budget) else 0, 1,
+                ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts),
+                ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_sel")
+            return
         if opponent_evaluation(evaluation, node_budget):
             self._ck(self._L.crl_sim_reply_opponent_ev(
                 self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)),
@@ -780,7 +801,7 @@ class Context(object):
 
     # ---- the built-in opponent (csrc/opponent.hpp; stockfish.py:23-31, gamestockfish.py:27-41) ------
     def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT, quiescence=0, node_budget=None,
-                       ordering=False, repetition=False, evaluation="material"):
+                       ordering=False, repetition=False, evaluation="material", selective=False):
         """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it,
         with ``quiescence`` plies (0 .. OPP_MAX_QUIESCENCE, one value per call) of quiescence search past the depth.
         Returns (moves u16, scores i32, nodes i64, flags u8); with ``push`` the moves are played.  ``node_budget`` (not
@@ -792,7 +813,10 @@ class Context(object):
         history, is worth 0), through ``crl_opponent_moves_rep``; False calls the entry it called.  ``evaluation``
         ("positional" needs a ``node_budget``): that search with EVALUATION (csrc/opponent.hpp: pawn structure,
         mobility, files, king safety, tapered) in place of the material evaluation, through ``crl_opponent_moves_ev``;
-        "material" calls the entry it called."""
+        "material" calls the entry it called.  ``selective`` (needs ``ordering``): the ordered search with SELECTIVE
+        (csrc/opponent.hpp: null-move pruning and late-move reductions), through ``crl_opponent_moves_sel``; False
+        calls the entry it called."""
+        selective = opponent_selective(selective, ordering)
         if ordering and node_budget is None:
             raise ValueError("ordering needs a node_budget")
         if repetition and node_budget is None:
@@ -806,6 +830,13 @@ class Context(object):
         flags = np.zeros(self.G, np.uint8)
         if node_budget is not None:
             done = np.zeros(self.G, np.int32)
+            if selective:
+                self._ck(self._L.crl_opponent_moves_sel(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
+                                                        min(int(node_budget), int(node_limit)), 1,
+                                                        1 if repetition else 0, 1 if positional else 0, 1, _ptr(moves),
+                                                        _ptr(scores), _ptr(nodes), _ptr(flags), _ptr(done)),
+                         "crl_opponent_moves_sel")
+                return moves, scores, nodes, flags, done
             if positional:
                 self._ck(self._L.crl_opponent_moves_ev(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
                                                        min(int(node_budget), int(node_limit)), 1 if ordering else 0,

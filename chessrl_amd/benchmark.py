@@ -17,7 +17,8 @@ black first get the opponent's opening move (gamestockfish.py:31-33); then per m
 The opponent sees a repetition below the root only on request: ``opponent_repetition=True`` / ``--repetition`` (needs a
 budget; csrc/opponent.hpp, REPETITION).  Without it, games it is winning may still end as draws by the fifth occurrence.
 Its static evaluation is material and centrality unless ``opponent_evaluation="positional"`` / ``--eval positional``
-(needs a budget; csrc/opponent.hpp, EVALUATION) asks for the positional one.
+(needs a budget; csrc/opponent.hpp, EVALUATION) asks for the positional one.  ``opponent_selective=True`` /
+``--selective`` (needs ordering; csrc/opponent.hpp, SELECTIVE) adds null-move pruning and late-move reductions.
 """
 import argparse
 import os
@@ -49,7 +50,7 @@ def _load_model(model_dir):
 
 
 def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence=0, budget=None,
-                 ordering=False, repetition=False, evaluation="material"):
+                 ordering=False, repetition=False, evaluation="material", selective=False):
     """(moves, plies, results) of the games with ``Agent.best_move(real_game=True)`` on the agent's plies."""
     import torch
     ctx = _lib.Context(games, 1, max_plies=max(max_plies, 2), device=dev.index or 0)
@@ -71,7 +72,7 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quie
             if opp_turn.any():
                 ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True, quiescence=quiescence,
                                    node_budget=budget, ordering=ordering, repetition=repetition,
-                                   evaluation=evaluation)
+                                   evaluation=evaluation, selective=selective)
             results = ctx.results()
         return ctx.records()
     finally:
@@ -79,7 +80,7 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quie
 
 
 def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, quiescence=0, budget=None,
-                 ordering=False, repetition=False, evaluation="material"):
+                 ordering=False, repetition=False, evaluation="material", selective=False):
     """(moves, plies, results) of the games with ``sims`` simulations per move against the opponent's replies.  A game
     is searched while it runs and has fewer than ``max_plies`` plies; a move adds two plies (one if it ends the game),
     so a game may end one ply past ``max_plies``."""
@@ -88,12 +89,13 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
     eng = LockstepEngine(model, games, sims, device=dev.index or 0, max_plies=max_plies + 2,
                          reply=MinimaxPlayer(False, search_depth=opponent_depth, quiescence=quiescence,
                                              node_budget=budget, ordering=ordering, repetition=repetition,
-                                             evaluation=evaluation))
+                                             evaluation=evaluation, selective=selective))
     try:
         ctx = eng.ctx
         if not agent_white.all():                            # gamestockfish.py:31-33: the opponent opens as white
             ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True, quiescence=quiescence,
-                               node_budget=budget, ordering=ordering, repetition=repetition, evaluation=evaluation)
+                               node_budget=budget, ordering=ordering, repetition=repetition, evaluation=evaluation,
+                               selective=selective)
         while True:
             _, plies, results = ctx.records(with_moves=False)
             live = (results == _lib.RESULT_NONE) & (plies < max_plies)
@@ -111,7 +113,7 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
 
 def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=None, max_plies=512, model=None,
               sims=0, opponent_quiescence=0, opponent_budget=None, opponent_ordering=False,
-              opponent_repetition=False, opponent_evaluation="material"):
+              opponent_repetition=False, opponent_evaluation="material", opponent_selective=False):
     """Plays ``games`` games against the built-in depth-``opponent_depth`` opponent (with ``opponent_quiescence``
     plies of quiescence search, 0 by default) and returns
     ``dict(played=, won=, drawn=, games=)``: the reference's tallies and the per-game UCI move lists.  ``workers`` is
@@ -123,7 +125,9 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     nodes per move (csrc/opponent.hpp, ITERATIVE DEEPENING); ``opponent_ordering`` (needs ``opponent_budget``): with
     the move ORDERING of that header; ``opponent_repetition`` (needs ``opponent_budget``): with its REPETITION rule, a
     position below the root that occurred before is a draw to the opponent's search; ``opponent_evaluation``
-    ("positional" needs ``opponent_budget``): with its EVALUATION in place of the material evaluation."""
+    ("positional" needs ``opponent_budget``): with its EVALUATION in place of the material evaluation;
+    ``opponent_selective`` (needs ``opponent_ordering``): with its SELECTIVE rules, null-move pruning and late-move
+    reductions."""
     if not 1 <= int(opponent_depth) <= _lib.OPP_MAX_DEPTH:
         raise ValueError("opponent_depth must lie in [1, %d]" % _lib.OPP_MAX_DEPTH)
     quiescence = int(opponent_quiescence)
@@ -140,6 +144,7 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
         raise ValueError("repetition needs a node_budget")
     evaluation = _lib.evaluation_name(opponent_evaluation)
     positional = _lib.opponent_evaluation(evaluation, budget)
+    selective = _lib.opponent_selective(opponent_selective, ordering)
     sims = int(sims)
     if sims < 0:
         raise ValueError("sims must be 0 (the greedy agent) or the number of simulations per move")
@@ -155,10 +160,10 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     agent_white = np.array(colors, dtype=bool)
     if sims > 0:
         moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims,
-                                             quiescence, budget, ordering, repetition, evaluation)
+                                             quiescence, budget, ordering, repetition, evaluation, selective)
     else:
         moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence,
-                                             budget, ordering, repetition, evaluation)
+                                             budget, ordering, repetition, evaluation, selective)
     res = [None if r == _lib.RESULT_NONE else int(r) for r in results]
     out = tally(colors, res)
     out["games"] = [[move_to_uci(m) for m in moves[i, :plies[i]]] for i in range(games)]
@@ -168,11 +173,11 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
             print("Against the built-in depth-%d opponent%s (not Stockfish, no Elo)"
                   % (opponent_depth, ", quiescence %d" % quiescence if quiescence else ""))
         else:
-            print("Against the built-in opponent, depth <= %d within %d nodes per move%s%s%s%s (not Stockfish, no Elo)"
+            print("Against the built-in opponent, depth <= %d within %d nodes per move%s%s%s%s%s (not Stockfish, no Elo)"
                   % (opponent_depth, budget, ", ordered" if ordering else "",
                      ", repetition-aware" if repetition else "",
                      ", quiescence %d" % quiescence if quiescence else "",
-                     ", positional evaluation" if positional else ""))
+                     ", positional evaluation" if positional else "", ", selective" if selective else ""))
         if sims > 0:
             print("agent: MCTS, %d simulations per move" % sims)
         print("Games played: %d" % out["played"])
@@ -199,6 +204,8 @@ def main(argv=None):
                    help="the --nodes search scores a position below the root that occurred before a draw (needs --nodes)")
     p.add_argument("--eval", dest="evaluation", choices=sorted(_lib.OPP_EVALUATIONS), default="material",
                    help="static evaluation of the --nodes search (positional needs --nodes)")
+    p.add_argument("--selective", action="store_true",
+                   help="null-move pruning and late-move reductions in the --ordering search (needs --ordering)")
     p.add_argument("--seed", type=int, default=None, help="seed of the colour draw")
     p.add_argument("--max-plies", type=int, default=512)
     p.add_argument("--sims", type=int, default=0,
@@ -206,7 +213,7 @@ def main(argv=None):
     a = p.parse_args(argv)
     benchmark(a.model_dir, games=a.games, opponent_depth=a.depth, seed=a.seed, max_plies=a.max_plies, log=True,
               sims=a.sims, opponent_quiescence=a.quiescence, opponent_budget=a.nodes, opponent_ordering=a.ordering,
-              opponent_repetition=a.repetition, opponent_evaluation=a.evaluation)
+              opponent_repetition=a.repetition, opponent_evaluation=a.evaluation, opponent_selective=a.selective)
 
 
 if __name__ == "__main__":

@@ -871,13 +871,34 @@ static ReplyEvKernel reply_ev_kernel(bool qs, bool ord, bool rep)
     return t[(rep ? 4 : 0) | (ord ? 2 : 0) | (qs ? 1 : 0)];
 }
 
+// selective = 1: SELECTIVE, the k_opponent_moves_sel / k_reply_opponent_sel kernels of the same shape (ordering is on)
+static MovesEvKernel moves_sel_kernel(bool qs, bool rep, bool pos)
+{
+    static const MovesEvKernel t[8] = {
+        k_opponent_moves_sel<false, false, false>, k_opponent_moves_sel<true, false, false>,
+        k_opponent_moves_sel<false, true, false>,  k_opponent_moves_sel<true, true, false>,
+        k_opponent_moves_sel<false, false, true>,  k_opponent_moves_sel<true, false, true>,
+        k_opponent_moves_sel<false, true, true>,   k_opponent_moves_sel<true, true, true>};
+    return t[(pos ? 4 : 0) | (rep ? 2 : 0) | (qs ? 1 : 0)];
+}
+static ReplyEvKernel reply_sel_kernel(bool qs, bool rep, bool pos)
+{
+    static const ReplyEvKernel t[8] = {
+        k_reply_opponent_sel<false, false, false>, k_reply_opponent_sel<true, false, false>,
+        k_reply_opponent_sel<false, true, false>,  k_reply_opponent_sel<true, true, false>,
+        k_reply_opponent_sel<false, false, true>,  k_reply_opponent_sel<true, false, true>,
+        k_reply_opponent_sel<false, true, true>,   k_reply_opponent_sel<true, true, true>};
+    return t[(pos ? 4 : 0) | (rep ? 2 : 0) | (qs ? 1 : 0)];
+}
+
 static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depths, int quiescence, int push,
                              int64_t node_budget, int ordering, int repetition, int evaluation, uint16_t *moves,
-                             int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
+                             int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done, int selective = 0)
 {
     ENTER(ctx, depths && moves && node_budget >= 1 && (ordering == 0 || ordering == 1) &&
                    (repetition == 0 || repetition == 1) &&
-                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL));
+                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL) &&
+                   (selective == 0 || (selective == 1 && ordering == 1)));
     if (quiescence < 0 || quiescence > CRL_OPP_MAX_QUIESCENCE)
         return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
     const size_t G = ctx->W;
@@ -886,7 +907,11 @@ static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depth
             return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a depth outside 0 .. CRL_OPP_MAX_DEPTH");
     long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
     HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
-    if (evaluation == CRL_OPP_EVAL_POSITIONAL)
+    if (selective)
+        LAUNCH(ctx, moves_sel_kernel(quiescence > 0, repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL), ctx->d,
+               (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes,
+               ctx->t_u8, ctx->t_i32d);
+    else if (evaluation == CRL_OPP_EVAL_POSITIONAL)
         LAUNCH(ctx, moves_ev_kernel(quiescence > 0, ordering != 0, repetition != 0), ctx->d,
                (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes,
                ctx->t_u8, ctx->t_i32d);
@@ -953,6 +978,14 @@ int crl_opponent_moves_ev(crl_ctx *ctx, const int32_t *depths, int quiescence, i
                              evaluation, moves, scores, nodes, flags, depths_done);
 }
 
+int crl_opponent_moves_sel(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
+                           int ordering, int repetition, int evaluation, int selective, uint16_t *moves,
+                           int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
+{
+    return opponent_moves_id(ctx, "crl_opponent_moves_sel", depths, quiescence, push, node_budget, ordering, repetition,
+                             evaluation, moves, scores, nodes, flags, depths_done, selective);
+}
+
 // the static evaluation of every window slot's current position (csrc/opponent.hpp: STATIC EVALUATION / EVALUATION)
 int crl_opponent_evaluate(crl_ctx *ctx, int evaluation, int32_t *scores)
 {
@@ -1012,6 +1045,25 @@ int crl_sim_reply_opponent_ev(crl_ctx *ctx, const int32_t *dev_depths_i32, int q
     LAUNCH(ctx, reply_ev_kernel(quiescence > 0, ordering != 0, repetition != 0), ctx->d, dev_depths_i32, quiescence,
            (long long)node_budget, dev_planes_s2, (unsigned long long *)dev_nodes_u64, dev_cuts_u32,
            (unsigned long long *)dev_depth_sum_u64);
+    return CRL_OK;
+}
+
+// selective = 0 is the _ev call; 1 (it needs ordering) launches the k_reply_opponent_sel kernel of the same shape
+int crl_sim_reply_opponent_sel(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, int repetition, int evaluation, int selective, void *dev_planes_s2,
+                               uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
+{
+    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
+                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
+                   (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1) &&
+                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL) &&
+                   (selective == 0 || (selective == 1 && ordering == 1)));
+    if (!selective)
+        return crl_sim_reply_opponent_ev(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, evaluation,
+                                         dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
+    LAUNCH(ctx, reply_sel_kernel(quiescence > 0, repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL), ctx->d,
+           dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2, (unsigned long long *)dev_nodes_u64,
+           dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
     return CRL_OK;
 }
 

@@ -219,6 +219,59 @@
 //     on the lane number): hoisted, it cost the kernels a wave of occupancy and reserved scratch.  |MG|, |EG| < 2^15 (also for every partial sum: a
 //     subset of the pieces obeys the same bound), so MG * 65536 + EG travels through ONE wave reduction as an int32
 //     and is taken apart exactly afterwards.  No LDS, no scratch.  (tests/evaluation_util.py restates this section.)
+//
+// SELECTIVE (the _sel kernels only: selective = 1, an opt-in on top of ORDERING, so of ITERATIVE DEEPENING and a node
+// budget; it combines freely with QUIESCENCE, REPETITION and EVALUATION, and everything in those sections holds unless
+// this one says otherwise.  Every other launch searches every line to full width, as above).  Null-move pruning and
+// late-move reductions; the three constants (the null move's 3 plies, c >= 3, r >= 3) are fixed.
+//     Remaining depth.  A node carries a remaining depth r: the root of iteration i has r = i, a child has r - 1
+//     unless a rule below says less.  A node with r <= 0 is a horizon node -- the static evaluation at Q = 0, otherwise
+//     a quiescence node whose quiescence ply j counts from the FIRST node on its path with r <= 0 (that node has
+//     j = 0, whatever its r; its children j = 1, ..).  This replaces "k = d" of NODE VALUE 4 and "j = k - d" of
+//     QUIESCENCE; without this section's rules the definitions coincide.  r falls by at least 1 per ply, so a node
+//     that searches moves still lies at ply <= D + Q - 1: the frames, the killers per ply and the REPETITION arrays
+//     keep their sizes.
+//     Null move.  Tried at a node at ply k >= 1, after NODE VALUE 1-3 and 3b, when ALL of these hold: the node has no
+//     result and is no repetition; r >= 2; the side to move is not in check; it owns at least one knight, bishop,
+//     rook or queen; the node's own position was not reached by a null move; |beta| < 29000; the static evaluation
+//     of the node (the call's evaluation kind) is >= beta.  Then the null child is searched before any move.  Its
+//     board is the node's with the side to move exchanged, the en-passant square cleared and the halfmove clock 0, so
+//     neither the fifty-move rule nor REPETITION looks across a null move (a fullmove number would change as after a
+//     move; the device board keeps none).  It is searched with r_child = r - 3 and the window (-beta, -beta + 1); its
+//     move generation is one node, counted and tested against the budget like any other.  If its negated score is
+//     s >= beta the node returns s, or beta when s >= 29000; it searches nothing more and sets no killer.  Otherwise
+//     the node searches its moves as if nothing had happened.
+//     Late-move reduction.  At a node at ply k >= 0, the root included, the move at 0-based position c of the node's
+//     order is FIRST searched with r_child = r - 2 and the window (-alpha - 1, -alpha) when ALL of these hold: r >= 3;
+//     the node is not in check; c >= 3; the move is not tactical (the predicate of ORDER OF THE MOVES in the node's
+//     position; at the root too, whose order stays that of ITERATIVE DEEPENING); it is neither killer A nor B of ply
+//     k; the child's position is not in check (read from the child's board before its moves are generated, as
+//     quiescence does).  If the negated score of the reduced search is > alpha, the move is searched again with
+//     r_child = r - 1 and the window (-beta, -alpha), and that result is the move's score; otherwise the reduced score
+//     is.  The strictly-greater rule, fail-soft, the killer rule and the cut then apply to the move's score as before.
+//     A root move counts as COMPLETELY searched when its last search has finished.
+//     Nothing else changes: the orders, one wave_movegen per turn, the budget tested before every node (a null child,
+//     a reduced search and a re-search included), the cut rules, depth_done and CRL_OPP_CUT.
+// Consequences.  (a) With D <= 2 no node has r >= 3 and none below the root has r >= 2: every output, `nodes`
+// included, equals the search without this section.  (b) The search is no longer minimax over the full tree: move and
+// score may differ from the _ido search even under a budget nothing reaches.  It stays a function of the root, its
+// reversible history and the arguments.  (c) A null-move cut is never a mate score, and no null move is tried against
+// a mate window, so a mate score still counts plies of real moves and null moves alike from the root.  (d) A null child
+// has r - 3, and a node below the root has r <= 4 at the depths this opponent runs (D <= 5), so a null child has r <= 1:
+// "not reached by a null move" never refuses a null move that the depth guard would have let through.  The guard is
+// stated and kept for the rule's sake; at D <= 5 no output depends on it.
+// Structure.  The main loop stays `while (nodes < budget)` with one wave_movegen per turn: the null child, a reduced
+// search and a re-search are changes of state inside turns (which child the descent builds, and what the turn that
+// hands its value up does with it), not loops of their own, so a logic error still ends as a flagged cut.  The
+// entering node carries r (as -j for a quiescence node) beside its window in a scalar register; a frame keeps its r,
+// whether its node is in check and what its current child is (a move, the null child, a reduced search, the
+// re-search) in its spare pad word, written by lane 0 with the frame's other fields, and a node reads "reached by a
+// null move" from its parent's frame: the parent's current child is the null child.
+// sizeof(OppFrame) stays 608 and the LDS of a kernel is that of its non-selective sibling.  A node at k >= 1 has its
+// tactical moves in front (ORDERING), so "not tactical" is the cursor against the stored number; the root asks the
+// predicate (a promotion, or a piece has left the board: the same moves).  ONE call site of the evaluation per
+// kernel: with quiescence ahead of the move generation (the stand-pat and the null move's last guard), without it
+// behind the move generation (the horizon and that guard).  (tests/selective_util.py restates this section.)
 #pragma once
 #include "search.hpp"
 
@@ -229,6 +282,13 @@ constexpr int OPP_MAX_QUIESCENCE = 6;
 constexpr int OPP_INF = 32000;
 constexpr int OPP_MATE = 30000;
 constexpr uint8_t OPP_CUT = 1, OPP_SKIPPED = 2;
+// SELECTIVE: scores from here on are mates (no null move against such a beta; a null-move cut is capped to beta)
+constexpr int OPP_NULL_MATE = 29000;
+// SELECTIVE, the frame's pad word.  Bits 0-1: what the child being searched is -- a move at full depth (the first
+// search of one), the null child, a reduced search, the re-search after a reduced one.  Bit 2: the node is in check.
+// Bits 8-15, signed: the node's remaining depth r where r > 0, otherwise -j, its quiescence ply.
+constexpr uint32_t OPP_CHILD_MOVE = 0, OPP_CHILD_NULL = 1, OPP_CHILD_REDUCED = 2, OPP_CHILD_AGAIN = 3;
+constexpr uint32_t OPP_NODE_IN_CHECK = 4;
 
 struct __attribute__((aligned(16))) OppFrame {
     Board b;
@@ -236,7 +296,7 @@ struct __attribute__((aligned(16))) OppFrame {
     int32_t cur, n, alpha, beta, best;
     int32_t nt;                                // ORDERING: the tactical moves of the node are mv[0 .. nt)
     uint32_t killers;                          // ORDERING: killer A (low half) and B of this ply
-    int32_t pad;
+    int32_t pad;                               // SELECTIVE: the OPP_CHILD_* / OPP_NODE_* bits and the remaining depth
 };
 static_assert(sizeof(OppFrame) == 608, "OppFrame must be 608 bytes");
 
@@ -560,15 +620,40 @@ __device__ inline void opp_move_to_front(u16 *mv, int n, u32 pm, int lane)
 // REP: REPETITION of the header comment, on top of ID; rs and rr are read only then.  Every line marked REP folds away
 // without it.
 // POS: EVALUATION of the header comment in place of STATIC EVALUATION, on top of ID; nothing else reads it.
+// SEL: SELECTIVE of the header comment, on top of ORD.  The entering node carries `e` (its remaining depth r where
+// r > 0, otherwise -j) beside its window; a frame keeps e, whether its node is in check and what its current child is
+// in its pad word, so a node reads there whether a null move led to it.  Every line marked SEL folds away without it.
 struct OppResult { u32 mv; int score; long long nodes; bool done; int depth_done; };
 
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false>
+// SEL: the board after a null move -- the side to move exchanged, no en-passant square, the halfmove clock 0
+__device__ inline Board opp_null_board(const Board &b)
+{
+    Board n = b;
+    n.state = mk_state(st_turn(b.state) ^ 1u, st_castle(b.state), (u32)NO_EP, 0u, 0u);
+    n.pad = 0;
+    return n;
+}
+
+// SEL: the null move's guards that need neither the moves nor the evaluation, for the node `b` at ply k of the frames
+// f with the remaining depth e, and beta.  (Whether the node was reached by a null move stands in its parent's frame.)
+__device__ inline bool opp_null_guards(const Board &b, int k, int e, int beta, const OppFrame *f)
+{
+    const u64 occ = occupied(b);
+    const u64 own = st_turn(b.state) ? b.white & occ : occ & ~b.white;
+    if (!(k >= 1 && e >= 2 && beta > -OPP_NULL_MATE && beta < OPP_NULL_MATE &&
+          (own & (b.bb[KNIGHT] | b.bb[BISHOP] | b.bb[ROOK] | b.bb[QUEEN])) != 0))
+        return false;
+    return ((u32)uni(f[k - 1].pad) & 3u) != OPP_CHILD_NULL;
+}
+
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false>
 __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long long limit, OppFrame *f, int lane,
                                        OppRepLds<QS> *rs = nullptr, OppRepRoot rr = OppRepRoot())
 {
     static_assert(ID || !ORD, "ORDERING requires ITERATIVE DEEPENING");
     static_assert(ID || !REP, "REPETITION requires ITERATIVE DEEPENING");
     static_assert(ID || !POS, "EVALUATION requires ITERATIVE DEEPENING");
+    static_assert(ORD || !SEL, "SELECTIVE requires ORDERING");
     int K = 0;                                             // REP: the positions behind the root that hh holds
     if (ORD) {                                             // both killers of every ply: NO_MOVE
         constexpr int NF = QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1;
@@ -589,15 +674,26 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
     long long nodes = 0;
     int D = ID ? 1 : Dmax, depth_done = 0, held_score = -OPP_INF;      // ID: the iteration; what the last whole one gave
     u32 held_mv = NO_MOVE;
+    int e = D;                                             // SEL: of the entering node, as a, be
     while (nodes < limit) {
         // ---- enter the node `b` at ply k, window (a, be)
         OppFrame *const F = f + k;                         // (read only where the node searches moves: k < D + Q)
-        const bool quiet = QS && k >= D;                   // a quiescence node, j = k - D
+        if (SEL && k >= (QS ? D + Q : D)) e = QS ? -Q : 0; // (r falls by at least 1 per ply: never taken.  The frames end here)
+        const bool quiet = QS && (SEL ? e <= 0 : k >= D);  // a quiescence node, j = k - D; SEL: j = -e
         int stand = 0;
         bool chk = false;
-        if (quiet) { stand = uni(opp_static<POS>(b, lane)); chk = opp_in_check(b); }
+        bool nullc = false;                                // SEL: the null move's guards that need no move generation
+        // (SEL: ONE place evaluates per kernel.  With quiescence, ahead of the move generation: the stand-pat and the
+        // null move's last guard; without, behind it: the horizon and that guard)
+        if (SEL) {
+            if (QS) {
+                nullc = opp_null_guards(b, k, e, be, f);
+                if (quiet || nullc) stand = uni(opp_static<POS>(b, lane));
+            }
+            if (quiet) chk = opp_in_check(b);
+        } else if (quiet) { stand = uni(opp_static<POS>(b, lane)); chk = opp_in_check(b); }
         // a node that searches no move: the horizon; with quiescence 4a, and the stand-pat at or above beta of 4c
-        const bool horizon = QS ? quiet && (k >= D + Q || (!chk && stand >= be)) : k == D;
+        const bool horizon = QS ? quiet && ((SEL ? -e >= Q : k >= D + Q) || (!chk && stand >= be)) : (SEL ? e <= 0 : k == D);
         MoveGenInfo mi = wave_movegen(b, lane, horizon ? nullptr : F->mv);
         nodes++;
         const int n = uni(mi.n);
@@ -631,9 +727,13 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
                 }
             }
         }
+        if (SEL && !QS && res == RESULT_NONE && !(REP && rep_hit)) {
+            nullc = !horizon && opp_null_guards(b, k, e, be, f);   // (in check or not: that guard comes below)
+            if (horizon || nullc) stand = uni(opp_static<POS>(b, lane));
+        }
         if (res != RESULT_NONE) v = res == 0 ? 0 : -(OPP_MATE - k);
         else if (REP && rep_hit) v = 0;
-        else if (horizon) v = QS ? stand : uni(opp_static<POS>(b, lane));
+        else if (horizon) v = QS || SEL ? stand : uni(opp_static<POS>(b, lane));
         else {
             __syncthreads();                               // F->mv visible
             int cnt = n, best0 = -OPP_INF, nt = 0;         // ORD: nt, the node's tactical moves
@@ -653,9 +753,14 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
             }
             if (QS && cnt == 0) v = stand;                 // 4c without a tactical move (cnt = n > 0 everywhere else)
             else {
+                // SEL: the null child is searched before any move (nullc: k >= 1, r >= 2, so no quiescence node)
+                const bool in_chk = SEL && (quiet ? chk : uni((int)mi.in_check) != 0);
+                const bool null_first = SEL && nullc && !in_chk && stand >= be;
                 if (lane == 0) {
                     F->b = b; F->cur = 0; F->n = cnt; F->alpha = a; F->beta = be; F->best = best0;
                     if (ORD) F->nt = nt;
+                    if (SEL) F->pad = (int32_t)((null_first ? OPP_CHILD_NULL : OPP_CHILD_MOVE) |
+                                                (in_chk ? OPP_NODE_IN_CHECK : 0u) | (((u32)e & 0xFFu) << 8));
                     if (REP) { rs->ph[k] = nh; rs->ps[k] = ns; }
                 }
                 __syncthreads();
@@ -675,6 +780,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
                         D++;
                         b = uni_board(f[0].b); a = -OPP_INF; be = OPP_INF;
                         best_mv = NO_MOVE; root_best = -OPP_INF;
+                        e = D;
                         again = true;
                         break;
                     }
@@ -686,6 +792,24 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
             OppFrame &P = f[k];
             const int sc = -v, pn = uni(P.n), pb = uni(P.beta);
             int cur = uni(P.cur), best = uni(P.best), al = uni(P.alpha);
+            u32 pad = 0;
+            if (SEL) {
+                pad = (u32)uni(P.pad);
+                const u32 child = pad & 3u;
+                if (child == OPP_CHILD_NULL && sc >= pb) {     // the null-move cut: frame k returns, no killer
+                    v = sc >= OPP_NULL_MATE ? pb : sc;
+                    continue;
+                }
+                // the null move failed: the moves, from the first; a reduced search above alpha: the move again
+                if (child == OPP_CHILD_NULL || (child == OPP_CHILD_REDUCED && sc > al)) {
+                    __syncthreads();                           // the frame was read
+                    if (lane == 0)
+                        P.pad = (int32_t)((pad & ~3u) | (child == OPP_CHILD_NULL ? OPP_CHILD_MOVE : OPP_CHILD_AGAIN));
+                    __syncthreads();
+                    have_v = false;
+                    continue;
+                }
+            }
             if (sc > best) {
                 best = sc;
                 if (k == 0) { best_mv = (u32)uni((int)P.mv[cur]); root_best = sc; }
@@ -704,6 +828,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
             if (lane == 0) {
                 P.cur = cur; P.best = best; P.alpha = al;
                 if (ORD && set_killer) P.killers = kl;
+                if (SEL) P.pad = (int32_t)(pad & ~3u);     // the next child: a move, not yet searched
             }
             __syncthreads();
             if (cur < pn && al < pb) have_v = false;       // frame k has a next move to search
@@ -713,10 +838,44 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
         if (ID && again) continue;                         // (the budget is tested before the new root like any node)
         // ---- descend: the next move of frame k  (k < D + Q: a frame with moves to search is above the last ply)
         OppFrame &P = f[k];
-        const u32 mv = (u32)uni((int)P.mv[uni(P.cur)]);
-        b = apply_move(uni_board(P.b), mv);
-        a = -uni(P.beta);
-        be = -uni(P.alpha);
+        if (SEL) {
+            const u32 pad = (u32)uni(P.pad), child = pad & 3u;
+            const int pe = (int)(signed char)(pad >> 8), pal = uni(P.alpha), pbe = uni(P.beta);
+            const Board pb = uni_board(P.b);
+            if (child == OPP_CHILD_NULL) {                     // r - 3 and the window (-beta, -beta + 1)
+                b = opp_null_board(pb);
+                a = -pbe; be = -pbe + 1;
+                e = pe > 3 ? pe - 3 : 0;
+            } else {
+                const int cur = uni(P.cur);
+                const u32 mv = (u32)uni((int)P.mv[cur]);
+                const int pieces = popc(occupied(pb));
+                b = apply_move(pb, mv);
+                a = -pbe; be = -pal;
+                e = pe - 1;                                // (a quiescence node: j + 1)
+                // late-move reduction: the guards in the order of their price
+                bool red = child != OPP_CHILD_AGAIN && pe >= 3 && !(pad & OPP_NODE_IN_CHECK) && cur >= 3;
+                if (red) {
+                    const u32 kl = (u32)uni((int)P.killers);   // (the root's pair stays NO_MOVE)
+                    // tactical: below the root the tactical moves stand in front; at the root a legal move is tactical
+                    // exactly if it promotes or a piece has left the board (en passant included), so no parent board
+                    const bool tact = k > 0 ? cur < uni(P.nt) : ((mv >> 12) & 7u) != 0 || popc(occupied(b)) != pieces;
+                    red = !tact && mv != (kl & 0xFFFFu) && mv != (kl >> 16) && !opp_in_check(b);
+                }
+                if (red) {                                     // r - 2 and the window (-alpha - 1, -alpha)
+                    e = pe - 2;
+                    a = -pal - 1; be = -pal;
+                    __syncthreads();                           // the frame was read
+                    if (lane == 0) P.pad = (int32_t)((pad & ~3u) | OPP_CHILD_REDUCED);
+                    __syncthreads();
+                }
+            }
+        } else {
+            const u32 mv = (u32)uni((int)P.mv[uni(P.cur)]);
+            b = apply_move(uni_board(P.b), mv);
+            a = -uni(P.beta);
+            be = -uni(P.alpha);
+        }
         k++;
     }
     OppResult o;
@@ -735,7 +894,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
 
 // One slot of k_opponent_moves / k_opponent_moves_q and, ID, of their _id forms.  Window-relative rows: depths / moves /
 // scores / nodes_out / flags [count] and, ID only, depths_done [count]
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false>
 __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, int push, long long limit, u16 *moves,
                                            int32_t *scores, long long *nodes_out, uint8_t *flags, OppLds<QS> &s,
                                            int32_t *depths_done = nullptr, OppRepLds<QS> *rs = nullptr)
@@ -755,7 +914,7 @@ __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, 
     const Board root = uni_board(d.cur[g]);
     OppRepRoot rr;                                         // REP: the root is the game's current position
     rr.d = &d; rr.g = g; rr.tp = 0; rr.ply = REP ? uni(d.game[g].ply) : 0;
-    const OppResult o = opp_search<QS, ID, ORD, REP, POS>(root, D, Q, limit, s.f, lane, rs, rr);
+    const OppResult o = opp_search<QS, ID, ORD, REP, POS, SEL>(root, D, Q, limit, s.f, lane, rs, rr);
     if (lane == 0) {
         moves[r] = (u16)o.mv;
         scores[r] = o.score;
@@ -871,7 +1030,7 @@ __global__ __launch_bounds__(64) void k_opponent_moves_idor_q(Dev d, const int32
 // search is ITERATIVE DEEPENING under the budget `limit`, and depth_acc [count] sums the completed depths.
 // REP: REPETITION -- S1 stands at tree ply 2 * path_len - 1 of the one path d.path_node holds, so what led to it is the
 // S1 / S2 of the pending node's ancestors and then the game's ring.
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false>
 __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, long long limit, void *planes2,
                                           unsigned long long *nodes_acc, uint32_t *cuts_acc, OppLds<QS> &s,
                                           unsigned long long *depth_acc = nullptr, OppRepLds<QS> *rs = nullptr)
@@ -888,7 +1047,7 @@ __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, l
     const Board s1 = uni_board(d.node[(size_t)g * d.N + c].s1);
     OppRepRoot rr;
     rr.d = &d; rr.g = g; rr.tp = REP ? 2 * uni(d.game[g].path_len) - 1 : 0; rr.ply = REP ? uni(d.game[g].ply) : 0;
-    const OppResult o = opp_search<QS, ID, ORD, REP, POS>(s1, D, Q, limit, s.f, lane, rs, rr);
+    const OppResult o = opp_search<QS, ID, ORD, REP, POS, SEL>(s1, D, Q, limit, s.f, lane, rs, rr);
     if (o.mv == NO_MOVE) { dev_error(d, DERR_STATE); return; }              // S1 is running: it has a legal move
     if (lane == 0) {
         nodes_acc[r] += (unsigned long long)o.nodes;
@@ -1016,6 +1175,38 @@ __global__ __launch_bounds__(64) void k_reply_opponent_ev(Dev d, const int32_t *
     } else
         reply_opponent_row<QS, true, ORD, false, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc, cuts_acc, s,
                                                        depth_acc);
+}
+
+// SELECTIVE: the eight ordered budgeted shapes (quiescence, repetition, evaluation) once more with null-move pruning
+// and late-move reductions, as two kernel templates with the argument lists of the _ev kernels.
+template <bool QS, bool REP, bool POS>
+__global__ __launch_bounds__(64) void k_opponent_moves_sel(Dev d, const int32_t *depths, int Q, int push,
+                                                           long long budget, u16 *moves, int32_t *scores,
+                                                           long long *nodes_out, uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<QS> s;
+    if constexpr (REP) {
+        __shared__ OppRepLds<QS> rs;
+        opponent_moves_slot<QS, true, true, true, POS, true>(d, depths, QS ? Q : 0, push, budget, moves, scores,
+                                                             nodes_out, flags, s, depths_done, &rs);
+    } else
+        opponent_moves_slot<QS, true, true, false, POS, true>(d, depths, QS ? Q : 0, push, budget, moves, scores,
+                                                              nodes_out, flags, s, depths_done);
+}
+
+template <bool QS, bool REP, bool POS>
+__global__ __launch_bounds__(64) void k_reply_opponent_sel(Dev d, const int32_t *depths, int Q, long long budget,
+                                                           void *planes2, unsigned long long *nodes_acc,
+                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<QS> s;
+    if constexpr (REP) {
+        __shared__ OppRepLds<QS> rs;
+        reply_opponent_row<QS, true, true, true, POS, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc,
+                                                            cuts_acc, s, depth_acc, &rs);
+    } else
+        reply_opponent_row<QS, true, true, false, POS, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc,
+                                                             cuts_acc, s, depth_acc);
 }
 
 // the static evaluation of every window slot's current position: scores [count], window-relative

@@ -12,6 +12,8 @@ The player sees a repetition below the root only on request (``repetition=True``
 budget; csrc/opponent.hpp, REPETITION): without it a large share of the games are draws in which the side that is ahead
 shuffles until the fifth occurrence.  ``evaluation="positional"`` / ``--eval positional`` (with a node budget;
 csrc/opponent.hpp, EVALUATION) gives both sides the positional static evaluation instead of material and centrality.
+``selective=True`` / ``--selective`` (with ordering; csrc/opponent.hpp, SELECTIVE) gives both sides null-move pruning
+and late-move reductions.
 """
 import argparse
 import logging
@@ -60,7 +62,8 @@ def side_depths(draws, white_to_move):
 
 
 def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512,
-             quiescence=0, node_budget=None, ordering=False, repetition=False, evaluation="material"):
+             quiescence=0, node_budget=None, ordering=False, repetition=False, evaluation="material",
+             selective=False):
     """Plays ``num_games`` games, saves the finished ones to ``save_path`` (appending to what the file holds, as
     ``DatasetGame.save`` does) and returns the ``DatasetGame`` it saved.  The reference's ``gen_data`` forgets to
     pass ``depth`` and ``random_dep`` on to ``play_game`` (gen_data_stockfish.py:44-49); here both are honoured.
@@ -69,12 +72,14 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
     (None: none): both sides deepen iteratively up to their depths and stop at that many nodes per move; ``ordering``
     (needs a ``node_budget``): with the move ORDERING of csrc/opponent.hpp; ``repetition`` (needs a ``node_budget``):
     with its REPETITION rule, both sides score a position below the root that occurred before a draw; ``evaluation``
-    ("positional" needs a ``node_budget``): both sides search with its EVALUATION."""
+    ("positional" needs a ``node_budget``): both sides search with its EVALUATION; ``selective`` (needs ``ordering``):
+    both sides search with its SELECTIVE rules."""
     if ordering and node_budget is None:
         raise ValueError("ordering needs a node_budget")
     if repetition and node_budget is None:
         raise ValueError("repetition needs a node_budget")
     _lib.opponent_evaluation(evaluation, node_budget)
+    selective = _lib.opponent_selective(selective, ordering)
     if node_budget is not None and int(node_budget) < 1:
         raise ValueError("node_budget must be None or at least 1")
     quiescence = int(quiescence)
@@ -104,7 +109,7 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
                 break
             ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True,
                                quiescence=quiescence, node_budget=node_budget, ordering=bool(ordering),
-                               repetition=bool(repetition), evaluation=evaluation)
+                               repetition=bool(repetition), evaluation=evaluation, selective=selective)
             results = ctx.results()
         moves, plies, results = ctx.records()
     finally:
@@ -134,6 +139,8 @@ def main(argv=None):
                    help="The --nodes search scores a position below the root that occurred before a draw, both sides.")
     p.add_argument("--eval", dest="evaluation", choices=sorted(_lib.OPP_EVALUATIONS), default="material",
                    help="Static evaluation of the --nodes search, both sides (positional needs --nodes).")
+    p.add_argument("--selective", action="store_true", default=False,
+                   help="Null-move pruning and late-move reductions in the --ordering search, both sides.")
     p.add_argument("--random_depth", action="store_true", default=False,
                    help="Use normal distribution of depths with mean --depth.")
     p.add_argument("--debug", action="store_true", default=False, help="Log debug messages on screen. Default false.")
@@ -143,7 +150,8 @@ def main(argv=None):
     logging.basicConfig(level=logging.DEBUG if a.debug else logging.INFO)
     gen_data(a.data_path, num_games=a.games, depth=a.depth, random_dep=a.random_depth,
              opening_plies=a.opening_plies, seed=a.seed, quiescence=a.quiescence,
-             node_budget=a.nodes, ordering=a.ordering, repetition=a.repetition, evaluation=a.evaluation)
+             node_budget=a.nodes, ordering=a.ordering, repetition=a.repetition, evaluation=a.evaluation,
+             selective=a.selective)
 
 
 if __name__ == "__main__":

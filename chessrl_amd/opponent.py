@@ -14,7 +14,9 @@ budget orders the moves below the root by victim and killer moves (opponent.hpp,
 of a budget scores a position below the root that occurred before -- on the search path or in the game's reversible
 history -- a draw (opponent.hpp, REPETITION), so a side that is ahead stops shuffling into the fivefold;
 ``evaluation="positional"`` on top of a budget replaces the static evaluation (material and centrality) by a tapered
-one with pawn structure, mobility, files, king shelter and king attack (opponent.hpp, EVALUATION).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
+one with pawn structure, mobility, files, king shelter and king attack (opponent.hpp, EVALUATION);
+``selective=True`` on top of ``ordering`` adds null-move pruning and late-move reductions, so the budget goes to fewer
+lines, deeper (opponent.hpp, SELECTIVE).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
 these classes are the one-game drop-in surface over it.
 """
 import numpy as np
@@ -42,10 +44,11 @@ class MinimaxPlayer(Player):
     the root that search tries the moves by victim, then the killer moves of the ply (opponent.hpp, ORDERING); with a
     budget it does not reach it plays the same move for fewer nodes.  ``repetition`` (needs a ``node_budget``): a node
     below the root whose position occurred before is worth 0 (opponent.hpp, REPETITION).  ``evaluation``: "material"
-    or "positional" (needs a ``node_budget``; opponent.hpp, EVALUATION)."""
+    or "positional" (needs a ``node_budget``; opponent.hpp, EVALUATION).  ``selective`` (needs ``ordering``): null-move
+    pruning and late-move reductions (opponent.hpp, SELECTIVE); the search is then no longer full-width."""
 
     def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0, node_budget=None, ordering=False,
-                 repetition=False, evaluation="material"):
+                 repetition=False, evaluation="material", selective=False):
         super().__init__(color)
         if not 1 <= int(search_depth) <= MAX_DEPTH:
             raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
@@ -67,6 +70,7 @@ class MinimaxPlayer(Player):
         self.repetition = bool(repetition)
         _lib.opponent_evaluation(evaluation, self.node_budget)
         self.evaluation = evaluation
+        self.selective = _lib.opponent_selective(selective, self.ordering)
         self.last = None                      # (score, nodes, flag) of the last search
         self.last_depth = None                # with a budget: the depth that search completed
 
@@ -76,7 +80,7 @@ class MinimaxPlayer(Player):
         ctx = arena().one(game._slot)
         out = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False, node_limit=self.node_limit,
                                  quiescence=self.quiescence, node_budget=self.node_budget, ordering=self.ordering,
-                                 repetition=self.repetition, evaluation=self.evaluation)
+                                 repetition=self.repetition, evaluation=self.evaluation, selective=self.selective)
         moves, scores, nodes, flags = out[:4]
         self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
         self.last_depth = int(out[4][0]) if self.node_budget is not None else None
@@ -92,11 +96,12 @@ class GameOpponent(Game):
     """Mirror of ``GameStockfish``: a game against the built-in opponent.  ``opponent``: a ``MinimaxPlayer``, or
     None for one of depth ``opponent_depth``, ``opponent_quiescence``, ``opponent_budget`` (the player's
     ``node_budget``), ``opponent_ordering`` (its ``ordering``), ``opponent_repetition`` (its ``repetition``) and
-    ``opponent_evaluation`` (its ``evaluation``) with the colour opposite to ``player_color``."""
+    ``opponent_evaluation`` (its ``evaluation``) and ``opponent_selective`` (its ``selective``) with the colour
+    opposite to ``player_color``."""
 
     def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2,
                  opponent_quiescence=0, opponent_budget=None, opponent_ordering=False, opponent_repetition=False,
-                 opponent_evaluation="material"):
+                 opponent_evaluation="material", opponent_selective=False):
         if opponent is not None and not isinstance(opponent, MinimaxPlayer):
             raise ValueError("opponent must be a MinimaxPlayer or None")
         self.opponent = None                  # (a board's move stack is replayed by plain Game.move)
@@ -105,7 +110,7 @@ class GameOpponent(Game):
             opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth,
                                      quiescence=opponent_quiescence, node_budget=opponent_budget,
                                      ordering=opponent_ordering, repetition=opponent_repetition,
-                                     evaluation=opponent_evaluation)
+                                     evaluation=opponent_evaluation, selective=opponent_selective)
         self.opponent = opponent
 
     def move(self, movement):

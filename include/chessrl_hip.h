@@ -70,8 +70,8 @@ typedef struct crl_ctx crl_ctx;
  * signature hands the GPU garbage pointers).  crl_source_hash(): sha256 over the sources (csrc/ + this
  * header + compiler flags) the library was built from, as chessrl_amd/_lib.py computes it; the string
  * is also findable in the file itself behind the marker "CRL_SRC_HASH=".  No reference counterpart.
- * (The _ord, _rep and _ev entries of the built-in opponent and crl_opponent_evaluate are additions that change no
- * existing signature or meaning: still 9.) */
+ * (The _ord, _rep, _ev and _sel entries of the built-in opponent and crl_opponent_evaluate are additions that change
+ * no existing signature or meaning: still 9.) */
 #define CRL_ABI_VERSION 9
 int  crl_abi_version(void);
 const char *crl_source_hash(void);
@@ -396,6 +396,22 @@ int  crl_opponent_moves_ev(crl_ctx *ctx, const int32_t *depths /*G*/, int quiesc
 int  crl_sim_reply_opponent_ev(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
                                int ordering, int repetition, int evaluation, void *dev_planes_s2,
                                uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64);
+/* The two _ev calls with opt-in SELECTIVE search (csrc/opponent.hpp states it): null-move pruning and late-move
+ * reductions on top of ORDERING.  selective = 0 is the _ev call, array for array, from the same kernels.
+ * selective = 1 needs ordering = 1 and launches the k_opponent_moves_sel / k_reply_opponent_sel kernel of the same
+ * shape (quiescence, repetition, evaluation): a node with remaining depth >= 2 whose static evaluation reaches beta
+ * first tries a null move searched 3 plies shallower, and a quiet late move (position >= 3, remaining depth >= 3) is
+ * first searched one ply shallower on a null window and again at full depth only if it beats alpha.  The search is
+ * no longer minimax over the full tree; with a maximum depth <= 2 every output equals the _ev call's.
+ * CRL_ERR_ARG: a selective other than 0 or 1, selective = 1 with ordering = 0, and what the _ev calls refuse.  No
+ * state changes on an error. */
+int  crl_opponent_moves_sel(crl_ctx *ctx, const int32_t *depths /*G*/, int quiescence, int push, int64_t node_budget,
+                            int ordering, int repetition, int evaluation, int selective, uint16_t *moves /*G*/,
+                            int32_t *scores /*G*/, int64_t *nodes /*G*/, uint8_t *flags /*G*/,
+                            int32_t *depths_done /*G*/);
+int  crl_sim_reply_opponent_sel(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                                int ordering, int repetition, int evaluation, int selective, void *dev_planes_s2,
+                                uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64);
 /* The static evaluation of every window slot's current position, from the side to move, whatever the game's result:
  * scores[g] (host int32, synchronous, window-relative).  evaluation as above: 0 is STATIC EVALUATION of
  * csrc/opponent.hpp, 1 its EVALUATION.  No search, no state change.

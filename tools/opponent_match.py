@@ -2,14 +2,16 @@
 """Two settings of the built-in opponent (csrc/opponent.hpp) play each other over paired openings.
 
     python tools/opponent_match.py [--pairs 512] [--depth 3] [--budget 600] [--quiescence 2] [--ordering] [--repetition]
-                                   [--eval-a positional] [--eval-b material] [--opening-plies 6] [--max-plies 300]
-                                   [--seed 0] [--out profiles/opponent_match.json]
+                                   [--eval-a positional] [--eval-b material] [--selective] [--opening-plies 6]
+                                   [--max-plies 300] [--seed 0] [--out profiles/opponent_match.json]
 
 Games 2i and 2i + 1 share --opening-plies random plies (the in-slot playout call; the words come from
 ``chessrl_amd.gen_data.opening_words``, the source ``gen_data`` draws them from); setting A is white in game 2i and
 black in game 2i + 1.  All games advance in lockstep: per ply two ``opponent_moves(push=True)`` launches under
 complementary depth masks -- depth 0 leaves a slot alone -- so each side is searched with its own settings.  --depth,
---budget, --quiescence, --ordering and --repetition hold for both sides; the sides differ in their evaluation.
+--budget, --quiescence, --ordering and --repetition hold for both sides; the sides differ in their evaluation and,
+with --selective (it needs --ordering), in that A searches with the SELECTIVE rules of opponent.hpp and B without: give
+both sides the same evaluation to measure the rules alone.
 
 Printed and written: wins, draws and losses of A, its score (a game still running at --max-plies counts as a draw)
 with a 95 % interval over the pair scores, the games still running and their share, and how every game ended (the
@@ -33,12 +35,12 @@ def side_kw(settings):
     """The keywords of ``Context.opponent_moves`` of one side's settings (without its depth)."""
     return dict(quiescence=settings.get("quiescence", 0), node_budget=settings["node_budget"],
                 ordering=bool(settings.get("ordering", False)), repetition=bool(settings.get("repetition", False)),
-                evaluation=settings.get("evaluation", "material"))
+                evaluation=settings.get("evaluation", "material"), selective=bool(settings.get("selective", False)))
 
 
 def play(pairs, a, b, opening_plies=6, max_plies=300, seed=0):
     """Plays 2 * ``pairs`` games between the settings ``a`` and ``b`` (dicts: depth, node_budget, quiescence, ordering,
-    repetition, evaluation) and returns (a_white bool [G], moves u16 [G][plies], plies, results): A is white in the
+    repetition, evaluation, selective) and returns (a_white bool [G], moves u16 [G][plies], plies, results): A is white in the
     even games."""
     import numpy as np
     from chessrl_amd import _lib
@@ -142,14 +144,17 @@ def main(argv=None):
     ap.add_argument("--repetition", action="store_true")
     ap.add_argument("--eval-a", default="positional", choices=("material", "positional"))
     ap.add_argument("--eval-b", default="material", choices=("material", "positional"))
+    ap.add_argument("--selective", action="store_true", help="A searches with the selective rules, B without")
     ap.add_argument("--opening-plies", type=int, default=6)
     ap.add_argument("--max-plies", type=int, default=300)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "opponent_match.json"))
     args = ap.parse_args(argv)
+    if args.selective and not args.ordering:
+        ap.error("--selective needs --ordering")
     common = dict(depth=args.depth, node_budget=args.budget, quiescence=args.quiescence, ordering=args.ordering,
                   repetition=args.repetition)
-    a, b = dict(common, evaluation=args.eval_a), dict(common, evaluation=args.eval_b)
+    a, b = dict(common, evaluation=args.eval_a, selective=args.selective), dict(common, evaluation=args.eval_b)
     out, _ = summary(*play(args.pairs, a, b, args.opening_plies, args.max_plies, args.seed))
     out.update(a=a, b=b, opening_plies=args.opening_plies, max_plies=args.max_plies, seed=args.seed,
                note="a score over paired openings at equal nodes per move, no Elo claim")

@@ -7,6 +7,7 @@
     python tools/opponent_probe.py --ordering --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2
     python tools/opponent_probe.py --repetition --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2 --opening-plies 40
     python tools/opponent_probe.py --eval positional --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2
+    python tools/opponent_probe.py --selective --ordering --budget 600,1500,6000 --max-depth 5 --quiescence 0,2
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words), so the slots hold
 different positions.  Per depth, in depth order: one warm-up launch, then three timed ones (host wall time around the
@@ -26,7 +27,12 @@ them; at 40 most do.  With --ordering as well, both rows of a budget are ordered
 run with the material evaluation and with the positional EVALUATION of opponent.hpp in the same process, the launches
 alternating; --ordering and --repetition then hold for both rows, the positional rows are keyed "... positional" and
 carry the time per node and per launch as ratios to the material row of the same run and the share of slots that play
-another move; the output goes to profiles/opponent_probe_eval.json.  No threshold: this is a measurement.
+another move; the output goes to profiles/opponent_probe_eval.json.  --selective (with --ordering): every budget is
+run with the SELECTIVE rules of opponent.hpp (null-move pruning, late-move reductions) off and on in the same process,
+the launches alternating; --repetition and --eval then hold for both rows, the selective rows are keyed "... selective"
+and carry the time per node and per launch as ratios to the full-width row of the same run, the mean completed depth of
+both and the share of slots that play another move; the output goes to profiles/opponent_probe_sel.json.  No
+threshold: this is a measurement.
 """
 import argparse
 import json
@@ -54,11 +60,16 @@ def main():
                     help="run every --budget with the repetition rule off and on, alternating")
     ap.add_argument("--eval", dest="evaluation", default="material", choices=("material", "positional"),
                     help="positional: run every --budget with the material and the positional evaluation, alternating")
+    ap.add_argument("--selective", action="store_true",
+                    help="run every --budget with the selective rules off and on, alternating (needs --ordering)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     budgets = [int(b) for b in args.budget.split(",") if b]
+    if args.selective and not args.ordering:
+        ap.error("--selective needs --ordering")
     if args.out is None:
         name = ("opponent_probe.json" if not budgets else
+                "opponent_probe_sel.json" if args.selective else
                 "opponent_probe_eval.json" if args.evaluation == "positional" else
                 "opponent_probe_rep.json" if args.repetition else
                 "opponent_probe_ord.json" if args.ordering else "opponent_probe_id.json")
@@ -83,7 +94,12 @@ def main():
             kw["node_budget"] = budget
         # the launches of a case alternate between its variants: ordering off and, with --ordering, on
         variants = [(key, kw)]
-        if budget is not None and args.evaluation == "positional":
+        if budget is not None and args.selective:
+            base = (key + " ordered" + (" repeating-aware" if args.repetition else "") +
+                    (" positional" if args.evaluation == "positional" else ""),
+                    dict(kw, ordering=True, repetition=args.repetition, evaluation=args.evaluation))
+            variants = [base, (base[0] + " selective", dict(base[1], selective=True))]
+        elif budget is not None and args.evaluation == "positional":
             base = (key + (" ordered" if args.ordering else "") + (" repeating-aware" if args.repetition else ""),
                     dict(kw, ordering=args.ordering, repetition=args.repetition))
             variants = [base, (base[0] + " positional", dict(base[1], evaluation="positional"))]
@@ -114,7 +130,14 @@ def main():
             if budget is not None:
                 out["depths"][k]["depth_done_histogram"] = np.bincount(last[k][4][searched], minlength=depth + 1).tolist()
             print(k, json.dumps(out["depths"][k]), flush=True)
-        if len(variants) == 2 and args.evaluation == "positional":     # against the material row of this run
+        if len(variants) == 2 and args.selective:                      # against the full-width row of this run
+            off, on = out["depths"][variants[0][0]], out["depths"][variants[1][0]]
+            on["time_per_node_ratio_to_full_width"] = off["nodes_per_s"] / on["nodes_per_s"]
+            on["ms_per_launch_ratio_to_full_width"] = on["ms_per_launch"] / off["ms_per_launch"]
+            on["share_of_slots_with_another_move"] = float((last[variants[0][0]][0] != last[variants[1][0]][0]).mean())
+            for k, _ in variants:
+                out["depths"][k]["depth_done_mean"] = float(last[k][4][last[k][3] != _lib.OPP_SKIPPED].mean())
+        elif len(variants) == 2 and args.evaluation == "positional":   # against the material row of this run
             off, on = out["depths"][variants[0][0]], out["depths"][variants[1][0]]
             on["time_per_node_ratio_to_material"] = off["nodes_per_s"] / on["nodes_per_s"]
             on["ms_per_launch_ratio_to_material"] = on["ms_per_launch"] / off["ms_per_launch"]
