@@ -71,6 +71,7 @@ SYMBOLS = [
     "crl_opponent_moves_rep", "crl_sim_reply_opponent_rep",
     "crl_opponent_moves_ev", "crl_sim_reply_opponent_ev", "crl_opponent_evaluate",
     "crl_opponent_moves_sel", "crl_sim_reply_opponent_sel",
+    "crl_opponent_moves_exc", "crl_sim_reply_opponent_exc", "crl_opponent_exchange",
     "crl_wave_config", "crl_wave_begin", "crl_wave_select", "crl_wave_reply", "crl_wave_backup", "crl_wave_remaining",
     "crl_wave_stats",
     "crl_advance_one",
@@ -95,6 +96,20 @@ def opponent_selective(selective, ordering):
     if selective and not ordering:
         raise ValueError("selective needs ordering")
     return bool(selective)
+
+
+def opponent_exchange(exchange, ordering, node_budget, quiescence):
+    """Whether the quiescence search prunes by delta and exchange (csrc/opponent.hpp, EXCHANGE); a ValueError for one
+    without ordering, without a node budget or without quiescence plies."""
+    if not exchange:
+        return False
+    if not ordering:
+        raise ValueError("exchange needs ordering")
+    if node_budget is None:
+        raise ValueError("ordering needs a node_budget")
+    if int(quiescence) < 1:
+        raise ValueError("exchange needs quiescence >= 1")
+    return True
 
 
 def opponent_evaluation(evaluation, node_budget):
@@ -287,6 +302,9 @@ def lib():
     L.crl_sim_reply_opponent_ev.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, i32, vp, vp, vp, vp]
     L.crl_opponent_moves_sel.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.crl_sim_reply_opponent_sel.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.crl_opponent_moves_exc.argtypes = [vp, vp, i32, i32, ctypes.c_int64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.crl_sim_reply_opponent_exc.argtypes = [vp, vp, i32, ctypes.c_int64, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.crl_opponent_exchange.argtypes = [vp, vp, vp]
     L.crl_opponent_evaluate.argtypes = [vp, i32, vp]
     L.crl_stamp_clock_khz.argtypes = [i32]
     L.crl_wave_config.argtypes = [vp, i32]
@@ -617,7 +635,7 @@ class Context(object):
 
     def sim_reply_opponent(self, dev_depths, node_limit, dev_planes_s2, dev_nodes, dev_cuts, quiescence=0,
                            node_budget=None, dev_depth_sum=None, ordering=False, repetition=False,
-                           evaluation="material", selective=False):
+                           evaluation="material", selective=False, exchange=False):
         """``sim_reply`` with the built-in opponent's move as the reply: device pointers to int32 [count] depths, the
         planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies; ``quiescence`` plies (0 ..
         OPP_MAX_QUIESCENCE) past the depth.  ``node_budget`` (not None): iterative deepening up to the depths under
@@ -628,7 +646,17 @@ class Context(object):
         False calls the entry it called.  ``evaluation`` ("positional" needs a ``node_budget``): the budgeted search with
         EVALUATION in place of the material evaluation, ``crl_sim_reply_opponent_ev``; "material" calls the entry it
         called.  ``selective`` (needs ``ordering``): the ordered search with SELECTIVE (null-move pruning and late-move
-        reductions), ``crl_sim_reply_opponent_sel``; False calls the entry it called."""
+        reductions), ``crl_sim_reply_opponent_sel``; False calls the entry it called.  ``exchange`` (needs ``ordering``
+        and ``quiescence`` >= 1): that search with EXCHANGE (delta and exchange pruning at the stand-pat nodes),
+        ``crl_sim_reply_opponent_exc``; False calls the entry it called."""
+        if opponent_exchange(exchange, ordering, node_budget, quiescence):
+            self._ck(self._L.crl_sim_reply_opponent_exc(
+                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)), 1,
+                1 if repetition else 0, 1 if opponent_evaluation(evaluation, node_budget) else 0,
+                1 if opponent_selective(selective, ordering) else 0, 1,
+                ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts),
+                ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_exc")
+            return
         if opponent_selective(selective, ordering):
             if node_budget is None:
                 raise ValueError("ordering needs a node_budget")
@@ -801,7 +829,7 @@ class Context(object):
 
     # ---- the built-in opponent (csrc/opponent.hpp; stockfish.py:23-31, gamestockfish.py:27-41) ------
     def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT, quiescence=0, node_budget=None,
-                       ordering=False, repetition=False, evaluation="material", selective=False):
+                       ordering=False, repetition=False, evaluation="material", selective=False, exchange=False):
         """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it,
         with ``quiescence`` plies (0 .. OPP_MAX_QUIESCENCE, one value per call) of quiescence search past the depth.
         Returns (moves u16, scores i32, nodes i64, flags u8); with ``push`` the moves are played.  ``node_budget`` (not
@@ -815,8 +843,12 @@ class Context(object):
         mobility, files, king safety, tapered) in place of the material evaluation, through ``crl_opponent_moves_ev``;
         "material" calls the entry it called.  ``selective`` (needs ``ordering``): the ordered search with SELECTIVE
         (csrc/opponent.hpp: null-move pruning and late-move reductions), through ``crl_opponent_moves_sel``; False
-        calls the entry it called."""
+        calls the entry it called.  ``exchange`` (needs ``ordering`` and ``quiescence`` >= 1): that search with EXCHANGE
+        (csrc/opponent.hpp: at a quiescence node that stands pat, captures that cannot come near alpha or lose
+        material on their square are not searched), through ``crl_opponent_moves_exc``; False calls the entry it
+        called."""
         selective = opponent_selective(selective, ordering)
+        exchange = opponent_exchange(exchange, ordering, node_budget, quiescence)
         if ordering and node_budget is None:
             raise ValueError("ordering needs a node_budget")
         if repetition and node_budget is None:
@@ -830,6 +862,14 @@ class Context(object):
         flags = np.zeros(self.G, np.uint8)
         if node_budget is not None:
             done = np.zeros(self.G, np.int32)
+            if exchange:
+                self._ck(self._L.crl_opponent_moves_exc(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
+                                                        min(int(node_budget), int(node_limit)), 1,
+                                                        1 if repetition else 0, 1 if positional else 0,
+                                                        1 if selective else 0, 1, _ptr(moves), _ptr(scores),
+                                                        _ptr(nodes), _ptr(flags), _ptr(done)),
+                         "crl_opponent_moves_exc")
+                return moves, scores, nodes, flags, done
             if selective:
                 self._ck(self._L.crl_opponent_moves_sel(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
                                                         min(int(node_budget), int(node_limit)), 1,
@@ -871,6 +911,16 @@ class Context(object):
         scores = np.zeros(self.G, np.int32)
         self._ck(self._L.crl_opponent_evaluate(self._h, kind, _ptr(scores)), "crl_opponent_evaluate")
         return scores
+
+    def opponent_exchange(self):
+        """The exchange test of csrc/opponent.hpp, EXCHANGE, alone and without a search, for every legal move of every
+        window slot's current position: (bits uint8 [G][MAX_MOVES], counts int32 [G]).  ``bits[g, i]`` belongs to move
+        i of ``legal_moves()``: bit 0 = the move is tactical, bit 1 = the test keeps it (static exchange value >= 0;
+        always set for a move that is not tactical); entries from ``counts[g]`` on are 0."""
+        bits = np.zeros((self.G, MAX_MOVES), np.uint8)
+        counts = np.zeros(self.G, np.int32)
+        self._ck(self._L.crl_opponent_exchange(self._h, _ptr(bits), _ptr(counts)), "crl_opponent_exchange")
+        return bits, counts
 
     # ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------
     def wave_config(self, threads):

@@ -19,6 +19,8 @@ budget; csrc/opponent.hpp, REPETITION).  Without it, games it is winning may sti
 Its static evaluation is material and centrality unless ``opponent_evaluation="positional"`` / ``--eval positional``
 (needs a budget; csrc/opponent.hpp, EVALUATION) asks for the positional one.  ``opponent_selective=True`` /
 ``--selective`` (needs ordering; csrc/opponent.hpp, SELECTIVE) adds null-move pruning and late-move reductions.
+``opponent_exchange=True`` / ``--exchange`` (needs ordering and quiescence; csrc/opponent.hpp, EXCHANGE) adds delta and
+exchange pruning at the quiescence nodes that stand pat.
 """
 import argparse
 import os
@@ -50,7 +52,7 @@ def _load_model(model_dir):
 
 
 def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence=0, budget=None,
-                 ordering=False, repetition=False, evaluation="material", selective=False):
+                 ordering=False, repetition=False, evaluation="material", selective=False, exchange=False):
     """(moves, plies, results) of the games with ``Agent.best_move(real_game=True)`` on the agent's plies."""
     import torch
     ctx = _lib.Context(games, 1, max_plies=max(max_plies, 2), device=dev.index or 0)
@@ -72,7 +74,7 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quie
             if opp_turn.any():
                 ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True, quiescence=quiescence,
                                    node_budget=budget, ordering=ordering, repetition=repetition,
-                                   evaluation=evaluation, selective=selective)
+                                   evaluation=evaluation, selective=selective, exchange=exchange)
             results = ctx.results()
         return ctx.records()
     finally:
@@ -80,7 +82,7 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quie
 
 
 def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, quiescence=0, budget=None,
-                 ordering=False, repetition=False, evaluation="material", selective=False):
+                 ordering=False, repetition=False, evaluation="material", selective=False, exchange=False):
     """(moves, plies, results) of the games with ``sims`` simulations per move against the opponent's replies.  A game
     is searched while it runs and has fewer than ``max_plies`` plies; a move adds two plies (one if it ends the game),
     so a game may end one ply past ``max_plies``."""
@@ -89,13 +91,13 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
     eng = LockstepEngine(model, games, sims, device=dev.index or 0, max_plies=max_plies + 2,
                          reply=MinimaxPlayer(False, search_depth=opponent_depth, quiescence=quiescence,
                                              node_budget=budget, ordering=ordering, repetition=repetition,
-                                             evaluation=evaluation, selective=selective))
+                                             evaluation=evaluation, selective=selective, exchange=exchange))
     try:
         ctx = eng.ctx
         if not agent_white.all():                            # gamestockfish.py:31-33: the opponent opens as white
             ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True, quiescence=quiescence,
                                node_budget=budget, ordering=ordering, repetition=repetition, evaluation=evaluation,
-                               selective=selective)
+                               selective=selective, exchange=exchange)
         while True:
             _, plies, results = ctx.records(with_moves=False)
             live = (results == _lib.RESULT_NONE) & (plies < max_plies)
@@ -113,7 +115,8 @@ def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims
 
 def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=None, max_plies=512, model=None,
               sims=0, opponent_quiescence=0, opponent_budget=None, opponent_ordering=False,
-              opponent_repetition=False, opponent_evaluation="material", opponent_selective=False):
+              opponent_repetition=False, opponent_evaluation="material", opponent_selective=False,
+              opponent_exchange=False):
     """Plays ``games`` games against the built-in depth-``opponent_depth`` opponent (with ``opponent_quiescence``
     plies of quiescence search, 0 by default) and returns
     ``dict(played=, won=, drawn=, games=)``: the reference's tallies and the per-game UCI move lists.  ``workers`` is
@@ -127,7 +130,8 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     position below the root that occurred before is a draw to the opponent's search; ``opponent_evaluation``
     ("positional" needs ``opponent_budget``): with its EVALUATION in place of the material evaluation;
     ``opponent_selective`` (needs ``opponent_ordering``): with its SELECTIVE rules, null-move pruning and late-move
-    reductions."""
+    reductions; ``opponent_exchange`` (needs ``opponent_ordering`` and ``opponent_quiescence`` >= 1): with its EXCHANGE
+    rules, delta and exchange pruning in quiescence."""
     if not 1 <= int(opponent_depth) <= _lib.OPP_MAX_DEPTH:
         raise ValueError("opponent_depth must lie in [1, %d]" % _lib.OPP_MAX_DEPTH)
     quiescence = int(opponent_quiescence)
@@ -145,6 +149,7 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     evaluation = _lib.evaluation_name(opponent_evaluation)
     positional = _lib.opponent_evaluation(evaluation, budget)
     selective = _lib.opponent_selective(opponent_selective, ordering)
+    exchange = _lib.opponent_exchange(opponent_exchange, ordering, budget, quiescence)
     sims = int(sims)
     if sims < 0:
         raise ValueError("sims must be 0 (the greedy agent) or the number of simulations per move")
@@ -160,10 +165,11 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     agent_white = np.array(colors, dtype=bool)
     if sims > 0:
         moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims,
-                                             quiescence, budget, ordering, repetition, evaluation, selective)
+                                             quiescence, budget, ordering, repetition, evaluation, selective,
+                                             exchange)
     else:
         moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence,
-                                             budget, ordering, repetition, evaluation, selective)
+                                             budget, ordering, repetition, evaluation, selective, exchange)
     res = [None if r == _lib.RESULT_NONE else int(r) for r in results]
     out = tally(colors, res)
     out["games"] = [[move_to_uci(m) for m in moves[i, :plies[i]]] for i in range(games)]
@@ -173,11 +179,12 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
             print("Against the built-in depth-%d opponent%s (not Stockfish, no Elo)"
                   % (opponent_depth, ", quiescence %d" % quiescence if quiescence else ""))
         else:
-            print("Against the built-in opponent, depth <= %d within %d nodes per move%s%s%s%s%s (not Stockfish, no Elo)"
+            print("Against the built-in opponent, depth <= %d within %d nodes per move%s%s%s%s%s%s (not Stockfish, no Elo)"
                   % (opponent_depth, budget, ", ordered" if ordering else "",
                      ", repetition-aware" if repetition else "",
                      ", quiescence %d" % quiescence if quiescence else "",
-                     ", positional evaluation" if positional else "", ", selective" if selective else ""))
+                     ", positional evaluation" if positional else "", ", selective" if selective else "",
+                     ", exchange-pruned" if exchange else ""))
         if sims > 0:
             print("agent: MCTS, %d simulations per move" % sims)
         print("Games played: %d" % out["played"])
@@ -206,6 +213,9 @@ def main(argv=None):
                    help="static evaluation of the --nodes search (positional needs --nodes)")
     p.add_argument("--selective", action="store_true",
                    help="null-move pruning and late-move reductions in the --ordering search (needs --ordering)")
+    p.add_argument("--exchange", action="store_true",
+                   help="delta and exchange pruning in the quiescence of the --ordering search (needs --ordering and "
+                        "--quiescence)")
     p.add_argument("--seed", type=int, default=None, help="seed of the colour draw")
     p.add_argument("--max-plies", type=int, default=512)
     p.add_argument("--sims", type=int, default=0,
@@ -213,7 +223,8 @@ def main(argv=None):
     a = p.parse_args(argv)
     benchmark(a.model_dir, games=a.games, opponent_depth=a.depth, seed=a.seed, max_plies=a.max_plies, log=True,
               sims=a.sims, opponent_quiescence=a.quiescence, opponent_budget=a.nodes, opponent_ordering=a.ordering,
-              opponent_repetition=a.repetition, opponent_evaluation=a.evaluation, opponent_selective=a.selective)
+              opponent_repetition=a.repetition, opponent_evaluation=a.evaluation, opponent_selective=a.selective,
+              opponent_exchange=a.exchange)
 
 
 if __name__ == "__main__":

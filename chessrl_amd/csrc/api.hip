@@ -891,14 +891,37 @@ static ReplyEvKernel reply_sel_kernel(bool qs, bool rep, bool pos)
     return t[(pos ? 4 : 0) | (rep ? 2 : 0) | (qs ? 1 : 0)];
 }
 
+// exchange = 1: EXCHANGE, the k_opponent_moves_exc / k_reply_opponent_exc kernels of the same shape (ordering is on and
+// quiescence >= 1)
+static MovesEvKernel moves_exc_kernel(bool rep, bool pos, bool sel)
+{
+    static const MovesEvKernel t[8] = {
+        k_opponent_moves_exc<false, false, false>, k_opponent_moves_exc<true, false, false>,
+        k_opponent_moves_exc<false, true, false>,  k_opponent_moves_exc<true, true, false>,
+        k_opponent_moves_exc<false, false, true>,  k_opponent_moves_exc<true, false, true>,
+        k_opponent_moves_exc<false, true, true>,   k_opponent_moves_exc<true, true, true>};
+    return t[(sel ? 4 : 0) | (pos ? 2 : 0) | (rep ? 1 : 0)];
+}
+static ReplyEvKernel reply_exc_kernel(bool rep, bool pos, bool sel)
+{
+    static const ReplyEvKernel t[8] = {
+        k_reply_opponent_exc<false, false, false>, k_reply_opponent_exc<true, false, false>,
+        k_reply_opponent_exc<false, true, false>,  k_reply_opponent_exc<true, true, false>,
+        k_reply_opponent_exc<false, false, true>,  k_reply_opponent_exc<true, false, true>,
+        k_reply_opponent_exc<false, true, true>,   k_reply_opponent_exc<true, true, true>};
+    return t[(sel ? 4 : 0) | (pos ? 2 : 0) | (rep ? 1 : 0)];
+}
+
 static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depths, int quiescence, int push,
                              int64_t node_budget, int ordering, int repetition, int evaluation, uint16_t *moves,
-                             int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done, int selective = 0)
+                             int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done, int selective = 0,
+                             int exchange = 0)
 {
     ENTER(ctx, depths && moves && node_budget >= 1 && (ordering == 0 || ordering == 1) &&
                    (repetition == 0 || repetition == 1) &&
                    (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL) &&
-                   (selective == 0 || (selective == 1 && ordering == 1)));
+                   (selective == 0 || (selective == 1 && ordering == 1)) &&
+                   (exchange == 0 || (exchange == 1 && ordering == 1 && quiescence >= 1)));
     if (quiescence < 0 || quiescence > CRL_OPP_MAX_QUIESCENCE)
         return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
     const size_t G = ctx->W;
@@ -907,7 +930,11 @@ static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depth
             return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a depth outside 0 .. CRL_OPP_MAX_DEPTH");
     long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
     HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
-    if (selective)
+    if (exchange)
+        LAUNCH(ctx, moves_exc_kernel(repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL, selective != 0), ctx->d,
+               (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes,
+               ctx->t_u8, ctx->t_i32d);
+    else if (selective)
         LAUNCH(ctx, moves_sel_kernel(quiescence > 0, repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL), ctx->d,
                (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes,
                ctx->t_u8, ctx->t_i32d);
@@ -986,6 +1013,26 @@ int crl_opponent_moves_sel(crl_ctx *ctx, const int32_t *depths, int quiescence, 
                              evaluation, moves, scores, nodes, flags, depths_done, selective);
 }
 
+int crl_opponent_moves_exc(crl_ctx *ctx, const int32_t *depths, int quiescence, int push, int64_t node_budget,
+                           int ordering, int repetition, int evaluation, int selective, int exchange, uint16_t *moves,
+                           int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done)
+{
+    return opponent_moves_id(ctx, "crl_opponent_moves_exc", depths, quiescence, push, node_budget, ordering, repetition,
+                             evaluation, moves, scores, nodes, flags, depths_done, selective, exchange);
+}
+
+// the exchange test of every legal move of every window slot's current position (csrc/opponent.hpp: EXCHANGE, test 2)
+int crl_opponent_exchange(crl_ctx *ctx, uint8_t *bits, int32_t *counts)
+{
+    ENTER(ctx, bits && counts);
+    const size_t G = ctx->W;
+    uint8_t *dbits = (uint8_t *)ctx->t_moves2;            // [G][MAX_MOVES] bytes of the [G][MAX_MOVES] u16
+    LAUNCH(ctx, k_opponent_exchange, ctx->d, dbits, ctx->t_i32b);
+    HIP_TRY(ctx, to_host(ctx, bits, (const uint8_t *)dbits, G * MAX_MOVES));
+    HIP_TRY(ctx, to_host(ctx, counts, ctx->t_i32b, G));
+    return check_dev_error(ctx);
+}
+
 // the static evaluation of every window slot's current position (csrc/opponent.hpp: STATIC EVALUATION / EVALUATION)
 int crl_opponent_evaluate(crl_ctx *ctx, int evaluation, int32_t *scores)
 {
@@ -1062,6 +1109,28 @@ int crl_sim_reply_opponent_sel(crl_ctx *ctx, const int32_t *dev_depths_i32, int 
         return crl_sim_reply_opponent_ev(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, evaluation,
                                          dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
     LAUNCH(ctx, reply_sel_kernel(quiescence > 0, repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL), ctx->d,
+           dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2, (unsigned long long *)dev_nodes_u64,
+           dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+    return CRL_OK;
+}
+
+// exchange = 0 is the _sel call; 1 (it needs ordering and quiescence >= 1) launches the k_reply_opponent_exc kernel of
+// the same shape
+int crl_sim_reply_opponent_exc(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, int repetition, int evaluation, int selective, int exchange,
+                               void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                               uint64_t *dev_depth_sum_u64)
+{
+    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
+                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
+                   (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1) &&
+                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL) &&
+                   (selective == 0 || (selective == 1 && ordering == 1)) &&
+                   (exchange == 0 || (exchange == 1 && ordering == 1 && quiescence >= 1)));
+    if (!exchange)
+        return crl_sim_reply_opponent_sel(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, evaluation,
+                                          selective, dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
+    LAUNCH(ctx, reply_exc_kernel(repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL, selective != 0), ctx->d,
            dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2, (unsigned long long *)dev_nodes_u64,
            dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
     return CRL_OK;

@@ -37,7 +37,8 @@
 //         its victim.  Without a tactical move the value is stand.
 // Children, the strictly-greater rule, alpha and the cut are those of SEARCH.  The root (k = 0 < d) is never a
 // quiescence node, so the root rule holds.  The evaluation is bounded by material, so a score that is not a mate stays
-// inside (-30000 + k, 30000 - k).  Not done: delta or exchange pruning, checks other than the evasions of 4b.
+// inside (-30000 + k, 30000 - k).  Not done: checks other than the evasions of 4b; delta and exchange pruning only on
+// request (EXCHANGE below).
 // (tests/quiescence_util.py restates this section.)
 //
 // ORDER OF THE MOVES.  At the root: python-chess generation order, as wave_movegen emits it.  Below the root: a stable
@@ -272,6 +273,53 @@
 // predicate (a promotion, or a piece has left the board: the same moves).  ONE call site of the evaluation per
 // kernel: with quiescence ahead of the move generation (the stand-pat and the null move's last guard), without it
 // behind the move generation (the horizon and that guard).  (tests/selective_util.py restates this section.)
+//
+// EXCHANGE (the _exc kernels only: exchange = 1, an opt-in on top of ORDERING, so of ITERATIVE DEEPENING and a node
+// budget, with Q >= 1; it combines freely with REPETITION, EVALUATION and SELECTIVE, and everything in those sections
+// holds.  Every other launch tries every tactical move of a stand-pat node, as QUIESCENCE 4c says).  Delta and exchange
+// pruning in quiescence; the margin 200 is conventional, untuned and fixed.
+//     Where.  Only at a quiescence node that stands pat and searches moves -- QUIESCENCE 4c: not in check,
+//     stand < beta, after alpha = max(alpha, stand); under SELECTIVE the quiescence node of that section.  Never at a
+//     node in check (4b), at a node above the horizon, or at the root.
+//     What.  After the victim partition the tactical moves mv[0 .. nt) pass two tests in this order; a move that fails
+//     either is removed from the node's list and the others keep their order (a stable compaction).  The node then
+//     searches what is left exactly as before; a removed move touches neither best nor alpha.  If nothing is left the
+//     value is stand, as for a node without a tactical move (no frame).
+//     value(.)  is the material of STATIC EVALUATION whichever evaluation the call uses: P 100, N 320, B 330, R 500,
+//     Q 900 (a king's value is never read).  The victim of a move is the piece on its destination; an en-passant
+//     capture has the victim P; a promotion onto an empty square has none, value 0.
+//     1. Delta.  The move is removed if it is not a promotion and stand + value(victim) + 200 <= alpha.
+//     2. Exchange.  The move is removed if SEE(m) < 0, the static exchange value on its destination square t:
+//         the occupancy starts as the node's without the mover's origin square (and, en passant, without the captured
+//         pawn) and with t;  gain[0] = value(victim), and a promotion adds value(promoted) - 100;  the piece on t is
+//         the mover, or the promoted piece;
+//         the sides then alternate, beginning with the opponent of the mover.  The side to capture takes with its
+//         least valuable attacker of t: the pieces of that side which stand in the occupancy and attack t in it
+//         (sliders stop at the first piece of the occupancy, so a slider behind a piece that has captured joins in: an
+//         x-ray), in the order P, N, B, R, Q, K and inside a type the lowest square index first.  Without an attacker
+//         the sequence ends.  A king captures only if the other side has no attacker of t in the occupancy as it is
+//         before the king's capture; otherwise the sequence ends before it.  A king's capture ends the sequence;
+//         capture d = 1, 2, .. has gain[d] = value(piece on t) - gain[d - 1]; the capturing piece then leaves the
+//         occupancy and is the piece on t;
+//         pins are ignored, and a pawn that captures on the last rank stays a pawn;
+//         either side may stop before any of its captures: from the last capture back, gain[d - 1] =
+//         -max(-gain[d - 1], gain[d]), and SEE(m) = gain[0].  Only its sign is read.
+// Consequences.  (a) Off, nothing changes: the same entries are called and the same kernels launched.  (b) On, from a
+// root whose search meets no removable move, every output equals the search without this section, `nodes` included.
+// (c) The search is no longer minimax over the full quiescence tree; it stays a function of the root, its reversible
+// history and the arguments.  (d) The filter generates no moves, so it costs no node: a node becomes dearer in time,
+// not in count.  (e) gain[0] >= 0, so a capture of a piece worth at least the mover is never removed by test 2.
+// Structure.  One site, behind opp_partition_victim in the 4c branch.  Lane i judges mv[i], 64 moves per pass and as
+// many passes as nt needs; each lane runs its own exchange loop on the wave-uniform board (the attack sets of
+// attackers_to with the lane's destination and occupancy, both colours in one set per capture: only the sliders'
+// share changes with the occupancy), so the loop is divergent and a pass lasts as long as its longest exchange.  The
+// SIGN of SEE needs no list of gains: the lane keeps one balance and one answer bit -- balance = value(piece on t) - gain[0],
+// answer "not negative"; if balance <= 0 the answer stands; every capture flips the answer and sets balance =
+// value(capturer) - balance, and the sequence is left as soon as balance < answer; a king flips the answer only if it
+// may capture.  Nothing is indexed per lane, so nothing goes to scratch.  One ballot per pass and prefix popcounts
+// compact the list, the scheme of opp_partition.  Frames, LDS and sizeof(OppFrame) stay; F->nt of such a node is the
+// filtered count.  k_opponent_exchange judges, without a search, every legal move of a slot's current position with
+// test 2 alone.  (tests/exchange_util.py restates this section and checks the sign form against the definition.)
 #pragma once
 #include "search.hpp"
 
@@ -607,6 +655,92 @@ __device__ inline void opp_move_to_front(u16 *mv, int n, u32 pm, int lane)
     __syncthreads();
 }
 
+// EXCHANGE of the header comment.  The material of a piece type (selects, no table: nothing is indexed per lane)
+__device__ inline int opp_value(int pt)
+{
+    return pt == PAWN ? 100 : pt == KNIGHT ? 320 : pt == BISHOP ? 330 : pt == ROOK ? 500 : pt == QUEEN ? 900 : 0;
+}
+
+// the value of the victim of the tactical move mv of `b` (occ: its occupancy): en passant P, a quiet promotion 0
+__device__ inline int opp_victim_value(const Board &b, u64 occ, u32 mv)
+{
+    const int to = (mv >> 6) & 63;
+    if (occ & bit(to)) return opp_value(piece_at(b, to));
+    return ((mv >> 12) & 7) ? 0 : 100;
+}
+
+// whether SEE(mv) >= 0 for the TACTICAL move mv of `b`: the alternating-bound form of the header.  `b` is wave-uniform,
+// mv is the lane's; every lane that enters runs its own loop, at most once per piece on the board.
+__device__ inline bool opp_see_not_negative(const Board &b, u64 occ0, u32 mv)
+{
+    const int from = mv & 63, to = (mv >> 6) & 63, promo = (mv >> 12) & 7;
+    const bool white = st_turn(b.state);
+    const u64 tb = bit(to);
+    u64 occ = occ0 & ~bit(from);
+    int first;
+    if (occ0 & tb) first = opp_value(piece_at(b, to));
+    else if (promo) first = 0;
+    else {                                                 // tactical, nothing on t, no promotion: en passant
+        first = 100;
+        occ &= ~bit(white ? to - 8 : to + 8);              // (t is on rank 6 or 3)
+    }
+    occ |= tb;
+    int on_t = opp_value(piece_at(b, from));
+    if (promo) { on_t = opp_value(promo - 1); first += on_t - 100; }
+    int balance = on_t - first;
+    if (balance <= 0) return true;                         // not negative even if the piece on t is lost for nothing
+    // the attackers of t of BOTH colours in one set per capture: only the sliders' share changes with the occupancy
+    const u64 rq = b.bb[ROOK] | b.bb[QUEEN], bq = b.bb[BISHOP] | b.bb[QUEEN];
+    const u64 fixed = (knight_attacks(to) & b.bb[KNIGHT]) | (king_attacks(to) & b.bb[KING]) |
+                      (b.bb[PAWN] & ((pawn_attacks(to, false) & b.white) | (pawn_attacks(to, true) & ~b.white)));
+    bool answer = true, side = white;
+    for (;;) {
+        side = !side;
+        const u64 all = (fixed | (rook_attacks(to, occ) & rq) | (bishop_attacks(to, occ) & bq)) & occ;
+        const u64 att = all & (side ? b.white : ~b.white);
+        if (!att) break;
+        int t = KING;
+        u64 s = att;
+#pragma unroll
+        for (int q = QUEEN; q >= PAWN; q--)
+            if (att & b.bb[q]) { t = q; s = att & b.bb[q]; }
+        if (t == KING) {                                   // it captures only where nothing could take it back
+            if (!(all & ~att)) answer = !answer;
+            break;
+        }
+        answer = !answer;
+        occ &= ~(s & (0ull - s));                          // the lowest square of the type
+        balance = opp_value(t) - balance;
+        if (balance < (answer ? 1 : 0)) break;
+    }
+    return answer;
+}
+
+// the two tests on the tactical moves mv[0 .. nt) of the stand-pat node `b`, and the stable compaction of those that
+// pass.  Returns how many are left: they are mv[0 .. that).  mv is visible on entry and on return; nt, stand and alpha
+// are wave-uniform.  A pass writes at or below what it read, and later passes read above it.
+__device__ inline int opp_exchange_filter(const Board &b, u16 *mv, int nt, int stand, int alpha, int lane)
+{
+    const u64 occ = occupied(b);
+    const u64 below = bit(lane) - 1;
+    int kept = 0;
+    for (int base = 0; base < nt; base += 64) {
+        const int i = base + lane;
+        const u32 m = i < nt ? mv[i] : 0u;
+        bool keep = false;
+        if (i < nt) {
+            keep = ((m >> 12) & 7) != 0 || stand + opp_victim_value(b, occ, m) + 200 > alpha;      // 1. delta
+            if (keep) keep = opp_see_not_negative(b, occ, m);                                      // 2. exchange
+        }
+        const u64 K = __ballot(keep);
+        __syncthreads();                                   // every move of the pass read before any is rewritten
+        if (keep) mv[kept + popc(K & below)] = (u16)m;     // kept + rank <= i < nt
+        kept += popc(K);
+    }
+    __syncthreads();
+    return kept;
+}
+
 // The search of the header comment, stated once for both kernels: from `root` to depth Dmax (1 .. OPP_MAX_DEPTH, checked by
 // the caller) with Q quiescence plies (QS: 1 .. OPP_MAX_QUIESCENCE, checked by the caller; otherwise not read) under the
 // node limit, in the frames f[0 .. Dmax] or, QS, f[0 .. Dmax + Q - 1].  mv: the move (NO_MOVE only for a root without a legal
@@ -623,6 +757,7 @@ __device__ inline void opp_move_to_front(u16 *mv, int n, u32 pm, int lane)
 // SEL: SELECTIVE of the header comment, on top of ORD.  The entering node carries `e` (its remaining depth r where
 // r > 0, otherwise -j) beside its window; a frame keeps e, whether its node is in check and what its current child is
 // in its pad word, so a node reads there whether a null move led to it.  Every line marked SEL folds away without it.
+// EXC: EXCHANGE of the header comment, on top of ORD and QS: one site, the filter behind the victim partition of 4c.
 struct OppResult { u32 mv; int score; long long nodes; bool done; int depth_done; };
 
 // SEL: the board after a null move -- the side to move exchanged, no en-passant square, the halfmove clock 0
@@ -646,7 +781,8 @@ __device__ inline bool opp_null_guards(const Board &b, int k, int e, int beta, c
     return ((u32)uni(f[k - 1].pad) & 3u) != OPP_CHILD_NULL;
 }
 
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false,
+          bool EXC = false>
 __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long long limit, OppFrame *f, int lane,
                                        OppRepLds<QS> *rs = nullptr, OppRepRoot rr = OppRepRoot())
 {
@@ -654,6 +790,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
     static_assert(ID || !REP, "REPETITION requires ITERATIVE DEEPENING");
     static_assert(ID || !POS, "EVALUATION requires ITERATIVE DEEPENING");
     static_assert(ORD || !SEL, "SELECTIVE requires ORDERING");
+    static_assert((ORD && QS) || !EXC, "EXCHANGE requires ORDERING and quiescence plies");
     int K = 0;                                             // REP: the positions behind the root that hh holds
     if (ORD) {                                             // both killers of every ply: NO_MOVE
         constexpr int NF = QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1;
@@ -741,6 +878,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
                 cnt = opp_partition_victim(b, F->mv, n, lane);
                 best0 = stand;
                 if (stand > a) a = stand;
+                if (EXC) cnt = opp_exchange_filter(b, F->mv, cnt, stand, a, lane);
                 nt = cnt;                                  // (never below the cursor: no killer from this frame)
             } else if (k > 0) {
                 if (ORD) {
@@ -894,7 +1032,8 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
 
 // One slot of k_opponent_moves / k_opponent_moves_q and, ID, of their _id forms.  Window-relative rows: depths / moves /
 // scores / nodes_out / flags [count] and, ID only, depths_done [count]
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false,
+          bool EXC = false>
 __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, int push, long long limit, u16 *moves,
                                            int32_t *scores, long long *nodes_out, uint8_t *flags, OppLds<QS> &s,
                                            int32_t *depths_done = nullptr, OppRepLds<QS> *rs = nullptr)
@@ -914,7 +1053,7 @@ __device__ inline void opponent_moves_slot(Dev d, const int32_t *depths, int Q, 
     const Board root = uni_board(d.cur[g]);
     OppRepRoot rr;                                         // REP: the root is the game's current position
     rr.d = &d; rr.g = g; rr.tp = 0; rr.ply = REP ? uni(d.game[g].ply) : 0;
-    const OppResult o = opp_search<QS, ID, ORD, REP, POS, SEL>(root, D, Q, limit, s.f, lane, rs, rr);
+    const OppResult o = opp_search<QS, ID, ORD, REP, POS, SEL, EXC>(root, D, Q, limit, s.f, lane, rs, rr);
     if (lane == 0) {
         moves[r] = (u16)o.mv;
         scores[r] = o.score;
@@ -1030,7 +1169,8 @@ __global__ __launch_bounds__(64) void k_opponent_moves_idor_q(Dev d, const int32
 // search is ITERATIVE DEEPENING under the budget `limit`, and depth_acc [count] sums the completed depths.
 // REP: REPETITION -- S1 stands at tree ply 2 * path_len - 1 of the one path d.path_node holds, so what led to it is the
 // S1 / S2 of the pending node's ancestors and then the game's ring.
-template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false>
+template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false,
+          bool EXC = false>
 __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, long long limit, void *planes2,
                                           unsigned long long *nodes_acc, uint32_t *cuts_acc, OppLds<QS> &s,
                                           unsigned long long *depth_acc = nullptr, OppRepLds<QS> *rs = nullptr)
@@ -1047,7 +1187,7 @@ __device__ inline void reply_opponent_row(Dev d, const int32_t *depths, int Q, l
     const Board s1 = uni_board(d.node[(size_t)g * d.N + c].s1);
     OppRepRoot rr;
     rr.d = &d; rr.g = g; rr.tp = REP ? 2 * uni(d.game[g].path_len) - 1 : 0; rr.ply = REP ? uni(d.game[g].ply) : 0;
-    const OppResult o = opp_search<QS, ID, ORD, REP, POS, SEL>(s1, D, Q, limit, s.f, lane, rs, rr);
+    const OppResult o = opp_search<QS, ID, ORD, REP, POS, SEL, EXC>(s1, D, Q, limit, s.f, lane, rs, rr);
     if (o.mv == NO_MOVE) { dev_error(d, DERR_STATE); return; }              // S1 is running: it has a legal move
     if (lane == 0) {
         nodes_acc[r] += (unsigned long long)o.nodes;
@@ -1207,6 +1347,66 @@ __global__ __launch_bounds__(64) void k_reply_opponent_sel(Dev d, const int32_t 
     } else
         reply_opponent_row<QS, true, true, false, POS, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc,
                                                              cuts_acc, s, depth_acc);
+}
+
+// EXCHANGE: the eight ordered budgeted shapes with quiescence plies (repetition, evaluation, selective) once more with
+// delta and exchange pruning at the stand-pat nodes, as two kernel templates with the argument lists of the _ev kernels.
+template <bool REP, bool POS, bool SEL>
+__global__ __launch_bounds__(64) void k_opponent_moves_exc(Dev d, const int32_t *depths, int Q, int push,
+                                                           long long budget, u16 *moves, int32_t *scores,
+                                                           long long *nodes_out, uint8_t *flags, int32_t *depths_done)
+{
+    __shared__ OppLds<true> s;
+    if constexpr (REP) {
+        __shared__ OppRepLds<true> rs;
+        opponent_moves_slot<true, true, true, true, POS, SEL, true>(d, depths, Q, push, budget, moves, scores,
+                                                                    nodes_out, flags, s, depths_done, &rs);
+    } else
+        opponent_moves_slot<true, true, true, false, POS, SEL, true>(d, depths, Q, push, budget, moves, scores,
+                                                                     nodes_out, flags, s, depths_done);
+}
+
+template <bool REP, bool POS, bool SEL>
+__global__ __launch_bounds__(64) void k_reply_opponent_exc(Dev d, const int32_t *depths, int Q, long long budget,
+                                                           void *planes2, unsigned long long *nodes_acc,
+                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
+{
+    __shared__ OppLds<true> s;
+    if constexpr (REP) {
+        __shared__ OppRepLds<true> rs;
+        reply_opponent_row<true, true, true, true, POS, SEL, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc,
+                                                                   s, depth_acc, &rs);
+    } else
+        reply_opponent_row<true, true, true, false, POS, SEL, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc,
+                                                                    s, depth_acc);
+}
+
+// EXCHANGE, test 2 alone and no search: every legal move of every window slot's current position, in generation
+// order.  bits [count][MAX_MOVES], window-relative: bit 0 = the move is tactical, bit 1 = it is kept (SEE >= 0; always
+// set for a move that is not tactical; 0 from the slot's move count on); counts [count]: the legal moves of the slot.  Lane i judges move i, 64 per pass.
+__global__ __launch_bounds__(64) void k_opponent_exchange(Dev d, uint8_t *bits, int32_t *counts)
+{
+    __shared__ u16 mv[MAX_MOVES];
+    const int r = blockIdx.x, g = r + d.g0, lane = threadIdx.x;
+    const Board b = uni_board(d.cur[g]);
+    const MoveGenInfo mi = wave_movegen(b, lane, mv);
+    __syncthreads();
+    int n = uni(mi.n);
+    if (n > MAX_MOVES) n = MAX_MOVES;                      // (no position has more than MAX_BRANCH)
+    const u64 occ = occupied(b);
+    const u64 own = st_turn(b.state) ? b.white : (occ & ~b.white);
+    for (int base = 0; base < MAX_MOVES; base += 64) {     // (the entries from n on: 0)
+        const int i = base + lane;
+        uint8_t out = 0;
+        if (i < n) {
+            const u32 m = mv[i];
+            const bool tact = opp_tactical(b, occ, own, m);
+            const bool keep = !tact || opp_see_not_negative(b, occ, m);
+            out = (uint8_t)((tact ? 1 : 0) | (keep ? 2 : 0));
+        }
+        bits[(size_t)r * MAX_MOVES + i] = out;
+    }
+    if (lane == 0) counts[r] = n;
 }
 
 // the static evaluation of every window slot's current position: scores [count], window-relative

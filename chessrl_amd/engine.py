@@ -240,7 +240,8 @@ class LockstepEngine(object):
     A budgeted player with ``repetition`` replies through the repetition-aware kernels (``k_reply_opponent_idr`` /
     ``_idor``): a reply search scores a position it has had, in its own line, on the tree path or in the game, a draw.
     A budgeted player with ``evaluation="positional"`` replies through the ``k_reply_opponent_ev`` kernel of the same shape,
-    one with ``selective=True`` through the ``k_reply_opponent_sel`` kernel of the same shape.
+    one with ``selective=True`` through the ``k_reply_opponent_sel`` kernel of the same shape, one with
+    ``exchange=True`` through the ``k_reply_opponent_exc`` kernel of the same shape.
     """
 
     def __init__(self, evaluator, n_games, max_sims, device=0, max_plies=4096,
@@ -426,7 +427,8 @@ class LockstepEngine(object):
                                     quiescence=self.reply.quiescence, node_budget=budget,
                                     dev_depth_sum=None if budget is None else self.reply_depth_sum.data_ptr(),
                                     ordering=self.reply.ordering, repetition=self.reply.repetition,
-                                    evaluation=self.reply.evaluation, selective=self.reply.selective)
+                                    evaluation=self.reply.evaluation, selective=self.reply.selective,
+                                    exchange=self.reply.exchange)
 
     def phase_tower_s2(self):
         if self.legal_priors:

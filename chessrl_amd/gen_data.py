@@ -13,7 +13,8 @@ budget; csrc/opponent.hpp, REPETITION): without it a large share of the games ar
 shuffles until the fifth occurrence.  ``evaluation="positional"`` / ``--eval positional`` (with a node budget;
 csrc/opponent.hpp, EVALUATION) gives both sides the positional static evaluation instead of material and centrality.
 ``selective=True`` / ``--selective`` (with ordering; csrc/opponent.hpp, SELECTIVE) gives both sides null-move pruning
-and late-move reductions.
+and late-move reductions.  ``exchange=True`` / ``--exchange`` (with ordering and quiescence; csrc/opponent.hpp, EXCHANGE)
+gives both sides delta and exchange pruning in quiescence.
 """
 import argparse
 import logging
@@ -63,7 +64,7 @@ def side_depths(draws, white_to_move):
 
 def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=4, seed=0, workers=2, max_plies=512,
              quiescence=0, node_budget=None, ordering=False, repetition=False, evaluation="material",
-             selective=False):
+             selective=False, exchange=False):
     """Plays ``num_games`` games, saves the finished ones to ``save_path`` (appending to what the file holds, as
     ``DatasetGame.save`` does) and returns the ``DatasetGame`` it saved.  The reference's ``gen_data`` forgets to
     pass ``depth`` and ``random_dep`` on to ``play_game`` (gen_data_stockfish.py:44-49); here both are honoured.
@@ -73,7 +74,8 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
     (needs a ``node_budget``): with the move ORDERING of csrc/opponent.hpp; ``repetition`` (needs a ``node_budget``):
     with its REPETITION rule, both sides score a position below the root that occurred before a draw; ``evaluation``
     ("positional" needs a ``node_budget``): both sides search with its EVALUATION; ``selective`` (needs ``ordering``):
-    both sides search with its SELECTIVE rules."""
+    both sides search with its SELECTIVE rules; ``exchange`` (needs ``ordering`` and ``quiescence`` >= 1): both sides
+    search with its EXCHANGE rules."""
     if ordering and node_budget is None:
         raise ValueError("ordering needs a node_budget")
     if repetition and node_budget is None:
@@ -83,6 +85,7 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
     if node_budget is not None and int(node_budget) < 1:
         raise ValueError("node_budget must be None or at least 1")
     quiescence = int(quiescence)
+    exchange = _lib.opponent_exchange(exchange, ordering, node_budget, quiescence)
     if not 0 <= quiescence <= _lib.OPP_MAX_QUIESCENCE:
         raise ValueError("quiescence must lie in [0, %d]" % _lib.OPP_MAX_QUIESCENCE)
     num_games, opening_plies, max_plies = int(num_games), int(opening_plies), int(max_plies)
@@ -109,7 +112,8 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
                 break
             ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True,
                                quiescence=quiescence, node_budget=node_budget, ordering=bool(ordering),
-                               repetition=bool(repetition), evaluation=evaluation, selective=selective)
+                               repetition=bool(repetition), evaluation=evaluation, selective=selective,
+                               exchange=exchange)
             results = ctx.results()
         moves, plies, results = ctx.records()
     finally:
@@ -141,6 +145,8 @@ def main(argv=None):
                    help="Static evaluation of the --nodes search, both sides (positional needs --nodes).")
     p.add_argument("--selective", action="store_true", default=False,
                    help="Null-move pruning and late-move reductions in the --ordering search, both sides.")
+    p.add_argument("--exchange", action="store_true", default=False,
+                   help="Delta and exchange pruning in the quiescence of the --ordering search, both sides.")
     p.add_argument("--random_depth", action="store_true", default=False,
                    help="Use normal distribution of depths with mean --depth.")
     p.add_argument("--debug", action="store_true", default=False, help="Log debug messages on screen. Default false.")
@@ -151,7 +157,7 @@ def main(argv=None):
     gen_data(a.data_path, num_games=a.games, depth=a.depth, random_dep=a.random_depth,
              opening_plies=a.opening_plies, seed=a.seed, quiescence=a.quiescence,
              node_budget=a.nodes, ordering=a.ordering, repetition=a.repetition, evaluation=a.evaluation,
-             selective=a.selective)
+             selective=a.selective, exchange=a.exchange)
 
 
 if __name__ == "__main__":

@@ -16,7 +16,9 @@ history -- a draw (opponent.hpp, REPETITION), so a side that is ahead stops shuf
 ``evaluation="positional"`` on top of a budget replaces the static evaluation (material and centrality) by a tapered
 one with pawn structure, mobility, files, king shelter and king attack (opponent.hpp, EVALUATION);
 ``selective=True`` on top of ``ordering`` adds null-move pruning and late-move reductions, so the budget goes to fewer
-lines, deeper (opponent.hpp, SELECTIVE).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
+lines, deeper (opponent.hpp, SELECTIVE); ``exchange=True`` on top of ``ordering`` and ``quiescence`` >= 1 drops, at the
+quiescence nodes that stand pat, the captures that cannot come near alpha or lose material on their square (opponent.hpp,
+EXCHANGE).  The batched form (thousands of games per launch) is ``Context.opponent_moves``;
 these classes are the one-game drop-in surface over it.
 """
 import numpy as np
@@ -45,10 +47,11 @@ class MinimaxPlayer(Player):
     budget it does not reach it plays the same move for fewer nodes.  ``repetition`` (needs a ``node_budget``): a node
     below the root whose position occurred before is worth 0 (opponent.hpp, REPETITION).  ``evaluation``: "material"
     or "positional" (needs a ``node_budget``; opponent.hpp, EVALUATION).  ``selective`` (needs ``ordering``): null-move
-    pruning and late-move reductions (opponent.hpp, SELECTIVE); the search is then no longer full-width."""
+    pruning and late-move reductions (opponent.hpp, SELECTIVE); the search is then no longer full-width.  ``exchange``
+    (needs ``ordering`` and ``quiescence`` >= 1): delta and exchange pruning in quiescence (opponent.hpp, EXCHANGE)."""
 
     def __init__(self, color, search_depth=2, node_limit=NODE_LIMIT, quiescence=0, node_budget=None, ordering=False,
-                 repetition=False, evaluation="material", selective=False):
+                 repetition=False, evaluation="material", selective=False, exchange=False):
         super().__init__(color)
         if not 1 <= int(search_depth) <= MAX_DEPTH:
             raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
@@ -71,6 +74,7 @@ class MinimaxPlayer(Player):
         _lib.opponent_evaluation(evaluation, self.node_budget)
         self.evaluation = evaluation
         self.selective = _lib.opponent_selective(selective, self.ordering)
+        self.exchange = _lib.opponent_exchange(exchange, self.ordering, self.node_budget, self.quiescence)
         self.last = None                      # (score, nodes, flag) of the last search
         self.last_depth = None                # with a budget: the depth that search completed
 
@@ -80,7 +84,8 @@ class MinimaxPlayer(Player):
         ctx = arena().one(game._slot)
         out = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False, node_limit=self.node_limit,
                                  quiescence=self.quiescence, node_budget=self.node_budget, ordering=self.ordering,
-                                 repetition=self.repetition, evaluation=self.evaluation, selective=self.selective)
+                                 repetition=self.repetition, evaluation=self.evaluation, selective=self.selective,
+                                 exchange=self.exchange)
         moves, scores, nodes, flags = out[:4]
         self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
         self.last_depth = int(out[4][0]) if self.node_budget is not None else None
@@ -96,12 +101,12 @@ class GameOpponent(Game):
     """Mirror of ``GameStockfish``: a game against the built-in opponent.  ``opponent``: a ``MinimaxPlayer``, or
     None for one of depth ``opponent_depth``, ``opponent_quiescence``, ``opponent_budget`` (the player's
     ``node_budget``), ``opponent_ordering`` (its ``ordering``), ``opponent_repetition`` (its ``repetition``) and
-    ``opponent_evaluation`` (its ``evaluation``) and ``opponent_selective`` (its ``selective``) with the colour
-    opposite to ``player_color``."""
+    ``opponent_evaluation`` (its ``evaluation``), ``opponent_selective`` (its ``selective``) and ``opponent_exchange``
+    (its ``exchange``) with the colour opposite to ``player_color``."""
 
     def __init__(self, opponent=None, player_color=Game.WHITE, board=None, date=None, opponent_depth=2,
                  opponent_quiescence=0, opponent_budget=None, opponent_ordering=False, opponent_repetition=False,
-                 opponent_evaluation="material", opponent_selective=False):
+                 opponent_evaluation="material", opponent_selective=False, opponent_exchange=False):
         if opponent is not None and not isinstance(opponent, MinimaxPlayer):
             raise ValueError("opponent must be a MinimaxPlayer or None")
         self.opponent = None                  # (a board's move stack is replayed by plain Game.move)
@@ -110,7 +115,8 @@ class GameOpponent(Game):
             opponent = MinimaxPlayer(not self.player_color, search_depth=opponent_depth,
                                      quiescence=opponent_quiescence, node_budget=opponent_budget,
                                      ordering=opponent_ordering, repetition=opponent_repetition,
-                                     evaluation=opponent_evaluation, selective=opponent_selective)
+                                     evaluation=opponent_evaluation, selective=opponent_selective,
+                                     exchange=opponent_exchange)
         self.opponent = opponent
 
     def move(self, movement):

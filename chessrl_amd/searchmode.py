@@ -118,4 +118,4 @@ class SearchMode(object):
         r = self.reply
         return (self.threads, self.simulate,
                 None if r is None else (r.search_depth, r.node_limit, r.quiescence, r.node_budget, r.ordering, r.repetition,
-                                         r.evaluation, r.selective))
+                                         r.evaluation, r.selective, r.exchange))

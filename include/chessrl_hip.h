@@ -70,8 +70,8 @@ typedef struct crl_ctx crl_ctx;
  * signature hands the GPU garbage pointers).  crl_source_hash(): sha256 over the sources (csrc/ + this
  * header + compiler flags) the library was built from, as chessrl_amd/_lib.py computes it; the string
  * is also findable in the file itself behind the marker "CRL_SRC_HASH=".  No reference counterpart.
- * (The _ord, _rep, _ev and _sel entries of the built-in opponent and crl_opponent_evaluate are additions that change
- * no existing signature or meaning: still 9.) */
+ * (The _ord, _rep, _ev, _sel and _exc entries of the built-in opponent, crl_opponent_evaluate and
+ * crl_opponent_exchange are additions that change no existing signature or meaning: still 9.) */
 #define CRL_ABI_VERSION 9
 int  crl_abi_version(void);
 const char *crl_source_hash(void);
@@ -412,6 +412,29 @@ int  crl_opponent_moves_sel(crl_ctx *ctx, const int32_t *depths /*G*/, int quies
 int  crl_sim_reply_opponent_sel(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
                                 int ordering, int repetition, int evaluation, int selective, void *dev_planes_s2,
                                 uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64);
+/* The two _sel calls with opt-in EXCHANGE (csrc/opponent.hpp states it): delta and exchange pruning at the quiescence
+ * nodes that stand pat.  exchange = 0 is the _sel call, array for array, from the same kernels.  exchange = 1 needs
+ * ordering = 1 and quiescence >= 1 and launches the k_opponent_moves_exc / k_reply_opponent_exc kernel of the same
+ * shape (repetition, evaluation, selective): at such a node a tactical move that is no promotion is dropped when
+ * stand + value(victim) + 200 <= alpha, and any tactical move when its static exchange value on the destination
+ * square is negative.  The filter generates no moves: node counts count what they counted.  From a root whose search
+ * meets no such move every output equals the _sel call's.
+ * CRL_ERR_ARG: an exchange other than 0 or 1, exchange = 1 with ordering = 0 or quiescence = 0, and what the _sel calls
+ * refuse.  No state changes on an error. */
+int  crl_opponent_moves_exc(crl_ctx *ctx, const int32_t *depths /*G*/, int quiescence, int push, int64_t node_budget,
+                            int ordering, int repetition, int evaluation, int selective, int exchange,
+                            uint16_t *moves /*G*/, int32_t *scores /*G*/, int64_t *nodes /*G*/, uint8_t *flags /*G*/,
+                            int32_t *depths_done /*G*/);
+int  crl_sim_reply_opponent_exc(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                                int ordering, int repetition, int evaluation, int selective, int exchange,
+                                void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                                uint64_t *dev_depth_sum_u64);
+/* The exchange test alone, without a search, for every legal move of every window slot's current position, whatever
+ * the game's result: bits[g * CRL_MAX_MOVES + i] for move i of crl_legal_moves' order (host uint8, synchronous,
+ * window-relative) has bit 0 set if the move is tactical and bit 1 if the test keeps it (static exchange value >= 0;
+ * always set for a move that is not tactical); bytes from counts[g] on are 0.  counts[g]: the slot's legal
+ * moves.  No state change.  CRL_ERR_ARG: a NULL array. */
+int  crl_opponent_exchange(crl_ctx *ctx, uint8_t *bits /*G*CRL_MAX_MOVES*/, int32_t *counts /*G*/);
 /* The static evaluation of every window slot's current position, from the side to move, whatever the game's result:
  * scores[g] (host int32, synchronous, window-relative).  evaluation as above: 0 is STATIC EVALUATION of
  * csrc/opponent.hpp, 1 its EVALUATION.  No search, no state change.

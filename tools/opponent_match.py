@@ -2,8 +2,9 @@
 """Two settings of the built-in opponent (csrc/opponent.hpp) play each other over paired openings.
 
     python tools/opponent_match.py [--pairs 512] [--depth 3] [--budget 600] [--quiescence 2] [--ordering] [--repetition]
-                                   [--eval-a positional] [--eval-b material] [--selective] [--opening-plies 6]
-                                   [--max-plies 300] [--seed 0] [--out profiles/opponent_match.json]
+                                   [--eval-a positional] [--eval-b material] [--selective] [--exchange]
+                                   [--opening-plies 6] [--max-plies 300] [--seed 0]
+                                   [--out profiles/opponent_match.json]
 
 Games 2i and 2i + 1 share --opening-plies random plies (the in-slot playout call; the words come from
 ``chessrl_amd.gen_data.opening_words``, the source ``gen_data`` draws them from); setting A is white in game 2i and
@@ -11,7 +12,9 @@ black in game 2i + 1.  All games advance in lockstep: per ply two ``opponent_mov
 complementary depth masks -- depth 0 leaves a slot alone -- so each side is searched with its own settings.  --depth,
 --budget, --quiescence, --ordering and --repetition hold for both sides; the sides differ in their evaluation and,
 with --selective (it needs --ordering), in that A searches with the SELECTIVE rules of opponent.hpp and B without: give
-both sides the same evaluation to measure the rules alone.
+both sides the same evaluation to measure the rules alone.  With --exchange (it needs --ordering and --quiescence >= 1)
+A searches with the EXCHANGE rules of opponent.hpp and B without, everything else equal when both sides get the same
+evaluation; a node of A is dearer in time, the match is at equal nodes.
 
 Printed and written: wins, draws and losses of A, its score (a game still running at --max-plies counts as a draw)
 with a 95 % interval over the pair scores, the games still running and their share, and how every game ended (the
@@ -35,12 +38,13 @@ def side_kw(settings):
     """The keywords of ``Context.opponent_moves`` of one side's settings (without its depth)."""
     return dict(quiescence=settings.get("quiescence", 0), node_budget=settings["node_budget"],
                 ordering=bool(settings.get("ordering", False)), repetition=bool(settings.get("repetition", False)),
-                evaluation=settings.get("evaluation", "material"), selective=bool(settings.get("selective", False)))
+                evaluation=settings.get("evaluation", "material"), selective=bool(settings.get("selective", False)),
+                exchange=bool(settings.get("exchange", False)))
 
 
 def play(pairs, a, b, opening_plies=6, max_plies=300, seed=0):
     """Plays 2 * ``pairs`` games between the settings ``a`` and ``b`` (dicts: depth, node_budget, quiescence, ordering,
-    repetition, evaluation, selective) and returns (a_white bool [G], moves u16 [G][plies], plies, results): A is white in the
+    repetition, evaluation, selective, exchange) and returns (a_white bool [G], moves u16 [G][plies], plies, results): A is white in the
     even games."""
     import numpy as np
     from chessrl_amd import _lib
@@ -145,6 +149,7 @@ def main(argv=None):
     ap.add_argument("--eval-a", default="positional", choices=("material", "positional"))
     ap.add_argument("--eval-b", default="material", choices=("material", "positional"))
     ap.add_argument("--selective", action="store_true", help="A searches with the selective rules, B without")
+    ap.add_argument("--exchange", action="store_true", help="A searches with delta and exchange pruning, B without")
     ap.add_argument("--opening-plies", type=int, default=6)
     ap.add_argument("--max-plies", type=int, default=300)
     ap.add_argument("--seed", type=int, default=0)
@@ -152,9 +157,13 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.selective and not args.ordering:
         ap.error("--selective needs --ordering")
+    if args.exchange and not (args.ordering and args.quiescence >= 1):
+        ap.error("--exchange needs --ordering and --quiescence >= 1")
     common = dict(depth=args.depth, node_budget=args.budget, quiescence=args.quiescence, ordering=args.ordering,
                   repetition=args.repetition)
-    a, b = dict(common, evaluation=args.eval_a, selective=args.selective), dict(common, evaluation=args.eval_b)
+    # the sides differ in the last option named: with --exchange a --selective holds for both
+    a = dict(common, evaluation=args.eval_a, selective=args.selective, exchange=args.exchange)
+    b = dict(common, evaluation=args.eval_b, selective=args.selective and args.exchange)
     out, _ = summary(*play(args.pairs, a, b, args.opening_plies, args.max_plies, args.seed))
     out.update(a=a, b=b, opening_plies=args.opening_plies, max_plies=args.max_plies, seed=args.seed,
                note="a score over paired openings at equal nodes per move, no Elo claim")

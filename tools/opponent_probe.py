@@ -8,6 +8,8 @@
     python tools/opponent_probe.py --repetition --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2 --opening-plies 40
     python tools/opponent_probe.py --eval positional --budget 150,300,600,1500 --depths 2,3 --max-depth 3 --quiescence 0,2
     python tools/opponent_probe.py --selective --ordering --budget 600,1500,6000 --max-depth 5 --quiescence 0,2
+    python tools/opponent_probe.py --exchange --ordering --budget 600,3000 --max-depth 5 --quiescence 2,6
+    python tools/opponent_probe.py --exchange --ordering --budget 600,3000 --max-depth 5 --quiescence 2,6 --exchange-counts 32
 
 Every slot first plays --opening-plies random plies (the in-slot playout call, seeded words), so the slots hold
 different positions.  Per depth, in depth order: one warm-up launch, then three timed ones (host wall time around the
@@ -31,8 +33,16 @@ another move; the output goes to profiles/opponent_probe_eval.json.  --selective
 run with the SELECTIVE rules of opponent.hpp (null-move pruning, late-move reductions) off and on in the same process,
 the launches alternating; --repetition and --eval then hold for both rows, the selective rows are keyed "... selective"
 and carry the time per node and per launch as ratios to the full-width row of the same run, the mean completed depth of
-both and the share of slots that play another move; the output goes to profiles/opponent_probe_sel.json.  No
-threshold: this is a measurement.
+both and the share of slots that play another move; the output goes to profiles/opponent_probe_sel.json.  --exchange
+(with --ordering and quiescence plies): every budget is run with the EXCHANGE rules of opponent.hpp (delta and exchange
+pruning at the stand-pat nodes) off and on in the same process, the launches alternating; --repetition, --eval and
+--selective then hold for both rows, the pruned rows are keyed "... exchange-pruned" and carry the time per node and per
+launch as ratios to the unpruned row of the same run, the mean completed depth of both and the share of slots that play
+another move; the output goes to profiles/opponent_probe_exc.json.  The kernels do not count what the filter removes;
+--exchange-counts N does, WITHOUT a GPU: the first N slots' positions are rebuilt on the CPU oracle from the same words,
+searched by the restatement tests/exchange_util.py (which the GPU test holds equal to the kernels), and the moves
+removed by each of the two tests per 1000 nodes are added to the pruned rows of the file already written.  No threshold:
+this is a measurement.
 """
 import argparse
 import json
@@ -62,13 +72,22 @@ def main():
                     help="positional: run every --budget with the material and the positional evaluation, alternating")
     ap.add_argument("--selective", action="store_true",
                     help="run every --budget with the selective rules off and on, alternating (needs --ordering)")
+    ap.add_argument("--exchange", action="store_true",
+                    help="run every --budget with delta and exchange pruning off and on, alternating (needs --ordering "
+                         "and --quiescence >= 1)")
+    ap.add_argument("--exchange-counts", type=int, default=0, metavar="N",
+                    help="no GPU: add the moves the two tests remove per 1000 nodes, counted by the CPU restatement "
+                         "on the first N slots, to the pruned rows of --out")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     budgets = [int(b) for b in args.budget.split(",") if b]
     if args.selective and not args.ordering:
         ap.error("--selective needs --ordering")
+    if args.exchange and not (args.ordering and all(int(q) >= 1 for q in args.quiescence.split(","))):
+        ap.error("--exchange needs --ordering and --quiescence >= 1")
     if args.out is None:
         name = ("opponent_probe.json" if not budgets else
+                "opponent_probe_exc.json" if args.exchange else
                 "opponent_probe_sel.json" if args.selective else
                 "opponent_probe_eval.json" if args.evaluation == "positional" else
                 "opponent_probe_rep.json" if args.repetition else
@@ -78,6 +97,8 @@ def main():
     from chessrl_amd import _lib
     from chessrl_amd.gen_data import opening_words
     G = args.games
+    if args.exchange_counts:
+        return exchange_counts(args, budgets, opening_words(random.Random(1), G, args.opening_plies))
     ctx = _lib.Context(G, 1, max_plies=max(64, args.opening_plies + 2))
     words = opening_words(random.Random(1), G, args.opening_plies)
     played, _, _ = ctx.rollout_games(words, np.full(G, words.shape[1], np.int32), 1, args.opening_plies)
@@ -94,7 +115,14 @@ def main():
             kw["node_budget"] = budget
         # the launches of a case alternate between its variants: ordering off and, with --ordering, on
         variants = [(key, kw)]
-        if budget is not None and args.selective:
+        if budget is not None and args.exchange:
+            base = (key + " ordered" + (" repeating-aware" if args.repetition else "") +
+                    (" positional" if args.evaluation == "positional" else "") +
+                    (" selective" if args.selective else ""),
+                    dict(kw, ordering=True, repetition=args.repetition, evaluation=args.evaluation,
+                         selective=args.selective))
+            variants = [base, (base[0] + " exchange-pruned", dict(base[1], exchange=True))]
+        elif budget is not None and args.selective:
             base = (key + " ordered" + (" repeating-aware" if args.repetition else "") +
                     (" positional" if args.evaluation == "positional" else ""),
                     dict(kw, ordering=True, repetition=args.repetition, evaluation=args.evaluation))
@@ -130,7 +158,14 @@ def main():
             if budget is not None:
                 out["depths"][k]["depth_done_histogram"] = np.bincount(last[k][4][searched], minlength=depth + 1).tolist()
             print(k, json.dumps(out["depths"][k]), flush=True)
-        if len(variants) == 2 and args.selective:                      # against the full-width row of this run
+        if len(variants) == 2 and args.exchange:                       # against the unpruned row of this run
+            off, on = out["depths"][variants[0][0]], out["depths"][variants[1][0]]
+            on["time_per_node_ratio_to_unpruned"] = off["nodes_per_s"] / on["nodes_per_s"]
+            on["ms_per_launch_ratio_to_unpruned"] = on["ms_per_launch"] / off["ms_per_launch"]
+            on["share_of_slots_with_another_move"] = float((last[variants[0][0]][0] != last[variants[1][0]][0]).mean())
+            for k, _ in variants:
+                out["depths"][k]["depth_done_mean"] = float(last[k][4][last[k][3] != _lib.OPP_SKIPPED].mean())
+        elif len(variants) == 2 and args.selective:                    # against the full-width row of this run
             off, on = out["depths"][variants[0][0]], out["depths"][variants[1][0]]
             on["time_per_node_ratio_to_full_width"] = off["nodes_per_s"] / on["nodes_per_s"]
             on["ms_per_launch_ratio_to_full_width"] = on["ms_per_launch"] / off["ms_per_launch"]
@@ -154,6 +189,43 @@ def main():
                 out["depths"][variants[1][0]]["answers_equal_unordered"] = bool(same)
     ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+    return 0
+
+
+def exchange_counts(args, budgets, words):
+    """--exchange-counts: what the filter removes, counted by the restatement on the first N slots' positions."""
+    from oracle.chess_oracle import OracleGame
+    from tests import exchange_util as xu
+    from tests import rollout_util as ru
+    with open(args.out) as f:
+        out = json.load(f)
+    games = []
+    for row in words[:args.exchange_counts]:
+        g, w = OracleGame(), iter(int(x) for x in row)
+        ru.run_in_slot(g, lambda: next(w), max_moves=args.opening_plies)
+        games.append(g)
+    for quiescence in (int(q) for q in args.quiescence.split(",")):
+        for budget in budgets:
+            key = ("<=%d@%d+q%d ordered" % (args.max_depth, budget, quiescence) +
+                   (" repeating-aware" if args.repetition else "") +
+                   (" positional" if args.evaluation == "positional" else "") +
+                   (" selective" if args.selective else "") + " exchange-pruned")
+            counts, nodes = xu.new_counts(), 0
+            for g in games:
+                nodes += xu.search(g, args.max_depth, min(budget, args.node_limit), quiescence, args.repetition,
+                                   args.evaluation, args.selective, counts=counts)[2]
+            row = out["depths"][key]
+            row["removed_counted_on"] = {"slots": len(games), "nodes": nodes, "by": "tests/exchange_util.py on the CPU"}
+            row["removed_by_delta_per_1000_nodes"] = 1e3 * counts["delta_removed"] / nodes
+            row["removed_by_exchange_per_1000_nodes"] = 1e3 * counts["exchange_removed"] / nodes
+            row["stand_pat_nodes_per_1000_nodes"] = 1e3 * counts["nodes_4c"] / nodes
+            row["tactical_moves_at_them_per_1000_nodes"] = 1e3 * counts["tactical_moves"] / nodes
+            print(key, json.dumps({k: v for k, v in row.items() if "per_1000" in k or k == "removed_counted_on"}),
+                  flush=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
