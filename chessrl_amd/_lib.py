@@ -4,6 +4,7 @@ There is deliberately NO CPU fallback: if the HIP library is missing or no GPU
 is visible, every entry point raises.  ``build()`` compiles the library in-tree
 with hipcc for gfx950 (works without a GPU: hipcc cross-compiles).
 """
+import collections
 import ctypes
 import hashlib
 import os
@@ -90,36 +91,48 @@ def evaluation_name(evaluation):
     return evaluation
 
 
-def opponent_selective(selective, ordering):
-    """Whether the search is selective (csrc/opponent.hpp, SELECTIVE); a ValueError for one without ordering (which
-    itself needs a node budget)."""
-    if selective and not ordering:
-        raise ValueError("selective needs ordering")
-    return bool(selective)
+class OpponentOptions(collections.namedtuple(
+        "OpponentOptions", "quiescence node_budget ordering repetition evaluation selective exchange")):
+    """The options of the built-in opponent's search (csrc/opponent.hpp) as one value, and the one statement in Python
+    of which of them combine: ``quiescence`` plies past the depth; ``node_budget`` (None: the fixed-depth search);
+    ``ordering`` (ORDERING), ``repetition`` (REPETITION) and ``evaluation`` = "positional" (EVALUATION) on top of a
+    budget; ``selective`` (SELECTIVE) on top of ordering; ``exchange`` (EXCHANGE) on top of ordering and quiescence
+    plies.  A ValueError names the first rule broken, in the order below.  ``ranges=False`` leaves the first two rules
+    to the library, which refuses such a value itself (``Context``'s methods: their callers expect its refusal)."""
+    __slots__ = ()
 
+    def __new__(cls, quiescence=0, node_budget=None, ordering=False, repetition=False, evaluation="material",
+                selective=False, exchange=False, ranges=True):
+        quiescence = int(quiescence)
+        node_budget = None if node_budget is None else int(node_budget)
+        if ranges and not 0 <= quiescence <= OPP_MAX_QUIESCENCE:
+            raise ValueError("quiescence must lie in [0, %d]" % OPP_MAX_QUIESCENCE)
+        if ranges and node_budget is not None and node_budget < 1:
+            raise ValueError("node_budget must be None or at least 1")
+        if ordering and node_budget is None:
+            raise ValueError("ordering needs a node_budget")
+        if repetition and node_budget is None:
+            raise ValueError("repetition needs a node_budget")
+        if evaluation_name(evaluation) != "material" and node_budget is None:
+            raise ValueError("evaluation needs a node_budget")
+        if selective and not ordering:
+            raise ValueError("selective needs ordering")
+        if exchange and not ordering:
+            raise ValueError("exchange needs ordering")
+        if exchange and quiescence < 1:
+            raise ValueError("exchange needs quiescence >= 1")
+        return super().__new__(cls, quiescence, node_budget, bool(ordering), bool(repetition), evaluation,
+                               bool(selective), bool(exchange))
 
-def opponent_exchange(exchange, ordering, node_budget, quiescence):
-    """Whether the quiescence search prunes by delta and exchange (csrc/opponent.hpp, EXCHANGE); a ValueError for one
-    without ordering, without a node budget or without quiescence plies."""
-    if not exchange:
-        return False
-    if not ordering:
-        raise ValueError("exchange needs ordering")
-    if node_budget is None:
-        raise ValueError("ordering needs a node_budget")
-    if int(quiescence) < 1:
-        raise ValueError("exchange needs quiescence >= 1")
-    return True
+    @property
+    def kwargs(self):
+        """The options as the keywords of ``Context.opponent_moves`` and ``Context.sim_reply_opponent``."""
+        return self._asdict()
 
-
-def opponent_evaluation(evaluation, node_budget):
-    """True for "positional", False for "material"; a ValueError for another name and for "positional" without a
-    ``node_budget`` (only the budgeted kernels exist with it)."""
-    if evaluation_name(evaluation) == "material":
-        return False
-    if node_budget is None:
-        raise ValueError("evaluation needs a node_budget")
-    return True
+    def budgeted_args(self, node_limit):
+        """What a ``crl_*_exc`` entry takes between ``quiescence`` and its arrays: the node budget and the five flags."""
+        return (min(self.node_budget, int(node_limit)), int(self.ordering), int(self.repetition),
+                OPP_EVALUATIONS[self.evaluation], int(self.selective), int(self.exchange))
 
 
 ABI_VERSION = 9          # include/chessrl_hip.h: CRL_ABI_VERSION (checked against the loaded library)
@@ -637,67 +650,23 @@ class Context(object):
                            node_budget=None, dev_depth_sum=None, ordering=False, repetition=False,
                            evaluation="material", selective=False, exchange=False):
         """``sim_reply`` with the built-in opponent's move as the reply: device pointers to int32 [count] depths, the
-        planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies; ``quiescence`` plies (0 ..
-        OPP_MAX_QUIESCENCE) past the depth.  ``node_budget`` (not None): iterative deepening up to the depths under
-        ``min(node_budget, node_limit)`` nodes per reply, ``dev_depth_sum`` the int64 [count] accumulator of the
-        completed depths.  ``ordering`` (needs a ``node_budget``): the budgeted search with ORDERING (csrc/opponent.hpp),
-        ``crl_sim_reply_opponent_ord``; False calls the entry it called.  ``repetition`` (needs a ``node_budget``): the
-        budgeted search with REPETITION (a repeated position below the root is a draw), ``crl_sim_reply_opponent_rep``;
-        False calls the entry it called.  ``evaluation`` ("positional" needs a ``node_budget``): the budgeted search with
-        EVALUATION in place of the material evaluation, ``crl_sim_reply_opponent_ev``; "material" calls the entry it
-        called.  ``selective`` (needs ``ordering``): the ordered search with SELECTIVE (null-move pruning and late-move
-        reductions), ``crl_sim_reply_opponent_sel``; False calls the entry it called.  ``exchange`` (needs ``ordering``
-        and ``quiescence`` >= 1): that search with EXCHANGE (delta and exchange pruning at the stand-pat nodes),
-        ``crl_sim_reply_opponent_exc``; False calls the entry it called."""
-        if opponent_exchange(exchange, ordering, node_budget, quiescence):
-            self._ck(self._L.crl_sim_reply_opponent_exc(
-                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)), 1,
-                1 if repetition else 0, 1 if opponent_evaluation(evaluation, node_budget) else 0,
-                1 if opponent_selective(selective, ordering) else 0, 1,
-                ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts),
-                ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_exc")
-            return
-        if opponent_selective(selective, ordering):
-            if node_budget is None:
-                raise ValueError("ordering needs a node_budget")
-            self._ck(self._L.crl_sim_reply_opponent_sel(
-                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)), 1,
-                1 if repetition else 0, 1 if opponent_evaluation(evaluation, node_budget) else 0, 1,
-                ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts),
-                ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_sel")
-            return
-        if opponent_evaluation(evaluation, node_budget):
-            self._ck(self._L.crl_sim_reply_opponent_ev(
-                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)),
-                1 if ordering else 0, 1 if repetition else 0, 1, ctypes.c_void_p(dev_planes_s2),
-                ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts), ctypes.c_void_p(dev_depth_sum)),
-                "crl_sim_reply_opponent_ev")
-            return
-        if repetition:
-            if node_budget is None:
-                raise ValueError("repetition needs a node_budget")
-            self._ck(self._L.crl_sim_reply_opponent_rep(
-                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)),
-                1 if ordering else 0, 1, ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes),
-                ctypes.c_void_p(dev_cuts), ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_rep")
-            return
-        if ordering:
-            if node_budget is None:
-                raise ValueError("ordering needs a node_budget")
-            self._ck(self._L.crl_sim_reply_opponent_ord(
-                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)), 1,
-                ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts),
-                ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_ord")
-            return
-        if node_budget is not None:
-            self._ck(self._L.crl_sim_reply_opponent_id(
-                self._h, ctypes.c_void_p(dev_depths), int(quiescence), min(int(node_budget), int(node_limit)),
-                ctypes.c_void_p(dev_planes_s2), ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts),
-                ctypes.c_void_p(dev_depth_sum)), "crl_sim_reply_opponent_id")
-            return
-        self._ck(self._L.crl_sim_reply_opponent_q(
-            self._h, ctypes.c_void_p(dev_depths), int(quiescence), int(node_limit), ctypes.c_void_p(dev_planes_s2),
-            ctypes.c_void_p(dev_nodes), ctypes.c_void_p(dev_cuts)), "crl_sim_reply_opponent_q")
+        planes of S2 and the int64 / int32 [count] accumulators of nodes and cut replies.  The search is the one the
+        ``OpponentOptions`` of the seven keywords name: without a ``node_budget`` the fixed-depth one
+        (``crl_sim_reply_opponent_q``), with one iterative deepening up to the depths under ``min(node_budget,
+        node_limit)`` nodes per reply (``crl_sim_reply_opponent_exc``), ``dev_depth_sum`` the int64 [count] accumulator
+        of the completed depths."""
+        opts = OpponentOptions(quiescence, node_budget, ordering, repetition, evaluation, selective, exchange,
+                               ranges=False)
+        vp = ctypes.c_void_p
+        if opts.node_budget is None:
+            self._ck(self._L.crl_sim_reply_opponent_q(self._h, vp(dev_depths), opts.quiescence, int(node_limit),
+                                                      vp(dev_planes_s2), vp(dev_nodes), vp(dev_cuts)),
+                     "crl_sim_reply_opponent_q")
+        else:
+            self._ck(self._L.crl_sim_reply_opponent_exc(self._h, vp(dev_depths), opts.quiescence,
+                                                        *opts.budgeted_args(node_limit), vp(dev_planes_s2),
+                                                        vp(dev_nodes), vp(dev_cuts), vp(dev_depth_sum)),
+                     "crl_sim_reply_opponent_exc")
 
     def sim_backup(self, dev_policy_s2, dev_value_s2):
         self._ck(self._L.crl_sim_backup(self._h, ctypes.c_void_p(dev_policy_s2),
@@ -830,79 +799,30 @@ class Context(object):
     # ---- the built-in opponent (csrc/opponent.hpp; stockfish.py:23-31, gamestockfish.py:27-41) ------
     def opponent_moves(self, depths, push=False, node_limit=OPP_NODE_LIMIT, quiescence=0, node_budget=None,
                        ordering=False, repetition=False, evaluation="material", selective=False, exchange=False):
-        """Fixed-depth alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it,
-        with ``quiescence`` plies (0 .. OPP_MAX_QUIESCENCE, one value per call) of quiescence search past the depth.
-        Returns (moves u16, scores i32, nodes i64, flags u8); with ``push`` the moves are played.  ``node_budget`` (not
-        None): iterative deepening, ``depths`` the maximum depths, under ``min(node_budget, node_limit)`` nodes per
-        slot; returns (moves, scores, nodes, flags, depths_done i32).  ``ordering`` (needs a ``node_budget``): that
-        search with ORDERING (csrc/opponent.hpp: victims first, then the killer moves of the ply), through
-        ``crl_opponent_moves_ord``; False calls the entry it called.  ``repetition`` (needs a ``node_budget``): that
-        search with REPETITION (a position below the root that occurred before, on the path or in the slot's reversible
-        history, is worth 0), through ``crl_opponent_moves_rep``; False calls the entry it called.  ``evaluation``
-        ("positional" needs a ``node_budget``): that search with EVALUATION (csrc/opponent.hpp: pawn structure,
-        mobility, files, king safety, tapered) in place of the material evaluation, through ``crl_opponent_moves_ev``;
-        "material" calls the entry it called.  ``selective`` (needs ``ordering``): the ordered search with SELECTIVE
-        (csrc/opponent.hpp: null-move pruning and late-move reductions), through ``crl_opponent_moves_sel``; False
-        calls the entry it called.  ``exchange`` (needs ``ordering`` and ``quiescence`` >= 1): that search with EXCHANGE
-        (csrc/opponent.hpp: at a quiescence node that stands pat, captures that cannot come near alpha or lose
-        material on their square are not searched), through ``crl_opponent_moves_exc``; False calls the entry it
-        called."""
-        selective = opponent_selective(selective, ordering)
-        exchange = opponent_exchange(exchange, ordering, node_budget, quiescence)
-        if ordering and node_budget is None:
-            raise ValueError("ordering needs a node_budget")
-        if repetition and node_budget is None:
-            raise ValueError("repetition needs a node_budget")
-        positional = opponent_evaluation(evaluation, node_budget)
+        """Alpha-beta per slot of the window: ``depths[g]`` = 0 leaves slot g alone, 1..5 searches it, with the search
+        the ``OpponentOptions`` of the seven keywords name (one value of each per call).  Without a ``node_budget``:
+        the fixed-depth search (``crl_opponent_moves_q``); returns (moves u16, scores i32, nodes i64, flags u8).  With
+        one: iterative deepening, ``depths`` the maximum depths, under ``min(node_budget, node_limit)`` nodes per slot
+        (``crl_opponent_moves_exc``); returns (moves, scores, nodes, flags, depths_done i32).  With ``push`` the moves
+        are played."""
+        opts = OpponentOptions(quiescence, node_budget, ordering, repetition, evaluation, selective, exchange,
+                               ranges=False)
         dp = np.ascontiguousarray(depths, dtype=np.int32)
         assert dp.shape == (self.G,)
         moves = np.zeros(self.G, np.uint16)
         scores = np.zeros(self.G, np.int32)
         nodes = np.zeros(self.G, np.int64)
         flags = np.zeros(self.G, np.uint8)
-        if node_budget is not None:
-            done = np.zeros(self.G, np.int32)
-            if exchange:
-                self._ck(self._L.crl_opponent_moves_exc(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
-                                                        min(int(node_budget), int(node_limit)), 1,
-                                                        1 if repetition else 0, 1 if positional else 0,
-                                                        1 if selective else 0, 1, _ptr(moves), _ptr(scores),
-                                                        _ptr(nodes), _ptr(flags), _ptr(done)),
-                         "crl_opponent_moves_exc")
-                return moves, scores, nodes, flags, done
-            if selective:
-                self._ck(self._L.crl_opponent_moves_sel(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
-                                                        min(int(node_budget), int(node_limit)), 1,
-                                                        1 if repetition else 0, 1 if positional else 0, 1, _ptr(moves),
-                                                        _ptr(scores), _ptr(nodes), _ptr(flags), _ptr(done)),
-                         "crl_opponent_moves_sel")
-                return moves, scores, nodes, flags, done
-            if positional:
-                self._ck(self._L.crl_opponent_moves_ev(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
-                                                       min(int(node_budget), int(node_limit)), 1 if ordering else 0,
-                                                       1 if repetition else 0, 1, _ptr(moves), _ptr(scores),
-                                                       _ptr(nodes), _ptr(flags), _ptr(done)), "crl_opponent_moves_ev")
-                return moves, scores, nodes, flags, done
-            if repetition:
-                self._ck(self._L.crl_opponent_moves_rep(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
-                                                        min(int(node_budget), int(node_limit)), 1 if ordering else 0, 1,
-                                                        _ptr(moves), _ptr(scores), _ptr(nodes), _ptr(flags), _ptr(done)),
-                         "crl_opponent_moves_rep")
-                return moves, scores, nodes, flags, done
-            if ordering:
-                self._ck(self._L.crl_opponent_moves_ord(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
-                                                        min(int(node_budget), int(node_limit)), 1, _ptr(moves),
-                                                        _ptr(scores), _ptr(nodes), _ptr(flags), _ptr(done)),
-                         "crl_opponent_moves_ord")
-                return moves, scores, nodes, flags, done
-            self._ck(self._L.crl_opponent_moves_id(self._h, _ptr(dp), int(quiescence), 1 if push else 0,
-                                                   min(int(node_budget), int(node_limit)), _ptr(moves), _ptr(scores),
-                                                   _ptr(nodes), _ptr(flags), _ptr(done)), "crl_opponent_moves_id")
-            return moves, scores, nodes, flags, done
-        self._ck(self._L.crl_opponent_moves_q(self._h, _ptr(dp), int(quiescence), 1 if push else 0, int(node_limit),
-                                              _ptr(moves), _ptr(scores), _ptr(nodes), _ptr(flags)),
-                 "crl_opponent_moves_q")
-        return moves, scores, nodes, flags
+        if opts.node_budget is None:
+            self._ck(self._L.crl_opponent_moves_q(self._h, _ptr(dp), opts.quiescence, 1 if push else 0,
+                                                  int(node_limit), _ptr(moves), _ptr(scores), _ptr(nodes),
+                                                  _ptr(flags)), "crl_opponent_moves_q")
+            return moves, scores, nodes, flags
+        done = np.zeros(self.G, np.int32)
+        self._ck(self._L.crl_opponent_moves_exc(self._h, _ptr(dp), opts.quiescence, 1 if push else 0,
+                                                *opts.budgeted_args(node_limit), _ptr(moves), _ptr(scores),
+                                                _ptr(nodes), _ptr(flags), _ptr(done)), "crl_opponent_moves_exc")
+        return moves, scores, nodes, flags, done
 
     def opponent_evaluate(self, evaluation="material"):
         """The static evaluation (int32 [G], from the side to move) of every window slot's current position:

@@ -51,9 +51,9 @@ def _load_model(model_dir):
     return ChessModel(weights=path if os.path.exists(path) else None)
 
 
-def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence=0, budget=None,
-                 ordering=False, repetition=False, evaluation="material", selective=False, exchange=False):
-    """(moves, plies, results) of the games with ``Agent.best_move(real_game=True)`` on the agent's plies."""
+def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, opts=_lib.OpponentOptions()):
+    """(moves, plies, results) of the games with ``Agent.best_move(real_game=True)`` on the agent's plies; ``opts``:
+    the opponent's ``OpponentOptions``."""
     import torch
     ctx = _lib.Context(games, 1, max_plies=max(max_plies, 2), device=dev.index or 0)
     try:
@@ -72,32 +72,25 @@ def _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quie
                 policy = model(planes)[0].float().contiguous()
                 ctx.greedy_moves(policy.data_ptr(), mask=agent_turn, push=True, want_moves=False)
             if opp_turn.any():
-                ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True, quiescence=quiescence,
-                                   node_budget=budget, ordering=ordering, repetition=repetition,
-                                   evaluation=evaluation, selective=selective, exchange=exchange)
+                ctx.opponent_moves(np.where(opp_turn, int(opponent_depth), 0), push=True, **opts.kwargs)
             results = ctx.results()
         return ctx.records()
     finally:
         ctx.close()
 
 
-def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, quiescence=0, budget=None,
-                 ordering=False, repetition=False, evaluation="material", selective=False, exchange=False):
+def _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, opts=_lib.OpponentOptions()):
     """(moves, plies, results) of the games with ``sims`` simulations per move against the opponent's replies.  A game
     is searched while it runs and has fewer than ``max_plies`` plies; a move adds two plies (one if it ends the game),
     so a game may end one ply past ``max_plies``."""
     from .engine import LockstepEngine, choose_children
     from .opponent import MinimaxPlayer
     eng = LockstepEngine(model, games, sims, device=dev.index or 0, max_plies=max_plies + 2,
-                         reply=MinimaxPlayer(False, search_depth=opponent_depth, quiescence=quiescence,
-                                             node_budget=budget, ordering=ordering, repetition=repetition,
-                                             evaluation=evaluation, selective=selective, exchange=exchange))
+                         reply=MinimaxPlayer(False, search_depth=opponent_depth, **opts.kwargs))
     try:
         ctx = eng.ctx
         if not agent_white.all():                            # gamestockfish.py:31-33: the opponent opens as white
-            ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True, quiescence=quiescence,
-                               node_budget=budget, ordering=ordering, repetition=repetition, evaluation=evaluation,
-                               selective=selective, exchange=exchange)
+            ctx.opponent_moves(np.where(agent_white, 0, int(opponent_depth)), push=True, **opts.kwargs)
         while True:
             _, plies, results = ctx.records(with_moves=False)
             live = (results == _lib.RESULT_NONE) & (plies < max_plies)
@@ -140,16 +133,10 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     budget = None if opponent_budget is None else int(opponent_budget)
     if budget is not None and budget < 1:
         raise ValueError("opponent_budget must be None or at least 1")
-    ordering = bool(opponent_ordering)
-    if ordering and budget is None:
+    if opponent_ordering and budget is None:
         raise ValueError("opponent_ordering needs an opponent_budget")
-    repetition = bool(opponent_repetition)
-    if repetition and budget is None:
-        raise ValueError("repetition needs a node_budget")
-    evaluation = _lib.evaluation_name(opponent_evaluation)
-    positional = _lib.opponent_evaluation(evaluation, budget)
-    selective = _lib.opponent_selective(opponent_selective, ordering)
-    exchange = _lib.opponent_exchange(opponent_exchange, ordering, budget, quiescence)
+    opts = _lib.OpponentOptions(quiescence, budget, opponent_ordering, opponent_repetition, opponent_evaluation,
+                                opponent_selective, opponent_exchange)
     sims = int(sims)
     if sims < 0:
         raise ValueError("sims must be 0 (the greedy agent) or the number of simulations per move")
@@ -164,12 +151,9 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
     dev = torch.device(dev)
     agent_white = np.array(colors, dtype=bool)
     if sims > 0:
-        moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims,
-                                             quiescence, budget, ordering, repetition, evaluation, selective,
-                                             exchange)
+        moves, plies, results = _play_search(model, dev, games, opponent_depth, max_plies, agent_white, sims, opts)
     else:
-        moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, quiescence,
-                                             budget, ordering, repetition, evaluation, selective, exchange)
+        moves, plies, results = _play_greedy(model, dev, games, opponent_depth, max_plies, agent_white, opts)
     res = [None if r == _lib.RESULT_NONE else int(r) for r in results]
     out = tally(colors, res)
     out["games"] = [[move_to_uci(m) for m in moves[i, :plies[i]]] for i in range(games)]
@@ -180,11 +164,11 @@ def benchmark(model_dir, workers=1, games=10, opponent_depth=2, log=False, seed=
                   % (opponent_depth, ", quiescence %d" % quiescence if quiescence else ""))
         else:
             print("Against the built-in opponent, depth <= %d within %d nodes per move%s%s%s%s%s%s (not Stockfish, no Elo)"
-                  % (opponent_depth, budget, ", ordered" if ordering else "",
-                     ", repetition-aware" if repetition else "",
+                  % (opponent_depth, budget, ", ordered" if opts.ordering else "",
+                     ", repetition-aware" if opts.repetition else "",
                      ", quiescence %d" % quiescence if quiescence else "",
-                     ", positional evaluation" if positional else "", ", selective" if selective else "",
-                     ", exchange-pruned" if exchange else ""))
+                     ", positional evaluation" if opts.evaluation == "positional" else "",
+                     ", selective" if opts.selective else "", ", exchange-pruned" if opts.exchange else ""))
         if sims > 0:
             print("agent: MCTS, %d simulations per move" % sims)
         print("Games played: %d" % out["played"])

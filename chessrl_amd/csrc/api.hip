@@ -843,85 +843,70 @@ int crl_sim_reply_opponent(crl_ctx *ctx, const int32_t *dev_depths_i32, int64_t 
 }
 
 // ITERATIVE DEEPENING under a node budget (csrc/opponent.hpp): kernels of their own, so the calls above launch what
-// they launched
-// (ordering = 1: ORDERING of csrc/opponent.hpp, the _ido kernels; 0 launches the _id kernels, whoever calls;
-// repetition = 1: REPETITION, the _idr / _idor kernels; 0 launches what the call launched without it;
-// evaluation = CRL_OPP_EVAL_POSITIONAL: EVALUATION, the k_opponent_moves_ev / k_reply_opponent_ev kernels of the same
-// shape; CRL_OPP_EVAL_MATERIAL launches what the call launched without it)
-using MovesEvKernel = void (*)(Dev, const int32_t *, int, int, long long, u16 *, int32_t *, long long *, uint8_t *,
-                               int32_t *);
-using ReplyEvKernel = void (*)(Dev, const int32_t *, int, long long, void *, unsigned long long *, uint32_t *,
-                               unsigned long long *);
-static MovesEvKernel moves_ev_kernel(bool qs, bool ord, bool rep)
+// they launched.  Every budgeted entry point of a family is one body, and the options choose the instantiation of the
+// family's kernel template, k_opponent_moves_id / k_reply_opponent_id<QS, ORD, REP, POS, SEL, EXC>: QS = quiescence > 0,
+// ORD = ordering, REP = repetition, POS = evaluation is CRL_OPP_EVAL_POSITIONAL, SEL = selective, EXC = exchange.  An
+// option an entry point does not have is 0 there.
+extern "C++" {
+struct MovesIdFamily {
+    using Kernel = void (*)(Dev, const int32_t *, int, int, long long, u16 *, int32_t *, long long *, uint8_t *,
+                            int32_t *);
+    template <bool... F> static constexpr Kernel kernel() { return k_opponent_moves_id<F...>; }
+};
+struct ReplyIdFamily {
+    using Kernel = void (*)(Dev, const int32_t *, int, long long, void *, unsigned long long *, uint32_t *,
+                            unsigned long long *);
+    template <bool... F> static constexpr Kernel kernel() { return k_reply_opponent_id<F...>; }
+};
+
+// the family's kernel of shape I (the OPP_SHAPE_* bits of csrc/opponent.hpp); nullptr where opp_shape_legal says no
+template <class Family, unsigned I>
+static constexpr typename Family::Kernel shape_kernel()
 {
-    static const MovesEvKernel t[8] = {
-        k_opponent_moves_ev<false, false, false>, k_opponent_moves_ev<true, false, false>,
-        k_opponent_moves_ev<false, true, false>,  k_opponent_moves_ev<true, true, false>,
-        k_opponent_moves_ev<false, false, true>,  k_opponent_moves_ev<true, false, true>,
-        k_opponent_moves_ev<false, true, true>,   k_opponent_moves_ev<true, true, true>};
-    return t[(rep ? 4 : 0) | (ord ? 2 : 0) | (qs ? 1 : 0)];
+    if constexpr (opp_shape_legal(I))
+        return Family::template kernel<(I & OPP_SHAPE_QS) != 0, (I & OPP_SHAPE_ORD) != 0, (I & OPP_SHAPE_REP) != 0,
+                                       (I & OPP_SHAPE_POS) != 0, (I & OPP_SHAPE_SEL) != 0, (I & OPP_SHAPE_EXC) != 0>();
+    else
+        return nullptr;
 }
-static ReplyEvKernel reply_ev_kernel(bool qs, bool ord, bool rep)
+template <class Family, unsigned... I>
+static typename Family::Kernel shape_kernel(unsigned shape, std::integer_sequence<unsigned, I...>)
 {
-    static const ReplyEvKernel t[8] = {
-        k_reply_opponent_ev<false, false, false>, k_reply_opponent_ev<true, false, false>,
-        k_reply_opponent_ev<false, true, false>,  k_reply_opponent_ev<true, true, false>,
-        k_reply_opponent_ev<false, false, true>,  k_reply_opponent_ev<true, false, true>,
-        k_reply_opponent_ev<false, true, true>,   k_reply_opponent_ev<true, true, true>};
-    return t[(rep ? 4 : 0) | (ord ? 2 : 0) | (qs ? 1 : 0)];
+    static const typename Family::Kernel t[OPP_SHAPES] = {shape_kernel<Family, I>()...};
+    return t[shape];
 }
 
-// selective = 1: SELECTIVE, the k_opponent_moves_sel / k_reply_opponent_sel kernels of the same shape (ordering is on)
-static MovesEvKernel moves_sel_kernel(bool qs, bool rep, bool pos)
+// the argument condition both families share: the flags are 0 or 1, the evaluation is one of the two, selective needs
+// ordering, exchange needs ordering and quiescence >= 1 (the range of quiescence is the caller's to refuse)
+static bool opponent_options_ok(int quiescence, int ordering, int repetition, int evaluation, int selective,
+                                int exchange)
 {
-    static const MovesEvKernel t[8] = {
-        k_opponent_moves_sel<false, false, false>, k_opponent_moves_sel<true, false, false>,
-        k_opponent_moves_sel<false, true, false>,  k_opponent_moves_sel<true, true, false>,
-        k_opponent_moves_sel<false, false, true>,  k_opponent_moves_sel<true, false, true>,
-        k_opponent_moves_sel<false, true, true>,   k_opponent_moves_sel<true, true, true>};
-    return t[(pos ? 4 : 0) | (rep ? 2 : 0) | (qs ? 1 : 0)];
-}
-static ReplyEvKernel reply_sel_kernel(bool qs, bool rep, bool pos)
-{
-    static const ReplyEvKernel t[8] = {
-        k_reply_opponent_sel<false, false, false>, k_reply_opponent_sel<true, false, false>,
-        k_reply_opponent_sel<false, true, false>,  k_reply_opponent_sel<true, true, false>,
-        k_reply_opponent_sel<false, false, true>,  k_reply_opponent_sel<true, false, true>,
-        k_reply_opponent_sel<false, true, true>,   k_reply_opponent_sel<true, true, true>};
-    return t[(pos ? 4 : 0) | (rep ? 2 : 0) | (qs ? 1 : 0)];
+    return (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1) &&
+           (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL) &&
+           (selective == 0 || (selective == 1 && ordering == 1)) &&
+           (exchange == 0 || (exchange == 1 && ordering == 1 && quiescence >= 1));
 }
 
-// exchange = 1: EXCHANGE, the k_opponent_moves_exc / k_reply_opponent_exc kernels of the same shape (ordering is on and
-// quiescence >= 1)
-static MovesEvKernel moves_exc_kernel(bool rep, bool pos, bool sel)
+// (after opponent_options_ok and the range of quiescence: the shape is legal, the kernel is there)
+template <class Family>
+static typename Family::Kernel opponent_kernel(int quiescence, int ordering, int repetition, int evaluation,
+                                               int selective, int exchange)
 {
-    static const MovesEvKernel t[8] = {
-        k_opponent_moves_exc<false, false, false>, k_opponent_moves_exc<true, false, false>,
-        k_opponent_moves_exc<false, true, false>,  k_opponent_moves_exc<true, true, false>,
-        k_opponent_moves_exc<false, false, true>,  k_opponent_moves_exc<true, false, true>,
-        k_opponent_moves_exc<false, true, true>,   k_opponent_moves_exc<true, true, true>};
-    return t[(sel ? 4 : 0) | (pos ? 2 : 0) | (rep ? 1 : 0)];
+    const unsigned shape = (quiescence > 0 ? OPP_SHAPE_QS : 0) | (ordering ? OPP_SHAPE_ORD : 0) |
+                           (repetition ? OPP_SHAPE_REP : 0) |
+                           (evaluation == CRL_OPP_EVAL_POSITIONAL ? OPP_SHAPE_POS : 0) |
+                           (selective ? OPP_SHAPE_SEL : 0) | (exchange ? OPP_SHAPE_EXC : 0);
+    return shape_kernel<Family>(shape, std::make_integer_sequence<unsigned, OPP_SHAPES>());
 }
-static ReplyEvKernel reply_exc_kernel(bool rep, bool pos, bool sel)
-{
-    static const ReplyEvKernel t[8] = {
-        k_reply_opponent_exc<false, false, false>, k_reply_opponent_exc<true, false, false>,
-        k_reply_opponent_exc<false, true, false>,  k_reply_opponent_exc<true, true, false>,
-        k_reply_opponent_exc<false, false, true>,  k_reply_opponent_exc<true, false, true>,
-        k_reply_opponent_exc<false, true, true>,   k_reply_opponent_exc<true, true, true>};
-    return t[(sel ? 4 : 0) | (pos ? 2 : 0) | (rep ? 1 : 0)];
-}
+}  // extern "C++"
 
 static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depths, int quiescence, int push,
                              int64_t node_budget, int ordering, int repetition, int evaluation, uint16_t *moves,
                              int32_t *scores, int64_t *nodes, uint8_t *flags, int32_t *depths_done, int selective = 0,
                              int exchange = 0)
 {
-    ENTER(ctx, depths && moves && node_budget >= 1 && (ordering == 0 || ordering == 1) &&
-                   (repetition == 0 || repetition == 1) &&
-                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL) &&
-                   (selective == 0 || (selective == 1 && ordering == 1)) &&
-                   (exchange == 0 || (exchange == 1 && ordering == 1 && quiescence >= 1)));
+    ENTER(ctx, depths && moves && node_budget >= 1 &&
+                   opponent_options_ok(quiescence, ordering, repetition, evaluation, selective, exchange));
     if (quiescence < 0 || quiescence > CRL_OPP_MAX_QUIESCENCE)
         return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a quiescence outside 0 .. CRL_OPP_MAX_QUIESCENCE");
     const size_t G = ctx->W;
@@ -930,42 +915,9 @@ static int opponent_moves_id(crl_ctx *ctx, const char *who, const int32_t *depth
             return fail(ctx, CRL_ERR_ARG, std::string(who) + ": a depth outside 0 .. CRL_OPP_MAX_DEPTH");
     long long *dnodes = (long long *)ctx->t_f64;          // [G] of the [G][256] doubles
     HIP_TRY(ctx, to_dev(ctx, ctx->t_i32b, depths, G));
-    if (exchange)
-        LAUNCH(ctx, moves_exc_kernel(repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL, selective != 0), ctx->d,
-               (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes,
-               ctx->t_u8, ctx->t_i32d);
-    else if (selective)
-        LAUNCH(ctx, moves_sel_kernel(quiescence > 0, repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL), ctx->d,
-               (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes,
-               ctx->t_u8, ctx->t_i32d);
-    else if (evaluation == CRL_OPP_EVAL_POSITIONAL)
-        LAUNCH(ctx, moves_ev_kernel(quiescence > 0, ordering != 0, repetition != 0), ctx->d,
-               (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes,
-               ctx->t_u8, ctx->t_i32d);
-    else if (repetition && ordering && quiescence > 0)
-        LAUNCH(ctx, k_opponent_moves_idor_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
-               (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
-    else if (repetition && ordering)
-        LAUNCH(ctx, k_opponent_moves_idor, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_budget,
-               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
-    else if (repetition && quiescence > 0)
-        LAUNCH(ctx, k_opponent_moves_idr_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
-               (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
-    else if (repetition)
-        LAUNCH(ctx, k_opponent_moves_idr, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_budget,
-               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
-    else if (ordering && quiescence > 0)
-        LAUNCH(ctx, k_opponent_moves_ido_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
-               (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
-    else if (ordering)
-        LAUNCH(ctx, k_opponent_moves_ido, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_budget,
-               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
-    else if (quiescence > 0)
-        LAUNCH(ctx, k_opponent_moves_id_q, ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push,
-               (long long)node_budget, ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
-    else
-        LAUNCH(ctx, k_opponent_moves_id, ctx->d, (const int32_t *)ctx->t_i32b, push, (long long)node_budget,
-               ctx->t_u16a, ctx->t_i32c, dnodes, ctx->t_u8, ctx->t_i32d);
+    LAUNCH(ctx, opponent_kernel<MovesIdFamily>(quiescence, ordering, repetition, evaluation, selective, exchange),
+           ctx->d, (const int32_t *)ctx->t_i32b, quiescence, push, (long long)node_budget, ctx->t_u16a, ctx->t_i32c,
+           dnodes, ctx->t_u8, ctx->t_i32d);
     HIP_TRY(ctx, to_host(ctx, moves, ctx->t_u16a, G));
     HIP_TRY(ctx, to_host(ctx, scores, ctx->t_i32c, G));
     HIP_TRY(ctx, to_host(ctx, (long long *)nodes, dnodes, G));
@@ -1042,114 +994,69 @@ int crl_opponent_evaluate(crl_ctx *ctx, int evaluation, int32_t *scores)
     return check_dev_error(ctx);
 }
 
-int crl_sim_reply_opponent_rep(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
-                               int ordering, int repetition, void *dev_planes_s2, uint64_t *dev_nodes_u64,
-                               uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
+// the budgeted reply of a search step: the counterpart of opponent_moves_id (device pointers only, as
+// crl_sim_reply_opponent_q)
+static int reply_opponent_id(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                             int ordering, int repetition, int evaluation, int selective, int exchange,
+                             void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                             uint64_t *dev_depth_sum_u64)
 {
     ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
                    node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
-                   (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1));
-    if (repetition && ordering && quiescence > 0)
-        LAUNCH(ctx, k_reply_opponent_idor_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
-               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    else if (repetition && ordering)
-        LAUNCH(ctx, k_reply_opponent_idor, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
-               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    else if (repetition && quiescence > 0)
-        LAUNCH(ctx, k_reply_opponent_idr_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
-               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    else if (repetition)
-        LAUNCH(ctx, k_reply_opponent_idr, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
-               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    else if (ordering && quiescence > 0)
-        LAUNCH(ctx, k_reply_opponent_ido_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
-               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    else if (ordering)
-        LAUNCH(ctx, k_reply_opponent_ido, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
-               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    else if (quiescence > 0)
-        LAUNCH(ctx, k_reply_opponent_id_q, ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
-               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    else
-        LAUNCH(ctx, k_reply_opponent_id, ctx->d, dev_depths_i32, (long long)node_budget, dev_planes_s2,
-               (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
+                   opponent_options_ok(quiescence, ordering, repetition, evaluation, selective, exchange));
+    LAUNCH(ctx, opponent_kernel<ReplyIdFamily>(quiescence, ordering, repetition, evaluation, selective, exchange),
+           ctx->d, dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2,
+           (unsigned long long *)dev_nodes_u64, dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
     return CRL_OK;
-}
-
-// evaluation = CRL_OPP_EVAL_MATERIAL is the _rep call; CRL_OPP_EVAL_POSITIONAL launches the k_reply_opponent_ev kernel
-// of the same shape
-int crl_sim_reply_opponent_ev(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
-                              int ordering, int repetition, int evaluation, void *dev_planes_s2,
-                              uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
-{
-    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
-                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
-                   (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1) &&
-                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL));
-    if (evaluation == CRL_OPP_EVAL_MATERIAL)
-        return crl_sim_reply_opponent_rep(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition,
-                                          dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
-    LAUNCH(ctx, reply_ev_kernel(quiescence > 0, ordering != 0, repetition != 0), ctx->d, dev_depths_i32, quiescence,
-           (long long)node_budget, dev_planes_s2, (unsigned long long *)dev_nodes_u64, dev_cuts_u32,
-           (unsigned long long *)dev_depth_sum_u64);
-    return CRL_OK;
-}
-
-// selective = 0 is the _ev call; 1 (it needs ordering) launches the k_reply_opponent_sel kernel of the same shape
-int crl_sim_reply_opponent_sel(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
-                               int ordering, int repetition, int evaluation, int selective, void *dev_planes_s2,
-                               uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
-{
-    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
-                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
-                   (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1) &&
-                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL) &&
-                   (selective == 0 || (selective == 1 && ordering == 1)));
-    if (!selective)
-        return crl_sim_reply_opponent_ev(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, evaluation,
-                                         dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
-    LAUNCH(ctx, reply_sel_kernel(quiescence > 0, repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL), ctx->d,
-           dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2, (unsigned long long *)dev_nodes_u64,
-           dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    return CRL_OK;
-}
-
-// exchange = 0 is the _sel call; 1 (it needs ordering and quiescence >= 1) launches the k_reply_opponent_exc kernel of
-// the same shape
-int crl_sim_reply_opponent_exc(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
-                               int ordering, int repetition, int evaluation, int selective, int exchange,
-                               void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
-                               uint64_t *dev_depth_sum_u64)
-{
-    ENTER(ctx, dev_depths_i32 && dev_planes_s2 && dev_nodes_u64 && dev_cuts_u32 && dev_depth_sum_u64 &&
-                   node_budget >= 1 && quiescence >= 0 && quiescence <= CRL_OPP_MAX_QUIESCENCE &&
-                   (ordering == 0 || ordering == 1) && (repetition == 0 || repetition == 1) &&
-                   (evaluation == CRL_OPP_EVAL_MATERIAL || evaluation == CRL_OPP_EVAL_POSITIONAL) &&
-                   (selective == 0 || (selective == 1 && ordering == 1)) &&
-                   (exchange == 0 || (exchange == 1 && ordering == 1 && quiescence >= 1)));
-    if (!exchange)
-        return crl_sim_reply_opponent_sel(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, evaluation,
-                                          selective, dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
-    LAUNCH(ctx, reply_exc_kernel(repetition != 0, evaluation == CRL_OPP_EVAL_POSITIONAL, selective != 0), ctx->d,
-           dev_depths_i32, quiescence, (long long)node_budget, dev_planes_s2, (unsigned long long *)dev_nodes_u64,
-           dev_cuts_u32, (unsigned long long *)dev_depth_sum_u64);
-    return CRL_OK;
-}
-
-int crl_sim_reply_opponent_ord(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
-                               int ordering, void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
-                               uint64_t *dev_depth_sum_u64)
-{
-    return crl_sim_reply_opponent_rep(ctx, dev_depths_i32, quiescence, node_budget, ordering, 0, dev_planes_s2,
-                                      dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
 }
 
 int crl_sim_reply_opponent_id(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
                               void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
                               uint64_t *dev_depth_sum_u64)
 {
-    return crl_sim_reply_opponent_ord(ctx, dev_depths_i32, quiescence, node_budget, 0, dev_planes_s2, dev_nodes_u64,
-                                      dev_cuts_u32, dev_depth_sum_u64);
+    return reply_opponent_id(ctx, dev_depths_i32, quiescence, node_budget, 0, 0, 0, 0, 0, dev_planes_s2, dev_nodes_u64,
+                             dev_cuts_u32, dev_depth_sum_u64);
+}
+
+int crl_sim_reply_opponent_ord(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                               uint64_t *dev_depth_sum_u64)
+{
+    return reply_opponent_id(ctx, dev_depths_i32, quiescence, node_budget, ordering, 0, 0, 0, 0, dev_planes_s2,
+                             dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
+}
+
+int crl_sim_reply_opponent_rep(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, int repetition, void *dev_planes_s2, uint64_t *dev_nodes_u64,
+                               uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
+{
+    return reply_opponent_id(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, 0, 0, 0,
+                             dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
+}
+
+int crl_sim_reply_opponent_ev(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                              int ordering, int repetition, int evaluation, void *dev_planes_s2,
+                              uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
+{
+    return reply_opponent_id(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, evaluation, 0, 0,
+                             dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
+}
+
+int crl_sim_reply_opponent_sel(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, int repetition, int evaluation, int selective, void *dev_planes_s2,
+                               uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64)
+{
+    return reply_opponent_id(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, evaluation, selective,
+                             0, dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
+}
+
+int crl_sim_reply_opponent_exc(crl_ctx *ctx, const int32_t *dev_depths_i32, int quiescence, int64_t node_budget,
+                               int ordering, int repetition, int evaluation, int selective, int exchange,
+                               void *dev_planes_s2, uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32,
+                               uint64_t *dev_depth_sum_u64)
+{
+    return reply_opponent_id(ctx, dev_depths_i32, quiescence, node_budget, ordering, repetition, evaluation, selective,
+                             exchange, dev_planes_s2, dev_nodes_u64, dev_cuts_u32, dev_depth_sum_u64);
 }
 
 // ---- threads > 1: virtual-loss waves (csrc/search_wave.hpp) -----------------------------------------------------

@@ -75,7 +75,7 @@
 // `push`, the chosen move is pushed through game_push: history, record, ply and result change exactly as by
 // crl_push_moves, repetition included.
 //
-// ITERATIVE DEEPENING (the _id kernels only; every other launch is the text above and nothing else).  Per slot:
+// ITERATIVE DEEPENING (the _id kernel templates only; every other launch is the text above and nothing else).  Per slot:
 // D = depths[slot], now the MAXIMUM depth, 1 .. CRL_OPP_MAX_DEPTH; B >= 1, the node budget of the call; Q as above.
 //     One node counter runs across all iterations of the slot.  It counts wave_movegen calls as above; the root is
 //     generated again at the start of every iteration and counted each time.  The counter is tested before every node:
@@ -99,7 +99,7 @@
 // best move), not a loop of its own, so a logic error still ends as a flagged cut.  The move-to-front is one ballot per
 // 64 moves and a shift by one lane.  (tests/iterdeep_util.py restates this section.)
 //
-// ORDERING (the _ido kernels only; it requires ITERATIVE DEEPENING, and everything in that section holds, the root's
+// ORDERING (the ORD shapes of the _id kernels only; it requires ITERATIVE DEEPENING, and everything in that section holds, the root's
 // order included: generation order with the previous iteration's best moved to the front).
 //     Move order below the root.  At every node at ply k >= 1 that searches moves the order is a stable partition into
 //     NINE classes, generation order inside each class:
@@ -117,7 +117,7 @@
 //     A node that stands pat searches tactical moves only, so it never sets a killer; the root never sets one.
 //     Nothing else changes: fail-soft, the strictly-greater rule, the windows, one wave_movegen per turn, the budget
 //     tested before every node, the cut rules, depth_done and CRL_OPP_CUT.
-// Consequence.  With a budget nothing reaches, move, score, flag and depth_done are those of the _id search (each
+// Consequence.  With a budget nothing reaches, move, score, flag and depth_done are those of the search without ORD (each
 // iteration returns the minimax pair of its root order, and the root order does not depend on what lies below it); only
 // `nodes` differs.  Under a budget that cuts, all five may differ.  Both searches stay a function of the board and the
 // settings alone.  Structure: the killers of ply k and the number of tactical moves of the node live in the pad words
@@ -127,7 +127,7 @@
 // cursor, best and alpha.  The partition is the seven ballots of 4c per 64 moves and two more that find the killers: a
 // killer class holds at most one move.  (tests/ordering_util.py restates this section.)
 //
-// REPETITION (the _idr and _idor kernels only; it requires ITERATIVE DEEPENING, so a node budget, and everything in
+// REPETITION (the REP shapes of the _id kernels only; it requires ITERATIVE DEEPENING, so a node budget, and everything in
 // ITERATIVE DEEPENING, QUIESCENCE and ORDERING holds; it combines freely with quiescence and with ordering).
 //     One step is added to NODE VALUE for the node at search ply k >= 1, after steps 1-3 (the moves are generated
 //     first: one node, counted and tested against the budget like any other; a result -- mate, stalemate,
@@ -160,10 +160,10 @@
 // bit comes from the MoveGenInfo of the movegen it runs anyway.  Per node the lanes compare the node's hash at the
 // distances 4, 6, .. in parallel, against the path's plies where the distance stays inside the search and against the
 // history copy beyond; a board is read (a frame's from LDS, a history one from the ring or the tree) only on a hash
-// hit.  These arrays lie outside the union game_push reuses.  LDS: 3.6 KiB + 864 B = 4 512 B (_idr, _idor) and
-// 6.5 KiB + 928 B = 7 616 B (their _q forms).  (tests/repetition_util.py restates this section.)
+// hit.  These arrays lie outside the union game_push reuses.  LDS: 3.6 KiB + 864 B = 4 512 B (REP without QS) and
+// 6.5 KiB + 928 B = 7 616 B (REP with QS).  (tests/repetition_util.py restates this section.)
 //
-// EVALUATION (the _ev kernels only: evaluation = "positional", an opt-in on top of ITERATIVE DEEPENING, so of a node
+// EVALUATION (the POS shapes of the _id kernels only: evaluation = "positional", an opt-in on top of ITERATIVE DEEPENING, so of a node
 // budget; it combines freely with QUIESCENCE, ORDERING and REPETITION.  Every other launch uses STATIC EVALUATION above
 // and nothing else).  It replaces the static evaluation and nothing else: NODE VALUE 1-3 and 3b, the stand-pat (4c
 // still reads the evaluation before the moves are generated), the orders, the windows, the budget and the cut stay.
@@ -221,7 +221,7 @@
 //     subset of the pieces obeys the same bound), so MG * 65536 + EG travels through ONE wave reduction as an int32
 //     and is taken apart exactly afterwards.  No LDS, no scratch.  (tests/evaluation_util.py restates this section.)
 //
-// SELECTIVE (the _sel kernels only: selective = 1, an opt-in on top of ORDERING, so of ITERATIVE DEEPENING and a node
+// SELECTIVE (the SEL shapes of the _id kernels only: selective = 1, an opt-in on top of ORDERING, so of ITERATIVE DEEPENING and a node
 // budget; it combines freely with QUIESCENCE, REPETITION and EVALUATION, and everything in those sections holds unless
 // this one says otherwise.  Every other launch searches every line to full width, as above).  Null-move pruning and
 // late-move reductions; the three constants (the null move's 3 plies, c >= 3, r >= 3) are fixed.
@@ -255,7 +255,7 @@
 //     a reduced search and a re-search included), the cut rules, depth_done and CRL_OPP_CUT.
 // Consequences.  (a) With D <= 2 no node has r >= 3 and none below the root has r >= 2: every output, `nodes`
 // included, equals the search without this section.  (b) The search is no longer minimax over the full tree: move and
-// score may differ from the _ido search even under a budget nothing reaches.  It stays a function of the root, its
+// score may differ from the ORD search even under a budget nothing reaches.  It stays a function of the root, its
 // reversible history and the arguments.  (c) A null-move cut is never a mate score, and no null move is tried against
 // a mate window, so a mate score still counts plies of real moves and null moves alike from the root.  (d) A null child
 // has r - 3, and a node below the root has r <= 4 at the depths this opponent runs (D <= 5), so a null child has r <= 1:
@@ -274,7 +274,7 @@
 // kernel: with quiescence ahead of the move generation (the stand-pat and the null move's last guard), without it
 // behind the move generation (the horizon and that guard).  (tests/selective_util.py restates this section.)
 //
-// EXCHANGE (the _exc kernels only: exchange = 1, an opt-in on top of ORDERING, so of ITERATIVE DEEPENING and a node
+// EXCHANGE (the EXC shapes of the _id kernels only: exchange = 1, an opt-in on top of ORDERING, so of ITERATIVE DEEPENING and a node
 // budget, with Q >= 1; it combines freely with REPETITION, EVALUATION and SELECTIVE, and everything in those sections
 // holds.  Every other launch tries every tactical move of a stand-pat node, as QUIESCENCE 4c says).  Delta and exchange
 // pruning in quiescence; the margin 200 is conventional, untuned and fixed.
@@ -781,6 +781,27 @@ __device__ inline bool opp_null_guards(const Board &b, int k, int e, int beta, c
     return ((u32)uni(f[k - 1].pad) & 3u) != OPP_CHILD_NULL;
 }
 
+// THE SHAPES of the budgeted search: six flags, one bit each in this order (the index of the host's kernel tables).
+// SELECTIVE requires ORDERING; EXCHANGE requires ORDERING and quiescence plies.
+enum : unsigned { OPP_SHAPE_QS = 1, OPP_SHAPE_ORD = 2, OPP_SHAPE_REP = 4, OPP_SHAPE_POS = 8, OPP_SHAPE_SEL = 16,
+                  OPP_SHAPE_EXC = 32, OPP_SHAPES = 64 };
+constexpr bool opp_shape_legal(bool QS, bool ORD, bool /*REP*/, bool /*POS*/, bool SEL, bool EXC)
+{
+    return (ORD || !SEL) && ((ORD && QS) || !EXC);
+}
+constexpr bool opp_shape_legal(unsigned i)
+{
+    return opp_shape_legal(i & OPP_SHAPE_QS, i & OPP_SHAPE_ORD, i & OPP_SHAPE_REP, i & OPP_SHAPE_POS,
+                           i & OPP_SHAPE_SEL, i & OPP_SHAPE_EXC);
+}
+constexpr int opp_legal_shapes()
+{
+    int n = 0;
+    for (unsigned i = 0; i < OPP_SHAPES; i++) n += opp_shape_legal(i) ? 1 : 0;
+    return n;
+}
+static_assert(opp_legal_shapes() == 32, "the budgeted search has 32 legal shapes");
+
 template <bool QS, bool ID = false, bool ORD = false, bool REP = false, bool POS = false, bool SEL = false,
           bool EXC = false>
 __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long long limit, OppFrame *f, int lane,
@@ -789,8 +810,7 @@ __device__ inline OppResult opp_search(const Board &root, int Dmax, int Q, long 
     static_assert(ID || !ORD, "ORDERING requires ITERATIVE DEEPENING");
     static_assert(ID || !REP, "REPETITION requires ITERATIVE DEEPENING");
     static_assert(ID || !POS, "EVALUATION requires ITERATIVE DEEPENING");
-    static_assert(ORD || !SEL, "SELECTIVE requires ORDERING");
-    static_assert((ORD && QS) || !EXC, "EXCHANGE requires ORDERING and quiescence plies");
+    static_assert(opp_shape_legal(QS, ORD, REP, POS, SEL, EXC), "not a shape of the search (opp_shape_legal)");
     int K = 0;                                             // REP: the positions behind the root that hh holds
     if (ORD) {                                             // both killers of every ply: NO_MOVE
         constexpr int NF = QS ? OPP_MAX_DEPTH + OPP_MAX_QUIESCENCE : OPP_MAX_DEPTH + 1;
@@ -1084,81 +1104,22 @@ __global__ __launch_bounds__(64) void k_opponent_moves_q(Dev d, const int32_t *d
     opponent_moves_slot<true>(d, depths, Q, push, limit, moves, scores, nodes_out, flags, s);
 }
 
-// ITERATIVE DEEPENING under the node budget: depths[] are maximum depths, depths_done [count] the completed ones.  Kernels
-// of their own, so a launch without a budget runs the code it ran.
-__global__ __launch_bounds__(64) void k_opponent_moves_id(Dev d, const int32_t *depths, int push, long long budget,
-                                                          u16 *moves, int32_t *scores, long long *nodes_out,
-                                                          uint8_t *flags, int32_t *depths_done)
+// ITERATIVE DEEPENING under the node budget: depths[] are maximum depths, depths_done [count] the completed ones.  One
+// kernel template of its own for the 32 legal shapes (opp_shape_legal), so a launch without a budget runs the code it
+// ran.  One argument list for all: Q is not read without QS, and the REPETITION arrays exist in LDS only with REP.
+template <bool QS, bool ORD, bool REP, bool POS, bool SEL, bool EXC>
+__global__ __launch_bounds__(64) void k_opponent_moves_id(Dev d, const int32_t *depths, int Q, int push,
+                                                          long long budget, u16 *moves, int32_t *scores,
+                                                          long long *nodes_out, uint8_t *flags, int32_t *depths_done)
 {
-    __shared__ OppLds<false> s;
-    opponent_moves_slot<false, true>(d, depths, 0, push, budget, moves, scores, nodes_out, flags, s, depths_done);
-}
-
-__global__ __launch_bounds__(64) void k_opponent_moves_id_q(Dev d, const int32_t *depths, int Q, int push,
-                                                            long long budget, u16 *moves, int32_t *scores,
-                                                            long long *nodes_out, uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<true> s;
-    opponent_moves_slot<true, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s, depths_done);
-}
-
-// the _id kernels with ORDERING: the same arguments
-__global__ __launch_bounds__(64) void k_opponent_moves_ido(Dev d, const int32_t *depths, int push, long long budget,
-                                                           u16 *moves, int32_t *scores, long long *nodes_out,
-                                                           uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<false> s;
-    opponent_moves_slot<false, true, true>(d, depths, 0, push, budget, moves, scores, nodes_out, flags, s, depths_done);
-}
-
-__global__ __launch_bounds__(64) void k_opponent_moves_ido_q(Dev d, const int32_t *depths, int Q, int push,
-                                                             long long budget, u16 *moves, int32_t *scores,
-                                                             long long *nodes_out, uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<true> s;
-    opponent_moves_slot<true, true, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s, depths_done);
-}
-
-// the _id and _ido kernels with REPETITION: the same arguments
-__global__ __launch_bounds__(64) void k_opponent_moves_idr(Dev d, const int32_t *depths, int push, long long budget,
-                                                           u16 *moves, int32_t *scores, long long *nodes_out,
-                                                           uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<false> s;
-    __shared__ OppRepLds<false> rs;
-    opponent_moves_slot<false, true, false, true>(d, depths, 0, push, budget, moves, scores, nodes_out, flags, s,
-                                                  depths_done, &rs);
-}
-
-__global__ __launch_bounds__(64) void k_opponent_moves_idr_q(Dev d, const int32_t *depths, int Q, int push,
-                                                             long long budget, u16 *moves, int32_t *scores,
-                                                             long long *nodes_out, uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<true> s;
-    __shared__ OppRepLds<true> rs;
-    opponent_moves_slot<true, true, false, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s,
-                                                 depths_done, &rs);
-}
-
-__global__ __launch_bounds__(64) void k_opponent_moves_idor(Dev d, const int32_t *depths, int push, long long budget,
-                                                            u16 *moves, int32_t *scores, long long *nodes_out,
-                                                            uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<false> s;
-    __shared__ OppRepLds<false> rs;
-    opponent_moves_slot<false, true, true, true>(d, depths, 0, push, budget, moves, scores, nodes_out, flags, s,
-                                                 depths_done, &rs);
-}
-
-__global__ __launch_bounds__(64) void k_opponent_moves_idor_q(Dev d, const int32_t *depths, int Q, int push,
-                                                              long long budget, u16 *moves, int32_t *scores,
-                                                              long long *nodes_out, uint8_t *flags,
-                                                              int32_t *depths_done)
-{
-    __shared__ OppLds<true> s;
-    __shared__ OppRepLds<true> rs;
-    opponent_moves_slot<true, true, true, true>(d, depths, Q, push, budget, moves, scores, nodes_out, flags, s,
-                                                depths_done, &rs);
+    __shared__ OppLds<QS> s;
+    OppRepLds<QS> *rs = nullptr;
+    if constexpr (REP) {
+        __shared__ OppRepLds<QS> rep;
+        rs = &rep;
+    }
+    opponent_moves_slot<QS, true, ORD, REP, POS, SEL, EXC>(d, depths, QS ? Q : 0, push, budget, moves, scores,
+                                                           nodes_out, flags, s, depths_done, rs);
 }
 
 // expand, the opponent's half (mctree.py:244-246) with the built-in opponent as the mover (gamestockfish.py:27-41):
@@ -1214,171 +1175,20 @@ __global__ __launch_bounds__(64) void k_reply_opponent_q(Dev d, const int32_t *d
     reply_opponent_row<true>(d, depths, Q, limit, planes2, nodes_acc, cuts_acc, s);
 }
 
-__global__ __launch_bounds__(64) void k_reply_opponent_id(Dev d, const int32_t *depths, long long budget, void *planes2,
-                                                          unsigned long long *nodes_acc, uint32_t *cuts_acc,
-                                                          unsigned long long *depth_acc)
-{
-    __shared__ OppLds<false> s;
-    reply_opponent_row<false, true>(d, depths, 0, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
-}
-
-__global__ __launch_bounds__(64) void k_reply_opponent_id_q(Dev d, const int32_t *depths, int Q, long long budget,
-                                                            void *planes2, unsigned long long *nodes_acc,
-                                                            uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<true> s;
-    reply_opponent_row<true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
-}
-
-// the _id kernels with ORDERING: the same arguments
-__global__ __launch_bounds__(64) void k_reply_opponent_ido(Dev d, const int32_t *depths, long long budget,
-                                                           void *planes2, unsigned long long *nodes_acc,
-                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<false> s;
-    reply_opponent_row<false, true, true>(d, depths, 0, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
-}
-
-__global__ __launch_bounds__(64) void k_reply_opponent_ido_q(Dev d, const int32_t *depths, int Q, long long budget,
-                                                             void *planes2, unsigned long long *nodes_acc,
-                                                             uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<true> s;
-    reply_opponent_row<true, true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc);
-}
-
-// the _id and _ido kernels with REPETITION: the same arguments
-__global__ __launch_bounds__(64) void k_reply_opponent_idr(Dev d, const int32_t *depths, long long budget,
-                                                           void *planes2, unsigned long long *nodes_acc,
-                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<false> s;
-    __shared__ OppRepLds<false> rs;
-    reply_opponent_row<false, true, false, true>(d, depths, 0, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
-}
-
-__global__ __launch_bounds__(64) void k_reply_opponent_idr_q(Dev d, const int32_t *depths, int Q, long long budget,
-                                                             void *planes2, unsigned long long *nodes_acc,
-                                                             uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<true> s;
-    __shared__ OppRepLds<true> rs;
-    reply_opponent_row<true, true, false, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
-}
-
-__global__ __launch_bounds__(64) void k_reply_opponent_idor(Dev d, const int32_t *depths, long long budget,
-                                                            void *planes2, unsigned long long *nodes_acc,
-                                                            uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<false> s;
-    __shared__ OppRepLds<false> rs;
-    reply_opponent_row<false, true, true, true>(d, depths, 0, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
-}
-
-__global__ __launch_bounds__(64) void k_reply_opponent_idor_q(Dev d, const int32_t *depths, int Q, long long budget,
-                                                              void *planes2, unsigned long long *nodes_acc,
-                                                              uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<true> s;
-    __shared__ OppRepLds<true> rs;
-    reply_opponent_row<true, true, true, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc, s, depth_acc, &rs);
-}
-
-// EVALUATION: the sixteen budgeted kernels once more with the positional evaluation, as two kernel templates (the
-// shapes _id, _ido, _idr, _idor, each with and without quiescence).  One argument list for all: Q is not read
-// without QS, and the REPETITION arrays exist in LDS only with REP.
-template <bool QS, bool ORD, bool REP>
-__global__ __launch_bounds__(64) void k_opponent_moves_ev(Dev d, const int32_t *depths, int Q, int push,
-                                                          long long budget, u16 *moves, int32_t *scores,
-                                                          long long *nodes_out, uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<QS> s;
-    if constexpr (REP) {
-        __shared__ OppRepLds<QS> rs;
-        opponent_moves_slot<QS, true, ORD, true, true>(d, depths, QS ? Q : 0, push, budget, moves, scores, nodes_out,
-                                                       flags, s, depths_done, &rs);
-    } else
-        opponent_moves_slot<QS, true, ORD, false, true>(d, depths, QS ? Q : 0, push, budget, moves, scores, nodes_out,
-                                                        flags, s, depths_done);
-}
-
-template <bool QS, bool ORD, bool REP>
-__global__ __launch_bounds__(64) void k_reply_opponent_ev(Dev d, const int32_t *depths, int Q, long long budget,
+// the budgeted reply: the 32 legal shapes as one kernel template with the argument list of k_opponent_moves_id's kind
+template <bool QS, bool ORD, bool REP, bool POS, bool SEL, bool EXC>
+__global__ __launch_bounds__(64) void k_reply_opponent_id(Dev d, const int32_t *depths, int Q, long long budget,
                                                           void *planes2, unsigned long long *nodes_acc,
                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
 {
     __shared__ OppLds<QS> s;
+    OppRepLds<QS> *rs = nullptr;
     if constexpr (REP) {
-        __shared__ OppRepLds<QS> rs;
-        reply_opponent_row<QS, true, ORD, true, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc, cuts_acc, s,
-                                                      depth_acc, &rs);
-    } else
-        reply_opponent_row<QS, true, ORD, false, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc, cuts_acc, s,
-                                                       depth_acc);
-}
-
-// SELECTIVE: the eight ordered budgeted shapes (quiescence, repetition, evaluation) once more with null-move pruning
-// and late-move reductions, as two kernel templates with the argument lists of the _ev kernels.
-template <bool QS, bool REP, bool POS>
-__global__ __launch_bounds__(64) void k_opponent_moves_sel(Dev d, const int32_t *depths, int Q, int push,
-                                                           long long budget, u16 *moves, int32_t *scores,
-                                                           long long *nodes_out, uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<QS> s;
-    if constexpr (REP) {
-        __shared__ OppRepLds<QS> rs;
-        opponent_moves_slot<QS, true, true, true, POS, true>(d, depths, QS ? Q : 0, push, budget, moves, scores,
-                                                             nodes_out, flags, s, depths_done, &rs);
-    } else
-        opponent_moves_slot<QS, true, true, false, POS, true>(d, depths, QS ? Q : 0, push, budget, moves, scores,
-                                                              nodes_out, flags, s, depths_done);
-}
-
-template <bool QS, bool REP, bool POS>
-__global__ __launch_bounds__(64) void k_reply_opponent_sel(Dev d, const int32_t *depths, int Q, long long budget,
-                                                           void *planes2, unsigned long long *nodes_acc,
-                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<QS> s;
-    if constexpr (REP) {
-        __shared__ OppRepLds<QS> rs;
-        reply_opponent_row<QS, true, true, true, POS, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc,
-                                                            cuts_acc, s, depth_acc, &rs);
-    } else
-        reply_opponent_row<QS, true, true, false, POS, true>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc,
-                                                             cuts_acc, s, depth_acc);
-}
-
-// EXCHANGE: the eight ordered budgeted shapes with quiescence plies (repetition, evaluation, selective) once more with
-// delta and exchange pruning at the stand-pat nodes, as two kernel templates with the argument lists of the _ev kernels.
-template <bool REP, bool POS, bool SEL>
-__global__ __launch_bounds__(64) void k_opponent_moves_exc(Dev d, const int32_t *depths, int Q, int push,
-                                                           long long budget, u16 *moves, int32_t *scores,
-                                                           long long *nodes_out, uint8_t *flags, int32_t *depths_done)
-{
-    __shared__ OppLds<true> s;
-    if constexpr (REP) {
-        __shared__ OppRepLds<true> rs;
-        opponent_moves_slot<true, true, true, true, POS, SEL, true>(d, depths, Q, push, budget, moves, scores,
-                                                                    nodes_out, flags, s, depths_done, &rs);
-    } else
-        opponent_moves_slot<true, true, true, false, POS, SEL, true>(d, depths, Q, push, budget, moves, scores,
-                                                                     nodes_out, flags, s, depths_done);
-}
-
-template <bool REP, bool POS, bool SEL>
-__global__ __launch_bounds__(64) void k_reply_opponent_exc(Dev d, const int32_t *depths, int Q, long long budget,
-                                                           void *planes2, unsigned long long *nodes_acc,
-                                                           uint32_t *cuts_acc, unsigned long long *depth_acc)
-{
-    __shared__ OppLds<true> s;
-    if constexpr (REP) {
-        __shared__ OppRepLds<true> rs;
-        reply_opponent_row<true, true, true, true, POS, SEL, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc,
-                                                                   s, depth_acc, &rs);
-    } else
-        reply_opponent_row<true, true, true, false, POS, SEL, true>(d, depths, Q, budget, planes2, nodes_acc, cuts_acc,
-                                                                    s, depth_acc);
+        __shared__ OppRepLds<QS> rep;
+        rs = &rep;
+    }
+    reply_opponent_row<QS, true, ORD, REP, POS, SEL, EXC>(d, depths, QS ? Q : 0, budget, planes2, nodes_acc, cuts_acc,
+                                                          s, depth_acc, rs);
 }
 
 // EXCHANGE, test 2 alone and no search: every legal move of every window slot's current position, in generation

@@ -236,12 +236,9 @@ class LockstepEngine(object):
     the built-in opponent's move, searched with the player's ``search_depth``, ``quiescence`` and ``node_limit`` (its colour is
     ignored: the side to move after our move replies).  A player with a ``node_budget`` replies by iterative deepening
     under that budget (csrc/opponent.hpp ``k_reply_opponent_id``); one without launches the fixed-depth kernel as before.
-    A budgeted player with ``ordering`` replies through the ordered kernels (``k_reply_opponent_ido``), eager and captured.
-    A budgeted player with ``repetition`` replies through the repetition-aware kernels (``k_reply_opponent_idr`` /
-    ``_idor``): a reply search scores a position it has had, in its own line, on the tree path or in the game, a draw.
-    A budgeted player with ``evaluation="positional"`` replies through the ``k_reply_opponent_ev`` kernel of the same shape,
-    one with ``selective=True`` through the ``k_reply_opponent_sel`` kernel of the same shape, one with
-    ``exchange=True`` through the ``k_reply_opponent_exc`` kernel of the same shape.
+    The player's other options (``MinimaxPlayer.options``: ``ordering``, ``repetition``, ``evaluation``, ``selective``,
+    ``exchange``) choose the instantiation of that kernel template, eager and captured.  With ``repetition`` a reply
+    search scores a position it has had, in its own line, on the tree path or in the game, a draw.
     """
 
     def __init__(self, evaluator, n_games, max_sims, device=0, max_plies=4096,
@@ -421,14 +418,11 @@ class LockstepEngine(object):
 
     def phase_reply_opponent(self):
         """Only with ``reply``: the built-in opponent's move from S1 becomes the node's reply."""
-        budget = self.reply.node_budget
+        opts = self.reply.options
         self.ctx.sim_reply_opponent(self.reply_depths.data_ptr(), self.reply.node_limit, self.planes_s2.data_ptr(),
                                     self.reply_nodes.data_ptr(), self.reply_cuts.data_ptr(),
-                                    quiescence=self.reply.quiescence, node_budget=budget,
-                                    dev_depth_sum=None if budget is None else self.reply_depth_sum.data_ptr(),
-                                    ordering=self.reply.ordering, repetition=self.reply.repetition,
-                                    evaluation=self.reply.evaluation, selective=self.reply.selective,
-                                    exchange=self.reply.exchange)
+                                    dev_depth_sum=None if opts.node_budget is None else self.reply_depth_sum.data_ptr(),
+                                    **opts.kwargs)
 
     def phase_tower_s2(self):
         if self.legal_priors:

@@ -76,18 +76,7 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
     ("positional" needs a ``node_budget``): both sides search with its EVALUATION; ``selective`` (needs ``ordering``):
     both sides search with its SELECTIVE rules; ``exchange`` (needs ``ordering`` and ``quiescence`` >= 1): both sides
     search with its EXCHANGE rules."""
-    if ordering and node_budget is None:
-        raise ValueError("ordering needs a node_budget")
-    if repetition and node_budget is None:
-        raise ValueError("repetition needs a node_budget")
-    _lib.opponent_evaluation(evaluation, node_budget)
-    selective = _lib.opponent_selective(selective, ordering)
-    if node_budget is not None and int(node_budget) < 1:
-        raise ValueError("node_budget must be None or at least 1")
-    quiescence = int(quiescence)
-    exchange = _lib.opponent_exchange(exchange, ordering, node_budget, quiescence)
-    if not 0 <= quiescence <= _lib.OPP_MAX_QUIESCENCE:
-        raise ValueError("quiescence must lie in [0, %d]" % _lib.OPP_MAX_QUIESCENCE)
+    opts = _lib.OpponentOptions(quiescence, node_budget, ordering, repetition, evaluation, selective, exchange)
     num_games, opening_plies, max_plies = int(num_games), int(opening_plies), int(max_plies)
     d = DatasetGame()
     if num_games < 1:
@@ -110,10 +99,7 @@ def gen_data(save_path, num_games=100, depth=1, random_dep=False, opening_plies=
             running = results == _lib.RESULT_NONE
             if not running.any():
                 break
-            ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True,
-                               quiescence=quiescence, node_budget=node_budget, ordering=bool(ordering),
-                               repetition=bool(repetition), evaluation=evaluation, selective=selective,
-                               exchange=exchange)
+            ctx.opponent_moves(np.where(running, side_depths(draws, ply % 2 == 0), 0), push=True, **opts.kwargs)
             results = ctx.results()
         moves, plies, results = ctx.records()
     finally:

@@ -57,24 +57,12 @@ class MinimaxPlayer(Player):
             raise ValueError("search_depth must lie in [1, %d]" % MAX_DEPTH)
         if int(node_limit) < 1:
             raise ValueError("node_limit must be at least 1")
-        if not 0 <= int(quiescence) <= MAX_QUIESCENCE:
-            raise ValueError("quiescence must lie in [0, %d]" % MAX_QUIESCENCE)
+        self.options = _lib.OpponentOptions(quiescence, node_budget, ordering, repetition, evaluation, selective,
+                                            exchange)
         self.search_depth = int(search_depth)
-        self.quiescence = int(quiescence)
-        if node_budget is not None and int(node_budget) < 1:
-            raise ValueError("node_budget must be None or at least 1")
         self.node_limit = int(node_limit)
-        self.node_budget = None if node_budget is None else int(node_budget)
-        if ordering and self.node_budget is None:
-            raise ValueError("ordering needs a node_budget")
-        self.ordering = bool(ordering)
-        if repetition and self.node_budget is None:
-            raise ValueError("repetition needs a node_budget")
-        self.repetition = bool(repetition)
-        _lib.opponent_evaluation(evaluation, self.node_budget)
-        self.evaluation = evaluation
-        self.selective = _lib.opponent_selective(selective, self.ordering)
-        self.exchange = _lib.opponent_exchange(exchange, self.ordering, self.node_budget, self.quiescence)
+        (self.quiescence, self.node_budget, self.ordering, self.repetition, self.evaluation, self.selective,
+         self.exchange) = self.options
         self.last = None                      # (score, nodes, flag) of the last search
         self.last_depth = None                # with a budget: the depth that search completed
 
@@ -83,9 +71,7 @@ class MinimaxPlayer(Player):
             raise RuntimeError("Game was freed")
         ctx = arena().one(game._slot)
         out = ctx.opponent_moves(np.array([self.search_depth], np.int32), push=False, node_limit=self.node_limit,
-                                 quiescence=self.quiescence, node_budget=self.node_budget, ordering=self.ordering,
-                                 repetition=self.repetition, evaluation=self.evaluation, selective=self.selective,
-                                 exchange=self.exchange)
+                                 **self.options.kwargs)
         moves, scores, nodes, flags = out[:4]
         self.last = (int(scores[0]), int(nodes[0]), int(flags[0]))
         self.last_depth = int(out[4][0]) if self.node_budget is not None else None

@@ -398,8 +398,8 @@ int  crl_sim_reply_opponent_ev(crl_ctx *ctx, const int32_t *dev_depths_i32, int 
                                uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64);
 /* The two _ev calls with opt-in SELECTIVE search (csrc/opponent.hpp states it): null-move pruning and late-move
  * reductions on top of ORDERING.  selective = 0 is the _ev call, array for array, from the same kernels.
- * selective = 1 needs ordering = 1 and launches the k_opponent_moves_sel / k_reply_opponent_sel kernel of the same
- * shape (quiescence, repetition, evaluation): a node with remaining depth >= 2 whose static evaluation reaches beta
+ * selective = 1 needs ordering = 1 and launches the SEL instantiation of k_opponent_moves_id / k_reply_opponent_id of the
+ * same shape (quiescence, repetition, evaluation): a node with remaining depth >= 2 whose static evaluation reaches beta
  * first tries a null move searched 3 plies shallower, and a quiet late move (position >= 3, remaining depth >= 3) is
  * first searched one ply shallower on a null window and again at full depth only if it beats alpha.  The search is
  * no longer minimax over the full tree; with a maximum depth <= 2 every output equals the _ev call's.
@@ -414,8 +414,8 @@ int  crl_sim_reply_opponent_sel(crl_ctx *ctx, const int32_t *dev_depths_i32, int
                                 uint64_t *dev_nodes_u64, uint32_t *dev_cuts_u32, uint64_t *dev_depth_sum_u64);
 /* The two _sel calls with opt-in EXCHANGE (csrc/opponent.hpp states it): delta and exchange pruning at the quiescence
  * nodes that stand pat.  exchange = 0 is the _sel call, array for array, from the same kernels.  exchange = 1 needs
- * ordering = 1 and quiescence >= 1 and launches the k_opponent_moves_exc / k_reply_opponent_exc kernel of the same
- * shape (repetition, evaluation, selective): at such a node a tactical move that is no promotion is dropped when
+ * ordering = 1 and quiescence >= 1 and launches the EXC instantiation of k_opponent_moves_id / k_reply_opponent_id of the
+ * same shape (repetition, evaluation, selective): at such a node a tactical move that is no promotion is dropped when
  * stand + value(victim) + 200 <= alpha, and any tactical move when its static exchange value on the destination
  * square is negative.  The filter generates no moves: node counts count what they counted.  From a root whose search
  * meets no such move every output equals the _sel call's.

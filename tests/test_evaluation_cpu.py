@@ -264,8 +264,14 @@ def test_host_refusals_the_mode_key_and_the_header():
     header = open(os.path.join(ROOT, "chessrl_amd", "csrc", "opponent.hpp")).read()
     assert "// EVALUATION (" in header and "static_assert(ID || !POS" in header
     assert "int opp_evaluate_positional(const Board &b, int lane)" in header
-    for k in ("k_opponent_moves_ev", "k_reply_opponent_ev", "k_opponent_evaluate"):
-        assert re.search(r"void %s\(" % k, header), k
+    assert re.search(r"void k_opponent_evaluate\(", header)
+    # the budgeted kernels are two templates over the six flags (POS among them), their legal shapes stated once
+    for k in ("k_opponent_moves_id", "k_reply_opponent_id"):
+        assert re.search(r"template <bool QS, bool ORD, bool REP, bool POS, bool SEL, bool EXC>\s*"
+                         r"__global__ __launch_bounds__\(64\) void %s\(" % k, header), k
+    assert re.search(r"constexpr bool opp_shape_legal\(bool QS, bool ORD,", header)
+    assert re.search(r"static_assert\(opp_legal_shapes\(\) == 32,", header)
+    assert "static_assert(opp_shape_legal(QS, ORD, REP, POS, SEL, EXC)" in header
 
 
 def test_cli_flags():

@@ -138,14 +138,16 @@ def test_the_gpu_set_meets_its_preconditions():
 def test_value_errors():
     from chessrl_amd import _lib
     from chessrl_amd.opponent import MinimaxPlayer
-    assert _lib.opponent_exchange(False, False, None, 0) is False
-    assert _lib.opponent_exchange(True, True, 100, 1) is True
+    options = lambda exchange, ordering, node_budget, quiescence: _lib.OpponentOptions(
+        quiescence=quiescence, node_budget=node_budget, ordering=ordering, exchange=exchange)
+    assert options(False, False, None, 0).exchange is False
+    assert options(True, True, 100, 1).exchange is True
     with pytest.raises(ValueError, match="exchange needs ordering"):
-        _lib.opponent_exchange(True, False, 100, 2)
+        options(True, False, 100, 2)
     with pytest.raises(ValueError, match="ordering needs a node_budget"):
-        _lib.opponent_exchange(True, True, None, 2)
+        options(True, True, None, 2)
     with pytest.raises(ValueError, match="exchange needs quiescence"):
-        _lib.opponent_exchange(True, True, 100, 0)
+        options(True, True, 100, 0)
     with pytest.raises(ValueError, match="exchange needs ordering"):
         MinimaxPlayer(True, 3, node_budget=100, quiescence=2, exchange=True)
     with pytest.raises(ValueError, match="ordering needs a node_budget"):

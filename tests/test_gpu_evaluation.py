@@ -1,5 +1,5 @@
 """GPU: the built-in opponent's positional evaluation (csrc/opponent.hpp EVALUATION; ``opp_evaluate_positional``, the
-``k_opponent_moves_ev`` / ``k_reply_opponent_ev`` kernels and ``k_opponent_evaluate``) against its CPU restatement
+POS shapes of the ``k_opponent_moves_id`` / ``k_reply_opponent_id`` kernel templates and ``k_opponent_evaluate``) against its CPU restatement
 (tests/evaluation_util.py; the restatement itself is held to the header's table without a GPU in
 tests/test_evaluation_cpu.py).
 

@@ -1,5 +1,5 @@
 """GPU: the built-in opponent's delta and exchange pruning in quiescence (csrc/opponent.hpp EXCHANGE; the
-``k_opponent_moves_exc`` / ``k_reply_opponent_exc`` / ``k_opponent_exchange`` kernels) against its CPU restatement
+EXC shapes of the ``k_opponent_moves_id`` / ``k_reply_opponent_id`` kernel templates and ``k_opponent_exchange``) against its CPU restatement
 (tests/exchange_util.py; the restatement itself is held to its definition, to the existing restatements and to the
 preconditions of these roots without a GPU in tests/test_exchange_cpu.py).
 

@@ -1,5 +1,5 @@
 """GPU: the built-in opponent's iterative deepening under a node budget (csrc/opponent.hpp ITERATIVE DEEPENING;
-``k_opponent_moves_id``, ``k_reply_opponent_id`` and their quiescence forms) against its CPU restatement
+the ``k_opponent_moves_id`` / ``k_reply_opponent_id`` kernel templates) against its CPU restatement
 (tests/iterdeep_util.py; its preconditions and the case list are asserted without a GPU in tests/test_iterdeep_cpu.py).
 
 1. move, score, node count, flag and completed depth of 16 roots and three set-up positions equal ``iterdeep`` in every

@@ -1,5 +1,5 @@
-"""GPU: the built-in opponent's move ordering under a node budget (csrc/opponent.hpp ORDERING; ``k_opponent_moves_ido``,
-``k_reply_opponent_ido`` and their quiescence forms) against its CPU restatement (tests/ordering_util.py; its
+"""GPU: the built-in opponent's move ordering under a node budget (csrc/opponent.hpp ORDERING; the ORD shapes of the
+``k_opponent_moves_id`` / ``k_reply_opponent_id`` kernel templates) against its CPU restatement (tests/ordering_util.py; its
 preconditions and the case list are asserted without a GPU in tests/test_ordering_cpu.py).
 
 1. move, score, node count, flag and completed depth of 16 roots and three set-up positions equal ``ordered`` in every

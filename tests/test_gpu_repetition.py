@@ -1,5 +1,5 @@
 """GPU: the built-in opponent's repetition rule under a node budget (csrc/opponent.hpp REPETITION;
-``k_opponent_moves_idr`` / ``_idor``, ``k_reply_opponent_idr`` / ``_idor`` and their quiescence forms) against its CPU
+the REP shapes of the ``k_opponent_moves_id`` / ``k_reply_opponent_id`` kernel templates) against its CPU
 restatement (tests/repetition_util.py; its preconditions and the case list are asserted without a GPU in
 tests/test_repetition_cpu.py).
 

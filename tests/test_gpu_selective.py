@@ -1,5 +1,5 @@
-"""GPU: the built-in opponent's selective search (csrc/opponent.hpp SELECTIVE; the ``k_opponent_moves_sel`` /
-``k_reply_opponent_sel`` kernels) against its CPU restatement (tests/selective_util.py; the restatement itself is held
+"""GPU: the built-in opponent's selective search (csrc/opponent.hpp SELECTIVE; the SEL shapes of the
+``k_opponent_moves_id`` / ``k_reply_opponent_id`` kernel templates) against its CPU restatement (tests/selective_util.py; the restatement itself is held
 to the ordered search and to its own branch counts without a GPU in tests/test_selective_cpu.py).
 
 1. ``opponent_moves(selective=True)``: move, score, node count, flag and completed depth equal the restatement in every

@@ -237,6 +237,10 @@ def test_host_refusals_the_mode_key_and_the_header():
     assert "#define CRL_ABI_VERSION 9" in text and _lib.ABI_VERSION == 9
     header = open(os.path.join(ROOT, "chessrl_amd", "csrc", "opponent.hpp")).read()
     assert "// REPETITION (" in header and "static_assert(ID || !REP" in header
-    for k in ("k_opponent_moves_idr", "k_opponent_moves_idr_q", "k_opponent_moves_idor", "k_opponent_moves_idor_q",
-              "k_reply_opponent_idr", "k_reply_opponent_idr_q", "k_reply_opponent_idor", "k_reply_opponent_idor_q"):
-        assert re.search(r"void %s\(" % k, header), k
+    # the budgeted kernels are two templates over the six flags (REP among them), their legal shapes stated once
+    for k in ("k_opponent_moves_id", "k_reply_opponent_id"):
+        assert re.search(r"template <bool QS, bool ORD, bool REP, bool POS, bool SEL, bool EXC>\s*"
+                         r"__global__ __launch_bounds__\(64\) void %s\(" % k, header), k
+    assert re.search(r"constexpr bool opp_shape_legal\(bool QS, bool ORD,", header)
+    assert re.search(r"static_assert\(opp_legal_shapes\(\) == 32,", header)
+    assert "static_assert(opp_shape_legal(QS, ORD, REP, POS, SEL, EXC)" in header

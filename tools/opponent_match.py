@@ -36,10 +36,8 @@ ENDINGS = ("mate", "stalemate", "fifth_occurrence", "seventy_five_move_rule", "f
 
 def side_kw(settings):
     """The keywords of ``Context.opponent_moves`` of one side's settings (without its depth)."""
-    return dict(quiescence=settings.get("quiescence", 0), node_budget=settings["node_budget"],
-                ordering=bool(settings.get("ordering", False)), repetition=bool(settings.get("repetition", False)),
-                evaluation=settings.get("evaluation", "material"), selective=bool(settings.get("selective", False)),
-                exchange=bool(settings.get("exchange", False)))
+    from chessrl_amd import _lib
+    return _lib.OpponentOptions(**{k: v for k, v in settings.items() if k != "depth"}).kwargs
 
 
 def play(pairs, a, b, opening_plies=6, max_plies=300, seed=0):

@@ -137,15 +137,16 @@ def main():
             variants.append((variants[0][0] + " repeating-aware", dict(variants[0][1], repetition=True)))
         elif budget is not None and args.ordering:
             variants.append((key + " ordered", dict(kw, ordering=True)))
+        variants = [(k, _lib.OpponentOptions(**vkw)) for k, vkw in variants]
         times = dict((k, []) for k, _ in variants)
         last = {}
         for i in range(4):
-            for k, vkw in variants:
+            for k, opts in variants:
                 t0 = time.perf_counter()
-                last[k] = ctx.opponent_moves(row, node_limit=args.node_limit, **vkw)
+                last[k] = ctx.opponent_moves(row, node_limit=args.node_limit, **opts.kwargs)
                 if i:
                     times[k].append(time.perf_counter() - t0)
-        for k, vkw in variants:
+        for k, _ in variants:
             moves, scores, nodes, flags = last[k][:4]
             t = statistics.median(times[k])
             searched = flags != _lib.OPP_SKIPPED

@@ -13,10 +13,10 @@ the timed windows alternate between them: a window is ``run_steps(--steps)`` bet
 clock; the median window is reported.  The trees grow alike in all engines, so window k compares like with like.
 Then one more step with cleared accumulators gives the nodes per reply (mean / max over the slots that needed one)
 and the cuts; the accumulators over the whole run give the mean per slot and step.  --budget B[,B..] adds one engine
-per node budget, ``reply=MinimaxPlayer(search_depth=--max-depth, node_budget=B)`` (iterative deepening:
-k_reply_opponent_id), with the histogram of the completed depths of the last step's replies; such a run is stored as the
+per node budget, ``reply=MinimaxPlayer(search_depth=--max-depth, node_budget=B)`` (iterative deepening: the
+k_reply_opponent_id kernel template), with the histogram of the completed depths of the last step's replies; such a run is stored as the
 block "node_budget" of the output file, whose other content stays.  --ordering adds, next to every budgeted engine,
-the same engine with ``ordering=True`` (k_reply_opponent_ido), so every budget runs with ordering off and on in the same
+the same engine with ``ordering=True`` (its ORD instantiation), so every budget runs with ordering off and on in the same
 process; such a run is stored as the block "ordering".  No threshold: a measurement.
 """
 import argparse
