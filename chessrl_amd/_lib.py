@@ -49,6 +49,7 @@ WAVE_MAX_THREADS = 64     # include/chessrl_hip.h: CRL_WAVE_MAX_THREADS
 POLICY_FULL, POLICY_LEGAL, POLICY_LEGAL_RAW = 0, 1, 2
 TRUNK_BITPLANES = 1
 TRUNK_SPLIT = 2
+TRUNK_BALANCE = 4        # include/chessrl_hip.h: CRL_TRUNK_BALANCE (rank-tile cell: the partner-balance kernel)
 LIST_HEADER = 4          # include/chessrl_hip.h: CRL_LIST_HEADER (int32 words in front of a board list)
 
 # every symbol include/chessrl_hip.h declares (tests check the .so exports all of them)

@@ -1214,18 +1214,31 @@ static bool trunk_small_batch(int filters, int n_boards)
     return n_boards <= 128 * (filters == 256 ? 2 : 4) && g_small_batch.load() != 0;
 }
 
-struct TrunkPick { int nb, pair, group; };
+struct TrunkPick { int nb, pair, group, alt; };
 
-static TrunkPick trunk_pick(int filters, int n_boards, bool split)
+static TrunkPick trunk_pick_cell(int filters, int n_boards, bool split);
+
+// CRL_TRUNK_BALANCE: the rank-tile cell (128 filters, four boards per workgroup, f16) runs its partner-balance
+// instantiation (tower_x16.hpp, ALT = 1); every other cell has none and runs as without the flag
+static TrunkPick trunk_pick(int filters, int n_boards, int flags)
+{
+    TrunkPick pk = trunk_pick_cell(filters, n_boards, flags & CRL_TRUNK_SPLIT);
+    const bool rank_tiles = crl_tower::RankTiles<128, 4, 1, 0, 0, 0>::value && filters == 128 && pk.nb == 4 && pk.pair == 1 &&
+                            pk.group == 0 && !(flags & CRL_TRUNK_SPLIT);
+    pk.alt = ((flags & CRL_TRUNK_BALANCE) && rank_tiles) ? 1 : 0;
+    return pk;
+}
+
+static TrunkPick trunk_pick_cell(int filters, int n_boards, bool split)
 {
     const bool small = trunk_small_batch(filters, n_boards);
     if (split) {
         // split precision ("f16x3"): activation rows hold hi and lo, so 128 / 256 filters keep half the
         // boards per workgroup resident; 256 filters: plain ring of four (a fifth slot needs the zero rows
         // shortened to fit and was measured: 32.76 vs 32.82 ms, the kernel sits on the L2 -> LDS stream)
-        if (filters == 256) return { 1, 0, 0 };
-        if (filters == 128) return { 2, 1, 0 };
-        return { small ? 2 : 4, 0, 0 };
+        if (filters == 256) return { 1, 0, 0, 0 };
+        if (filters == 128) return { 2, 1, 0, 0 };
+        return { small ? 2 : 4, 0, 0, 0 };
     }
     // production: the 16x16x32-MFMA kernels of tower_x16.hpp for every filter count; 128 and 256
     // filters with one barrier per two weight tiles over a five-slot ring (PAIR)
@@ -1234,7 +1247,7 @@ static TrunkPick trunk_pick(int filters, int n_boards, bool split)
     // A batch that gives at most half of the 256 CUs a workgroup runs the half-size geometry
     // (half the boards per workgroup, twice the workgroups): C2's 512 boards are 128 workgroups of 4.
     const int nb = filters == 256 ? (small ? 1 : 2) : (small ? 2 : 4);
-    return { nb, filters == 64 ? 0 : 1, (filters == 64 && nb == 4) ? 1 : 0 };
+    return { nb, filters == 64 ? 0 : 1, (filters == 64 && nb == 4) ? 1 : 0, 0 };
 }
 
 // The layer-wise split-precision trunk of 256 filters (csrc/tower_layer.hpp): one launch that expands the input planes into
@@ -1334,7 +1347,7 @@ static int trunk_forward(void *hip_stream, int filters, const void *dev_planes_f
     if (!dev_planes_f16 || !dev_wtiles_f16 || !dev_bias_f32 || (!dev_out_f32 && !dev_head_out_f32) ||
         (dev_head_out_f32 && (!dev_head_w_f32 || !dev_head_b_f32)) || n_boards < 4 ||
         n_boards % crl_tower::BOARDS_PER_WG != 0 || n_blocks < 0 ||
-        1 + 2 * n_blocks > crl_tower::MAX_CONVS || (flags & ~(CRL_TRUNK_BITPLANES | CRL_TRUNK_SPLIT)) ||
+        1 + 2 * n_blocks > crl_tower::MAX_CONVS || (flags & ~(CRL_TRUNK_BITPLANES | CRL_TRUNK_SPLIT | CRL_TRUNK_BALANCE)) ||
         (dev_index && (dev_out_f32 || !dev_head_out_f32 || flags != (CRL_TRUNK_BITPLANES | CRL_TRUNK_SPLIT))))
         return fail(nullptr, CRL_ERR_ARG, "crl_trunk_forward: bad argument");
     typedef void (*kern_t)(const unsigned char *, const unsigned char *, const float *, float *, int,
@@ -1346,7 +1359,7 @@ static int trunk_forward(void *hip_stream, int filters, const void *dev_planes_f
         return layer_trunk_forward((hipStream_t)hip_stream, bits, dev_planes_f16, dev_wtiles_f16, dev_bias_f32, dev_out_f32,
                                    n_boards, n_blocks, dev_head_w_f32, dev_head_b_f32, dev_head_out_f32, dev_workspace,
                                    workspace_bytes, dev_index);
-    const TrunkPick pk = trunk_pick(filters, n_boards, split);
+    const TrunkPick pk = trunk_pick(filters, n_boards, flags);
 #define CRL_X16(F_, NB_, PAIR_, GROUP_, SPLIT_)                                                  \
     if (filters == F_ && pk.nb == NB_ && pk.pair == PAIR_ && pk.group == GROUP_ && split == (SPLIT_ != 0)) { \
         kern = bits ? crl_tower::k_trunk_x16<F_, NB_, 1, 0, PAIR_, GROUP_, SPLIT_>               \
@@ -1358,6 +1371,9 @@ static int trunk_forward(void *hip_stream, int filters, const void *dev_planes_f
     CRL_X16(128, 2, 1, 0, 0) CRL_X16(128, 4, 1, 0, 0)
     CRL_X16(128, 2, 1, 0, 1) CRL_X16(64, 2, 0, 0, 1) CRL_X16(64, 4, 0, 0, 1)       // (256 filters: tower_layer.hpp)
 #undef CRL_X16
+    // (trunk_pick: the rank-tile cell, same geometry and LDS; a build without rank tiles never picks alt and names ALT = 0 here)
+    constexpr int BAL = crl_tower::RankTiles<128, 4, 1, 0, 0, 0>::value ? 1 : 0;
+    if (pk.alt == 1) kern = bits ? crl_tower::k_trunk_x16<128, 4, 1, BAL, 1> : crl_tower::k_trunk_x16<128, 4, 0, BAL, 1>;
     if (dev_index) {
         // the list form (hybrid precision: the boards the single-MFMA pass could not decide): the split kernels
         // with their boards taken from the list the kernel finds in its `out` slot
@@ -1415,7 +1431,7 @@ int crl_reply_margin(void *hip_stream, const void *dev_priors_f32, const int32_t
 int crl_trunk_kernel_name(int filters, int n_boards, int flags, char *buf, int buf_len)
 {
     if ((filters != 64 && filters != 128 && filters != 256) || n_boards < 4 || !buf || buf_len < 1 ||
-        (flags & ~(CRL_TRUNK_BITPLANES | CRL_TRUNK_SPLIT)))
+        (flags & ~(CRL_TRUNK_BITPLANES | CRL_TRUNK_SPLIT | CRL_TRUNK_BALANCE)))
         return fail(nullptr, CRL_ERR_ARG, "crl_trunk_kernel_name: bad argument");
     if (trunk_is_layerwise(filters, flags)) {
         // one forward = k_layer_expand + the stem + 2 launches per block; the block convolutions dominate
@@ -1425,9 +1441,9 @@ int crl_trunk_kernel_name(int filters, int n_boards, int flags, char *buf, int b
                  nb, nb, (flags & CRL_TRUNK_BITPLANES) ? 1 : 0, nb);
         return CRL_OK;
     }
-    const TrunkPick pk = trunk_pick(filters, n_boards, flags & CRL_TRUNK_SPLIT);
-    snprintf(buf, (size_t)buf_len, "k_trunk_x16<%d, %d, %d, 0, %d, %d, %d, 0>", filters, pk.nb,
-             (flags & CRL_TRUNK_BITPLANES) ? 1 : 0, pk.pair, pk.group, (flags & CRL_TRUNK_SPLIT) ? 1 : 0);
+    const TrunkPick pk = trunk_pick(filters, n_boards, flags);
+    snprintf(buf, (size_t)buf_len, "k_trunk_x16<%d, %d, %d, %d, %d, %d, %d, 0>", filters, pk.nb,
+             (flags & CRL_TRUNK_BITPLANES) ? 1 : 0, pk.alt, pk.pair, pk.group, (flags & CRL_TRUNK_SPLIT) ? 1 : 0);
     return CRL_OK;
 }
 

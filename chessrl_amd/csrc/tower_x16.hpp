@@ -184,6 +184,37 @@ struct RankTiles {
 #endif
 static_assert(CRL_TRUNK_DMA_PHASE >= -1 && CRL_TRUNK_DMA_PHASE <= 3, "CRL_TRUNK_DMA_PHASE: 0 .. 3");
 
+// Rank tiles, ALT = 1 ("partner balance"): work moves from the wave that reaches every tap sync first -- the older wave
+// of the SIMD, w < 4, which wins the issue arbitration and then idles at the barrier -- to its partner w + 4, by two
+// independent compile-time choices (tools/ubench/trunk_r3.hip times each alone and both against ALT = 0):
+//   CRL_TRUNK_ALT_EDGE  1: the upper half owns the edge ranks, slots -> ranks {0, 7, 1, 6}, and skips the rank-0 block in
+//                       the dy = -1 taps and the rank-7 block in the dy = +1 taps; the lower half owns ranks {2, 3, 4, 5}
+//                       and never skips: 576 / 480 MFMAs per convolution instead of 528 / 528, still 112 per SIMD and
+//                       dy != 0 tap.  0: the rank halves of ALT = 0.
+//   CRL_TRUNK_ALT_REQ   1: behind a tap's sync the lower half requests its partner's four 1-KiB pieces with its own,
+//                       all eight directly behind the barrier; 2: its own four there and the partner's four a sub-step
+//                       later (where phase 2 above puts the upper half's).  The upper half then requests nothing inside
+//                       the loop and keeps no request state.  0: every wave requests its own, as ALT = 0 does.
+// No barrier and no wait moves, every output element sees the same MFMAs in the same tap and K order: the same bits.
+// The library builds edge 0, requests 2: -1.1 % of the 10 x 128 launch at 4096 boards against ALT = 0, the lower half's
+// wait at a tap sync 670 -> 247 cycles.  Edge 1 alone changes nothing (-0.1 %: the older wave still wins the issue
+// arbitration and still waits 559 cycles, the MFMAs it takes over only move inside the SIMD's pipe), with requests 2 it
+// gives -0.8 %; requests 1 is SLOWER with either (+0.9 %: eight requests in one clump keep the wave that feeds the pipe
+// first off it for 550 cycles).  docs/history/experiments.md, round 13.
+#ifndef CRL_TRUNK_ALT_EDGE
+#define CRL_TRUNK_ALT_EDGE 0
+#endif
+#ifndef CRL_TRUNK_ALT_REQ
+#define CRL_TRUNK_ALT_REQ 2
+#endif
+static_assert(CRL_TRUNK_ALT_EDGE >= 0 && CRL_TRUNK_ALT_EDGE <= 1 && CRL_TRUNK_ALT_REQ >= 0 && CRL_TRUNK_ALT_REQ <= 2,
+              "CRL_TRUNK_ALT_EDGE: 0 / 1, CRL_TRUNK_ALT_REQ: 0 .. 2");
+// edge ranks: the rank that slot s of rank half hh is
+__host__ __device__ constexpr int edge_rank(int hh, int s)
+{
+    return hh ? (s == 0 ? 0 : (s == 1 ? 7 : (s == 2 ? 1 : 6))) : 2 + s;
+}
+
 // What run_tap gets as its rank half where the half has a request schedule of its own: the sync whose requests are
 // not issued yet (its tile, its ring slot, whether the next bias row goes with them: plain integers, the taps are
 // straight-line code) and the function that issues pieces [P0, P1) of them.  Every other body gets a bare constant,
@@ -261,8 +292,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                                                        const float *__restrict__ head_b,
                                                        float *__restrict__ head_out)
 {
-    // ALT selected diagnostic variants until round 7; the slot stays so that every kernel keeps its mangled name
-    static_assert(ALT == 0, "reserved");
+    // ALT selected diagnostic variants until round 7; 1 is the partner balance of the rank tiles (above)
+    static_assert(ALT == 0 || (ALT == 1 && RankTiles<F, NB, PAIR, GROUP, SPLIT, IDX>::value), "ALT = 1: rank tiles only");
+    constexpr bool EDGE = ALT == 1 && CRL_TRUNK_ALT_EDGE != 0;
+    constexpr int REQ = ALT == 1 ? CRL_TRUNK_ALT_REQ : 0;
     typedef Geo16<F, NB, SPLIT> G;
     static_assert(!SPLIT || !GROUP, "split precision runs the plain / pair pipelines");
     constexpr int PT = G::PT, CT = G::CT;
@@ -287,7 +320,8 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
     const int rp_half = wave_u >> 2;                    // RP: 0 = ranks 0-3 (slot = rank), 1 = ranks 7-4
     const int board = RP ? 2 * ((wave >> 1) & 1) + (r >> 3) : board_w;           // RP: per lane
     // position of the lane in block 0 and the step to the next block, in positions (= activation rows)
-    const int pos0 = RP ? (rp_half ? 56 : 0) + (r & 7) : pbase + r;
+    // (EDGE: the lane's file alone; the slots' ranks are the table edge_rank, see slot_pos below)
+    const int pos0 = EDGE ? (r & 7) : (RP ? (rp_half ? 56 : 0) + (r & 7) : pbase + r);
     const int pstep = RP ? (rp_half ? -8 : 8) : 16;
     const int n_convs = 1 + 2 * n_blocks;
     // SPLIT: two weight parts per tap (the planes of Whi, then of Wlo)
@@ -361,6 +395,15 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
     const int zero_q = lds_base + G::ZERO_OFF + q * 16;
     const int act_row0 = board * G::ABOARD + pos0 * G::AROW;           // the lane's row in block 0
     const int row_step = pstep * G::AROW;               // bytes from a block's row to the next block's
+    // block pt's distance from block 0's row, in positions and in bytes of activation rows
+    auto slot_pos = [&](int pt) {
+        if constexpr (EDGE) return 8 * (rp_half ? edge_rank(1, pt) : edge_rank(0, pt));
+        else return pstep * pt;
+    };
+    auto slot_row = [&](int pt) {
+        if constexpr (EDGE) return 8 * G::AROW * (rp_half ? edge_rank(1, pt) : edge_rank(0, pt));
+        else return pt * row_step;
+    };
     // which lanes have an on-board neighbour to the left / right, and (per block) above / below
     // (RP: above / below is a property of the whole block -- it is computed or skipped, never masked)
     const unsigned long long xm_left = __ballot(px >= 1), xm_right = __ballot(px <= 6);
@@ -425,7 +468,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         auto run_tap = [&](auto NSC, auto DUPC, bool first_tap, bool last_tap, auto SKC, auto NSKC, auto HHC) {
             constexpr int NS = decltype(NSC)::value, DUP = decltype(DUPC)::value;
             // the request schedule of this body: the upper rank half's, if it has one of its own
-            constexpr int DPH = (RP && decltype(HHC)::value == 1) ? CRL_TRUNK_DMA_PHASE : 0;
+            constexpr int DPH = (RP && decltype(HHC)::value == 1 && REQ == 0) ? CRL_TRUNK_DMA_PHASE : 0;
             constexpr int NP = 2 * G::GL;                // pieces per wave and sync: tiles t+3 and t+4
             constexpr std::integral_constant<int, 0> p0{};
             constexpr std::integral_constant<int, 1> p1{};
@@ -433,6 +476,16 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             constexpr std::integral_constant<int, NP> pn{};
             static_assert(DPH == 0 || (PAIR && NS == 4 && DUP == 1 && G::SPT == 2 && NP == 4), "one sync per tap, in sub-step 3");
             constexpr int SK = decltype(SKC)::value ? 1 : 0, NSK = decltype(NSKC)::value ? 1 : 0;
+            // edge ranks: SKC = 2 says that the block that leaves the board is slot 1; the tap then runs slots 0 and
+            // 1 in the other order (ab[] holds the rows in that order, vtap_rows_edge), so the hand-placed schedule
+            // below still skips the FIRST block of the first half.  PM(pt): the accumulator block that is.
+            constexpr bool SW = decltype(SKC)::value == 2;
+            static_assert(!SW || (EDGE && G::PT == 4), "swapped slots belong to the edge ranks");
+            auto PM = [](int pt) constexpr { return SW && pt < 2 ? 1 - pt : pt; };
+            // ALT = 1 requests: the upper half issues none (NOREQ), the lower half its partner's with its own (REQ 1:
+            // all behind the barrier, REQ 2: the partner's where phase 2 puts them)
+            constexpr bool NOREQ = REQ != 0 && decltype(HHC)::value == 1;
+            constexpr bool LATE4 = REQ == 2 && decltype(HHC)::value == 0;
             static_assert(RP || (SK == 0 && NSK == 0), "whole blocks leave the board only with rank tiles");
             static_assert(DUP == 1 || (SPLIT && DUP == 2), "shared weight sub-steps belong to the split kernels");
             const int t_tap0 = t;
@@ -504,7 +557,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                         st_wait += s1 - s0;
                         st_syncs++;
 #endif
-                        if constexpr (DPH == 0) {
+                        if constexpr (DPH == 0 && !NOREQ) {
                         if (!bias_staged) {
                             bias_staged = true;
                             if (conv + 1 < n_convs) stage_bias_x16<G, F>(bias, lds, conv + 1, lane, wave_u);
@@ -512,6 +565,11 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                         const int slot_cur = slot_add(slot_tap, wi / G::SPT);
                         if (t + 3 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 3, tid, wave_u, slot_add(slot_cur, 3));
                         if (t + 4 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 4, tid, wave_u, slot_add(slot_cur, 4));
+                        if constexpr (REQ == 1) {         // and the pieces of the partner wave w + 4 (thread tid + 256)
+                            if (t + 3 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 3, tid + 256, wave_u + 4, slot_add(slot_cur, 3));
+                            if (t + 4 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 4, tid + 256, wave_u + 4, slot_add(slot_cur, 4));
+                        }
+                        if constexpr (LATE4) half_record(HHC, false, t, slot_cur);   // the partner's go out a sub-step later
 #if defined(CRL_TRUNK_STAMPS)
                         st_req += trunk_stamp() - s1;
 #endif
@@ -531,7 +589,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     if (t + 3 < n_tiles) stage_wtile_x16<G>(wts, lds, t + 3, tid, wave_u);
                 }
                 // phase 2: the previous tap's sync was a whole sub-step ago
-                if constexpr (DPH == 2 && i == 0) { if (!first_tap) half_pieces(HHC, p0, pn); }
+                if constexpr ((DPH == 2 || LATE4) && i == 0) { if (!first_tap) half_pieces(HHC, p0, pn); }
                 // ---- half 0: position blocks [0, HP)
                 fetch_xb(IC);
                 wait_lgkm<HP>();                         // xa and w[cur] have landed
@@ -540,7 +598,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     const bool now = i == 0 ? !first_tap : last_tap;
                     static_for<SK * CT, HP * CT>([&](auto KC) {
                         constexpr int k = decltype(KC)::value, pt = k / CT, ct = k % CT;
-                        acc[pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xa[pt], acc[pt][ct], 0, 0, 0);
+                        acc[PM(pt)][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xa[pt], acc[PM(pt)][ct], 0, 0, 0);
                         if constexpr (k == SK * CT) { if (now) half_pieces(HHC, p0, p1); }
                         if constexpr (k == SK * CT + 1) { if (now) half_pieces(HHC, p1, p2); }
                     });
@@ -549,12 +607,12 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 for (int pt = SK; pt < HP; pt++)
 #pragma unroll
                     for (int ct = 0; ct < CT; ct++)
-                        acc[pt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xa[pt], acc[pt][ct], 0, 0, 0);
+                        acc[PM(pt)][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[cur][ct], xa[pt], acc[PM(pt)][ct], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // phase 1 (and a layer's last tap in phase 2): the partner wave is back in its MFMAs
                 if constexpr (DPH == 1 && i == NS - 1) half_pieces(HHC, p0, pn);
-                if constexpr (DPH == 2 && i == NS - 1) { if (last_tap) half_pieces(HHC, p0, pn); }
+                if constexpr ((DPH == 2 || LATE4) && i == NS - 1) { if (last_tap) half_pieces(HHC, p0, pn); }
                 // ---- half 1: position blocks [HP, PT); prefetch the next sub-step
                 constexpr bool wrap = i + 1 >= NS;
                 bool issued = false;
@@ -631,6 +689,23 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
             for (int pt = 0; pt < PT; pt++) {
                 const unsigned long long m = xm & (dy < 0 ? ym_up[pt] : (dy > 0 ? ym_down[pt] : ~0ull));
                 const int row = inb + pt * row_step;
+                asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(dst[pt]) : "v"(zrow), "v"(row), "s"(m));
+            }
+        };
+        // the same with edge ranks, for tap v of rank half hh: block pt is slot pt -- in the upper half's dy = +1 taps
+        // slots 0 and 1 the other way round, the rank-7 block first (run_tap, SW) -- and its row lies
+        // 8 edge_rank(hh, slot) rows behind the lane's file in rank 0: a constant per body.  A rank test there is none:
+        // a block is on the board as a whole or it is skipped (its row is then computed and never read).
+        auto vtap_rows_edge = [&](auto HC, auto VC, int (&dst)[PT]) {
+            constexpr int hh = decltype(HC)::value, v = decltype(VC)::value;
+            constexpr int dy = v / 3 - 1, dx = v % 3 - 1, shift = 8 * dy + dx;
+            const int zrow = zero_q + ((r_tap + shift) & 15) * G::ZSTRIDE;
+            const int inb = base0_tap + shift * G::AROW;
+            const unsigned long long m = dx < 0 ? xm_left : (dx > 0 ? xm_right : ~0ull);
+#pragma unroll
+            for (int pt = 0; pt < PT; pt++) {
+                const int slot = (hh == 1 && dy > 0 && pt < 2) ? 1 - pt : pt;
+                const int row = inb + 8 * edge_rank(hh, slot) * G::AROW;
                 asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(dst[pt]) : "v"(zrow), "v"(row), "s"(m));
             }
         };
@@ -723,7 +798,8 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                     asm volatile("" : "+v"(base0_tap), "+v"(r_tap));
                 };
                 fresh();
-                vtap_rows(0, ab[1]);
+                if constexpr (EDGE) vtap_rows_edge(HC, std::integral_constant<int, 0>{}, ab[1]);
+                else vtap_rows(0, ab[1]);
                 // pieces [P0, P1) of the 2 GL that tiles t+3, t+4 of the recorded sync are, the bias row in front of piece 0
                 TrunkDmaSync dma_sync;
                 auto dma_pieces = [&](auto P0C, auto P1C) {
@@ -737,7 +813,8 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                             if (dma_sync.bias && conv + 1 < n_convs) stage_bias_x16<G, F>(bias, lds, conv + 1, lane, wave_u);
                         }
                         if (dma_sync.t + k < n_tiles)
-                            stage_wpiece_x16<G>(wts, lds, dma_sync.t + k, tid, wave_u, slot_add(dma_sync.slot, k), p % G::GL);
+                            stage_wpiece_x16<G>(wts, lds, dma_sync.t + k, REQ == 2 ? tid + 256 : tid, REQ == 2 ? wave_u + 4 : wave_u,
+                                                slot_add(dma_sync.slot, k), p % G::GL);   // (REQ 2: the partner's, from the lower half)
                     });
 #if defined(CRL_TRUNK_STAMPS)
                     st_req += trunk_stamp() - s0;
@@ -747,13 +824,15 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 const RankHalfDma<hh, decltype(dma_pieces)> half{dma_sync, dma_pieces};
                 static_for<0, 9>([&](auto VC) {
                     constexpr int v = decltype(VC)::value;
-                    constexpr bool sk = hh == 0 ? v < 3 : v >= 6;
-                    constexpr bool nsk = v + 1 < 9 && (hh == 0 ? v + 1 < 3 : v + 1 >= 6);
+                    // 0 = no block leaves the board, 1 = slot 0 does, 2 = slot 1 does (edge ranks: the upper half's rank 7)
+                    constexpr int sk = EDGE ? (hh == 0 ? 0 : (v < 3 ? 1 : (v >= 6 ? 2 : 0))) : ((hh == 0 ? v < 3 : v >= 6) ? 1 : 0);
+                    constexpr bool nsk = v + 1 < 9 && (EDGE ? hh == 1 && (v + 1 < 3 || v + 1 >= 6) : (hh == 0 ? v + 1 < 3 : v + 1 >= 6));
 #pragma unroll
                     for (int pt = 0; pt < PT; pt++) ab[0][pt] = ab[1][pt];
                     fresh();
-                    vtap_rows(v + 1 < 9 ? v + 1 : 0, ab[1]);
-                    run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == 8, std::integral_constant<bool, sk>{},
+                    if constexpr (EDGE) vtap_rows_edge(HC, std::integral_constant<int, (v + 1 < 9 ? v + 1 : 0)>{}, ab[1]);
+                    else vtap_rows(v + 1 < 9 ? v + 1 : 0, ab[1]);
+                    run_tap(std::integral_constant<int, 4>{}, once, v == 0, v == 8, std::integral_constant<int, sk>{},
                             std::integral_constant<bool, nsk>{}, half);
                     slot_tap = slot_add(slot_tap, 4 / G::SPT);
                 });
@@ -810,7 +889,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         // channel blocks 2g, 2g+1 of a position block: 8 consecutive channels per lane, one 16-byte write
         auto store_pair = [&](int pt, int g, const half4 &lo, const half4 &hi) {
             *reinterpret_cast<__attribute__((address_space(3))) half8 *>(
-                lds + act_row0 + pt * row_step + (obase + 32 * g + 8 * q) * 2) =
+                lds + act_row0 + slot_row(pt) + (obase + 32 * g + 8 * q) * 2) =
                 half8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         };
         const half4 zero4 = {(_Float16)0, (_Float16)0, (_Float16)0, (_Float16)0};
@@ -824,7 +903,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
                 lo8[j] = (_Float16)(a[j] - (float)hi8[j]);
                 lo8[4 + j] = (_Float16)(b[j] - (float)hi8[4 + j]);
             }
-            lds_byte *dst = lds + act_row0 + pt * row_step + (obase + 32 * g + 8 * q) * 2;
+            lds_byte *dst = lds + act_row0 + slot_row(pt) + (obase + 32 * g + 8 * q) * 2;
             *reinterpret_cast<__attribute__((address_space(3))) half8 *>(dst) = hi8;
             *reinterpret_cast<__attribute__((address_space(3))) half8 *>(dst + G::LO_OFF) = lo8;
         };
@@ -907,7 +986,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
     if (!IDX && out) {
 #pragma unroll
         for (int pt = 0; pt < PT; pt++) {
-            const int p = pos0 + pstep * pt;
+            const int p = pos0 + slot_pos(pt);
 #pragma unroll
             for (int ct = 0; ct < CT; ct++) {
                 const int o0 = obase + G::chan_of(ct, 0) + 8 * q;
@@ -945,7 +1024,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_x16(const unsigned char *__res
         for (int pt = 0; pt < PT; pt++)
 #pragma unroll
             for (int k = 0; k < 3; k++)
-                scratch[(((board * 64 + pos0 + pstep * pt) * 3) + k) * NC + (obase / (16 * CT)) * 4 + q] = part[pt][k];
+                scratch[(((board * 64 + pos0 + slot_pos(pt)) * 3) + k) * NC + (obase / (16 * CT)) * 4 + q] = part[pt][k];
         wait_lgkm<0>();
         __builtin_amdgcn_s_barrier();
         for (int i = tid; i < G::NB * 64 * 3; i += 512) {

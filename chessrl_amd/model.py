@@ -389,7 +389,9 @@ class ChessModel(object):
             raise _lib.HipLibraryError("the weight image of precision mode %r is not packed (model built with "
                                        "precision=%r): use set_precision() or precision='auto'"
                                        % ("f16x3" if split else "f16", self.precision_requested))
-        flags = (_lib.TRUNK_BITPLANES if bits else 0) | (_lib.TRUNK_SPLIT if split else 0)
+        # (TRUNK_BALANCE: the partner-balance kernel where this batch has one -- 128 filters, four boards per workgroup --
+        # and nothing elsewhere; the same bits, csrc/tower_x16.hpp ALT = 1)
+        flags = (_lib.TRUNK_BITPLANES if bits else 0) | (_lib.TRUNK_SPLIT if split else _lib.TRUNK_BALANCE)
         ws = self._trunk_workspace(bp) if split else None
         ev = self._trunk_event("f16x3" if split else "f16")
         _lib.trunk_forward_x(self.filters, flags, planes, image, self._wbias, trunk, bp, self.blocks, self._head_w,

@@ -498,9 +498,14 @@ int  crl_trunk_forward(void *hip_stream, int filters, const void *dev_planes_f16
  * and lightly trained towers but not for sharp ones; model.py:31-63 runs fp32).  The weight image
  * then lists, per conv and spatial tap, the planes of Whi and then the planes of Wlo = fp16(W - Whi),
  * each in the plane order above (twice the size of the plain image; a Whi plane serves hi.Whi and
- * lo.Whi while it sits in LDS). */
+ * lo.Whi while it sits in LDS).
+ * CRL_TRUNK_BALANCE = where the kernel of this filter count, batch and precision tiles the board by ranks (128 filters,
+ * four boards per workgroup, one MFMA per product), its partner-balance instantiation runs (csrc/tower_x16.hpp, ALT = 1:
+ * the wave of each SIMD that reaches a tap's sync first requests the weight tiles for both); everywhere else the flag
+ * changes nothing.  Same outputs bit for bit; crl_trunk_kernel_name reports which kernel a flag combination gets. */
 #define CRL_TRUNK_BITPLANES 1
 #define CRL_TRUNK_SPLIT 2
+#define CRL_TRUNK_BALANCE 4
 int  crl_trunk_forward_x(void *hip_stream, int filters, int flags, const void *dev_planes,
                          const void *dev_wtiles_f16, const void *dev_bias_f32, void *dev_out_f32,
                          int n_boards, int n_blocks, const void *dev_head_w_f32,

@@ -13,6 +13,10 @@
 // compare them) and alternate the binaries as above; the last column is a hash of head_out, equal across all of them.
 // -DCRL_TRUNK_STAMPS (with -DCRL_TRUNK_DMA_PHASE=0 .. 2) adds a diagnostic section: in-kernel cycle stamps around the tap
 // sync and around the weight requests, per rank half (tower_x16.hpp).  Read that build's shares, never its run time.
+// Round 13: the partner balance of that kernel (tower_x16.hpp, ALT = 1: CRL_TRUNK_ALT_EDGE 0 / 1, CRL_TRUNK_ALT_REQ 0 .. 2).  Every
+// binary holds the production kernel (ALT = 0) and ONE balance variant and times them alternately, three times each in the
+// 10 x 128 section, against the production kernel's head_out; the stamps build reads both.  Build one binary per variant
+// (-DCRL_TRUNK_ALT_EDGE=1 -DCRL_TRUNK_ALT_REQ=0 -o trunk_r3_e1r0, ...) and run them in one call on one device.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I chessrl_amd/csrc tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3
 // hipcc ... -DCRL_TRUNK_RANKPAIR=0 tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3_boards
 // hipcc ... -DCRL_TRUNK_DMA_PHASE=0 tools/ubench/trunk_r3.hip -o tools/ubench/trunk_r3_phase0
@@ -29,6 +33,7 @@ typedef void (*kern_t)(const unsigned char *, const unsigned char *, const float
                        const float *, const float *, float *);
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 
+constexpr int BAL = RankTiles<128, 4, 1, 0, 0, 0>::value ? 1 : 0;      // the partner balance exists with rank tiles only
 struct Bufs { unsigned char *planes, *wts; float *bias, *head_w, *head_b, *head_out; };
 static uint32_t rng_state = 12345;
 static uint32_t rnd() { rng_state = rng_state * 1664525u + 1013904223u; return rng_state >> 8; }
@@ -93,16 +98,20 @@ int main(int argc, char **argv)
 {
     const int boards = argc > 1 ? atoi(argv[1]) : 4096, reps = argc > 2 ? atoi(argv[2]) : 20;
     std::vector<float> ref, out;
-    for (int rep = 0; rep < 2; rep++) {
+    char balance[96];
+    snprintf(balance, sizeof balance, "x16<128,4> pair balance (ALT 1: edge %d, requests %d)", CRL_TRUNK_ALT_EDGE, CRL_TRUNK_ALT_REQ);
+    for (int rep = 0; rep < 3; rep++) {
         Bufs b = make(128, 10, boards, 1);
         printf("== 10 x 128, %d boards (pass %d), production = %s tiles\n", boards, rep,
                RankTiles<128, 4, 1, 0, 0, 0>::value ? "rank" : "board");
         const int lds = Geo16<128, 4>::lds_bytes(ring_slots<4, 1, 0>());
         run("x16<128,4> pair (production)", k_trunk_x16<128, 4, 1, 0, 1>, lds, 4, 128, 10, boards, reps, b, ref, nullptr);
+        if (BAL) run(balance, k_trunk_x16<128, 4, 1, BAL, 1>, lds, 4, 128, 10, boards, reps, b, out, &ref);
         run("x16<128,4> pair (production) again", k_trunk_x16<128, 4, 1, 0, 1>, lds, 4, 128, 10, boards, reps, b, out, &ref);
     }
 #if defined(CRL_TRUNK_STAMPS)
-    {   // per wave [loop, sync wait, requests, syncs, one stamp]: means over the workgroups, per rank half (waves 0-3 / 4-7)
+    for (int alt = 0; alt <= BAL; alt++) {   // per wave [loop, sync wait, requests, syncs, one stamp]: means over the workgroups, per rank half (waves 0-3 / 4-7)
+        const kern_t kern = alt ? k_trunk_x16<128, 4, 1, BAL, 1> : k_trunk_x16<128, 4, 1, 0, 1>;
         Bufs b = make(128, 10, boards, 1);
         const int lds = Geo16<128, 4>::lds_bytes(ring_slots<4, 1, 0>()), n_wg = boards / 4;
         const size_t n_dbg = (size_t)n_wg * 8 * 5;
@@ -110,9 +119,9 @@ int main(int argc, char **argv)
         CK(hipMalloc(&d_dbg, n_dbg * 8));
         CK(hipMemset(d_dbg, 0, n_dbg * 8));
         CK(hipMemcpyToSymbol(HIP_SYMBOL(crl_trunk_stamp_buf), &d_dbg, sizeof d_dbg));
-        CK(hipFuncSetAttribute((const void *)k_trunk_x16<128, 4, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         for (int i = 0; i < 3; i++)
-            hipLaunchKernelGGL((k_trunk_x16<128, 4, 1, 0, 1>), dim3(n_wg), dim3(512), lds, 0, b.planes, b.wts, b.bias, nullptr, 10, b.head_w, b.head_b, b.head_out);
+            hipLaunchKernelGGL(kern, dim3(n_wg), dim3(512), lds, 0, b.planes, b.wts, b.bias, nullptr, 10, b.head_w, b.head_b, b.head_out);
         CK(hipDeviceSynchronize());
         std::vector<unsigned long long> dbg(n_dbg);
         CK(hipMemcpy(dbg.data(), d_dbg, n_dbg * 8, hipMemcpyDeviceToHost));
@@ -122,13 +131,14 @@ int main(int argc, char **argv)
                 for (int w = 4 * half; w < 4 * half + 4; w++)
                     for (int k = 0; k < 5; k++) sum[k] += (double)dbg[((size_t)wg * 8 + w) * 5 + k];
             const double nw = 4.0 * n_wg, syncs = sum[3] / nw, self = sum[4] / nw;
-            printf("stamps phase %d, rank half %d, mean per wave: loop %.0f cycles, %.0f tap syncs; per sync: vmcnt wait + barrier %.0f, "
+            printf("stamps ALT %d (edge %d, requests %d) phase %d, rank half %d, mean per wave: loop %.0f cycles, %.0f tap syncs; per sync: vmcnt wait + barrier %.0f, "
                    "weight requests %.0f (one stamp's own %.0f taken off each); per convolution of 9 taps: %.0f and %.0f of %.0f\n",
-                   CRL_TRUNK_DMA_PHASE, half, sum[0] / nw, syncs, sum[1] / nw / syncs - self, sum[2] / nw / syncs - self, self,
+                   alt, alt ? CRL_TRUNK_ALT_EDGE : 0, alt ? CRL_TRUNK_ALT_REQ : 0, CRL_TRUNK_DMA_PHASE, half, sum[0] / nw, syncs, sum[1] / nw / syncs - self, sum[2] / nw / syncs - self, self,
                    9 * (sum[1] / nw / syncs - self), 9 * (sum[2] / nw / syncs - self), sum[0] / nw / 21);
         }
     }
 #endif
+    if (getenv("ONLY128")) return 0;                    // the balance variants: the 10 x 128 sections alone
     {
         Bufs b = make(256, 20, boards, 1);
         printf("== 20 x 256, %d boards\n", boards);
