@@ -354,45 +354,97 @@ def test_hybrid_mode_searches_the_trees_of_the_split_precision_mode():
     (visits, value sums, priors, stored replies) are those of the pure f16x3 search bit for bit -- for two
     consecutive moves under one captured hipGraph --, a minority of the S1 boards went through the fall-back,
     and the pure f16 search -- the negative control -- does NOT reproduce them (its replies differ somewhere)."""
-    from chessrl_amd.engine import LockstepEngine
-    from chessrl_amd.model import ChessModel
     _, planes = _positions()
     sharp = tower_oracle.calibrated_weights(6, 64, planes[:512], seed=7)
     G, sims = 512, 64
-    rng = np.random.RandomState(11)
-    target = rng.randint(0, 120, size=G)
-    picks = rng.random_sample((int(target.max()), G))
-    out = {}
-    for mode in ("f16x3", "hybrid", "f16"):
-        model = ChessModel(weights=sharp, precision=mode)
-        model.HYBRID_MIN_BOARDS = 0                                  # (batches this small would run plain f16x3)
-        eng = LockstepEngine(model, G, sims)
-        eng.reset()
-        _random_playouts(eng, target, picks)                         # the same random playouts for every mode
-        eng.search(sims)
-        first = eng.root_children()
-        # a second move under the same captured graph (the list's counter must start from zero at every step:
-        # a 4-byte memset node did not replay on this stack and the list overflowed from the second move on)
-        chosen = np.where(first["nchild"] > 0, np.maximum(first["visits"].argmax(1), 0), -1).astype(np.int32)
-        eng.advance(chosen)
-        eng.search(sims)
-        if mode == "hybrid":
-            lst = model._fallback[G].cpu().numpy()
-            assert 0 <= lst[0] <= G and len(set(lst[4:4 + lst[0]].tolist())) == lst[0]      # one step's list, no repeats
-        out[mode] = (first, eng.ctx.counters(), model.fallback_boards() if mode == "hybrid" else 0, eng.root_children())
-        eng.close()
+    target, picks = _playout_plan(G)
+    out = {mode: _two_moves(sharp, mode, G, sims, target, picks) for mode in ("f16x3", "hybrid", "f16")}
     for k in (0, 3):
-        a, b = out["f16x3"][k], out["hybrid"][k]
-        assert np.array_equal(a["nchild"], b["nchild"]) and np.array_equal(a["visits"], b["visits"])
-        assert np.array_equal(a["values"].view(np.uint64), b["values"].view(np.uint64))
-        assert np.array_equal(a["priors"].view(np.uint32), b["priors"].view(np.uint32))
-        assert np.array_equal(a["replies"], b["replies"]) and np.array_equal(a["moves"], b["moves"])
+        _assert_same_trees(out["f16x3"][k], out["hybrid"][k])
     a = out["f16x3"][0]
     s1 = out["hybrid"][1]["sims"]
     fb = out["hybrid"][2]
     print("hybrid: %d of %d S1 boards evaluated twice (%.1f %%)" % (fb, s1, 100.0 * fb / s1))
     assert 0 < fb < 0.3 * s1
     c = out["f16"][0]
+    assert not (np.array_equal(a["replies"], c["replies"]) and np.array_equal(a["visits"], c["visits"]))
+
+
+def _playout_plan(G):
+    """(plies per game, the pick of every ply): the random playouts of the hybrid search tests"""
+    rng = np.random.RandomState(11)
+    target = rng.randint(0, 120, size=G)
+    picks = rng.random_sample((int(target.max()), G))
+    return target, picks
+
+
+def _two_moves(weights, mode, G, sims, target, picks, margin=None):
+    """Two consecutive searched moves of ``G`` games in precision ``mode`` (``margin``: instead of the probe's reply
+    margin): (root children after the first search, the counters, boards evaluated twice, root children after the
+    second search, the device list of the last step, the reply margin in force)."""
+    from chessrl_amd.engine import LockstepEngine
+    from chessrl_amd.model import ChessModel
+    model = ChessModel(weights=weights, precision=mode)
+    model.HYBRID_MIN_BOARDS = 0                                      # (batches this small would run plain f16x3)
+    if margin is not None:
+        model.reply_margin = margin
+        model._publish_reply_margin()                                # (before the engine is built)
+    eng = LockstepEngine(model, G, sims)
+    eng.reset()
+    _random_playouts(eng, target, picks)                             # the same random playouts for every mode
+    eng.search(sims)
+    first = eng.root_children()
+    # a second move under the same captured graph (the list's counter must start from zero at every step:
+    # a 4-byte memset node did not replay on this stack and the list overflowed from the second move on)
+    chosen = np.where(first["nchild"] > 0, np.maximum(first["visits"].argmax(1), 0), -1).astype(np.int32)
+    eng.advance(chosen)
+    eng.search(sims)
+    lst = None
+    if mode == "hybrid":
+        lst = model._fallback[G].cpu().numpy()
+        assert 0 <= lst[0] <= G and len(set(lst[4:4 + lst[0]].tolist())) == lst[0]          # one step's list, no repeats
+    out = (first, eng.ctx.counters(), model.fallback_boards() if mode == "hybrid" else 0, eng.root_children(), lst,
+           model.reply_margin)
+    eng.close()
+    return out
+
+
+def _assert_same_trees(a, b):
+    assert np.array_equal(a["nchild"], b["nchild"]) and np.array_equal(a["visits"], b["visits"])
+    assert np.array_equal(a["values"].view(np.uint64), b["values"].view(np.uint64))
+    assert np.array_equal(a["priors"].view(np.uint32), b["priors"].view(np.uint32))
+    assert np.array_equal(a["replies"], b["replies"]) and np.array_equal(a["moves"], b["moves"])
+
+
+@pytest.mark.parametrize("blocks,filters", [(2, 256), (3, 128)])
+def test_hybrid_mode_searches_the_trees_of_the_split_precision_mode_at_128_and_256_filters(blocks, filters):
+    """The same claim where the indexed launch is another kernel: 128 filters (the fused indexed kernel at depth) and 256
+    (the layer-wise kernels under the list: one board per workgroup for a step's list of at most 256 boards, two beyond).
+    512 games x 32 simulations, two consecutive moves under one captured hipGraph, on a sharp net.  Three hybrid-side
+    searches against pure f16x3: with EVERY board of two or more legal moves listed (a margin no gap reaches: lists
+    beyond 256 boards; the kernels alone decide this one), with the product's margin (lists of at most 256 boards; the
+    product's claim), and pure f16 as the negative control."""
+    _, planes = _positions()
+    sharp = tower_oracle.calibrated_weights(blocks, filters, planes[:512], seed=7)
+    G, sims = 512, 32
+    target, picks = _playout_plan(G)
+    want = _two_moves(sharp, "f16x3", G, sims, target, picks)
+    every = _two_moves(sharp, "hybrid", G, sims, target, picks, margin=1e9)
+    s1 = every[1]["sims"]
+    print("hybrid %dx%d, everything listed: last step's list %d boards; %d of %d S1 boards evaluated twice (%.1f %%)"
+          % (blocks, filters, every[4][0], every[2], s1, 100.0 * every[2] / s1))
+    assert every[4][0] > 256                                         # 256 filters: two boards per workgroup
+    for k in (0, 3):
+        _assert_same_trees(want[k], every[k])
+    got = _two_moves(sharp, "hybrid", G, sims, target, picks)
+    s1 = got[1]["sims"]
+    print("hybrid %dx%d, margin %.3e: last step's list %d boards; %d of %d S1 boards evaluated twice (%.1f %%)"
+          % (blocks, filters, got[5], got[4][0], got[2], s1, 100.0 * got[2] / s1))
+    assert 0 < got[4][0] <= 256                                      # 256 filters: one board per workgroup
+    assert got[2] > 0
+    for k in (0, 3):
+        _assert_same_trees(want[k], got[k])
+    a, c = want[0], _two_moves(sharp, "f16", G, sims, target, picks)[0]
     assert not (np.array_equal(a["replies"], c["replies"]) and np.array_equal(a["visits"], c["visits"]))
 
 
